@@ -2,6 +2,7 @@
 """Benchmark: audio clips/s (MFCC -> logits) on 1..8 MI355X, one process per GPU.
 
   python bench.py [--gpus N --steps K --warmup W --workload od_pipeline|si_pipeline|od_features|noise_gate]
+                  [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no torchrun environment, bench.py starts
 `python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py` as a child
@@ -15,7 +16,11 @@ A step = one pass of the hot path over one batch of synthetic clips already resi
   si_pipeline (config 4): 65 536 x 1.5 s clips / GPU, MFCC+delta+delta-delta -> SI-NET, K = 630.
   od_features (config 2): the front-end kernel alone, 4 096 x 2.5 s clips / GPU.
   noise_gate: the stationary noise gate on 4 096 x 2.5 s clips / GPU.
-Prints ONE JSON line (rank 0) with roofline + cpu_baseline objects.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the value,
+`ms_per_step` and the stage table / roofline the timed steps' own HIP events give.  --dump-outputs DIR
+also writes what the last timed step computed as DIR/<name>.npy.  --full adds the legs that take runs
+of their own: the CPU baselines, the exact-f32 leg, the front-end roofline, the oracle parity sample,
+the range guard and the batch-1 latency probe.
 """
 import argparse
 import json
@@ -66,6 +71,13 @@ def parse():
     ap.add_argument('--workload', default='od_pipeline',
                     choices=['od_pipeline', 'si_pipeline', 'od_features', 'noise_gate'])
     ap.add_argument('--clips', type=int, default=None, help='clips per GPU')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the last timed step\'s outputs as DIR/<name>.npy (float32; a fixed '
+                         'seeded sample of the clips where the whole output is over the size budget)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the CPU baselines, the exact-f32 leg, the front-end roofline, the '
+                         'oracle parity sample, the range guard and the batch-1 latency probe '
+                         '(the --no-* options below drop single legs of it)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-f32', action='store_true', help='skip the exact-f32 precision leg')
     ap.add_argument('--no-parity', action='store_true', help='skip the oracle parity sample')
@@ -280,6 +292,27 @@ def parity_sample(ctx, wl, pcm, probs, argmax, W, mb, clip_len, k=24, fe_out=Non
     return out
 
 
+DUMP_BUDGET_BYTES = 48 * 1000 * 1000   # all .npy files of one --dump-outputs together
+
+
+def dump_outputs(out_dir, outputs, budget=None, index_name='clip_index', seed=20261015):
+    """outputs: {name: tensor [n, ...]} of the last timed step -> out_dir/<name>.npy as float32.
+    When all rows together are over the budget (DUMP_BUDGET_BYTES), the same seeded sample of rows
+    (clips) of every array is written, and the rows' indices as <index_name>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = next(iter(outputs.values())).shape[0]
+    row_bytes = sum(4 * (t.numel() // n) for t in outputs.values())
+    k = min(n, (DUMP_BUDGET_BYTES if budget is None else budget) // row_bytes)
+    idx = None
+    if k < n:
+        idx = np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+        np.save(os.path.join(out_dir, index_name + '.npy'), idx.astype(np.float64))
+        idx = torch.from_numpy(idx).to(next(iter(outputs.values())).device)
+    for name, t in outputs.items():
+        a = (t if idx is None else t[idx]).to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def main():
     args = parse()
     world_env = int(os.environ.get('WORLD_SIZE', '1'))
@@ -293,7 +326,7 @@ def main():
 
     # CPU baseline first, before this process touches a GPU (child processes, pinned cores)
     cpu = None
-    if rank == 0 and world_env == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world_env == 1 and not args.no_cpu_baseline:
         from oracle import cpu_baseline
         cpu = cpu_baseline.run_modes(wl, args.cpu_seconds)
 
@@ -380,16 +413,31 @@ def main():
     roof_conv = (roofline(prof, wl, mb, PREC_F16X3, 'conv')
                  if roof['kernel'] != 'conv' and prof.get('conv', (0, 0, 0))[1] else None)
     stages = stage_table(prof)
-    range_ok = True
-    try:
-        ctx.range_check()
-    except _lib.MmlaError:
-        range_ok = False
+    if args.dump_outputs and rank == 0:
+        if pipeline:
+            outputs = {'probs': probs, 'argmax': argmax}
+        elif wl == 'noise_gate':
+            outputs = {'nr_out': nr_out}
+        else:
+            outputs = {'norm': norm, 'zcr': zcr}
+        if pipeline and world > 1:   # rank 0's shard, and the whole batch's probabilities it gathered
+            dump_outputs(args.dump_outputs, outputs, DUMP_BUDGET_BYTES // 2)
+            dump_outputs(args.dump_outputs, {'gathered_probs': gathered}, DUMP_BUDGET_BYTES // 2,
+                         'gathered_index')
+        else:
+            dump_outputs(args.dump_outputs, outputs)
+    range_ok = None
+    if args.full:
+        range_ok = True
+        try:
+            ctx.range_check()
+        except _lib.MmlaError:
+            range_ok = False
 
     # the exact-f32 arithmetic on the same batch (N = 1): value and roofline beside the 3xFP16 one,
     # and how many argmax labels the two arithmetics disagree on
     f32 = None
-    if pipeline and world == 1 and not args.no_f32:
+    if args.full and pipeline and world == 1 and not args.no_f32:
         am16 = argmax.clone()
         ctx.set_precision(PREC_F32)
         steps32 = max(1, min(args.steps, 2))
@@ -404,7 +452,7 @@ def main():
 
     # front-end roofline on the same clips (config 2 measurement) for the OD pipeline
     fe = None
-    if wl == 'od_pipeline' and rank == 0:
+    if args.full and wl == 'od_pipeline' and rank == 0:
         n_fe = min(clips, 4096)
         nrm = torch.empty((n_fe, 128, 151), dtype=torch.float32, device='cuda')
         zc = torch.empty((n_fe, 151), dtype=torch.float32, device='cuda')
@@ -428,7 +476,7 @@ def main():
         fe['roofline']['traffic'], fe['roofline']['traffic_source'] = pmc_traffic('od_features', 'od_fe', n_fe)
 
     parity = None
-    if rank == 0 and not args.no_parity:
+    if args.full and rank == 0 and not args.no_parity:
         if wl == 'noise_gate':
             from oracle import noisereduce as onr
             idx = sample_indices(clips, clips, 6)[:8]
@@ -445,7 +493,7 @@ def main():
     # window per predict, record_on_pc.py:139-160): median of 20 after 5 warmups, outside the
     # timed region; informational (the headline is the batched throughput above)
     latency = None
-    if pipeline and world == 1 and not args.no_latency:
+    if args.full and pipeline and world == 1 and not args.no_latency:
         one = np.ascontiguousarray(pcm[:1].cpu().numpy())
         call = ctx.od_pipeline if wl == 'od_pipeline' else ctx.si_pipeline
         ts = []

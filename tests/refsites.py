@@ -1,9 +1,9 @@
 """The reference's hot-path call-site statements that reach TensorFlow, as the statement text the
 drop-in tests execute against ``mmla_audio_amd.tf_compat`` ("executes the reference's own
 lines verbatim").  Each entry is (reference file, first line, statements); the CPU test
-``test_tf_compat_cpu.py::test_call_site_text_matches_reference`` checks the text against
-``/root/reference`` when it is present, so these are the reference's lines, dedented, and nothing
-else.  They are a few API calls, the interface under test -- not a reference source file."""
+``test_tf_compat_cpu.py::test_call_site_text_matches_reference`` checks the text against the digests
+of the reference's own lines (tests/golden/refsites_sha256.json), so these are the reference's lines,
+dedented, and nothing else.  They are a few API calls, the interface under test -- not a reference source file."""
 
 OD_REALTIME = ('OverlapDetection/scripts/record_on_pc.py', 156, """\
 image = tf.io.read_file(features_image_path2)

@@ -1,5 +1,5 @@
 """VERDICT r5 missing #1: the reference's own TensorFlow call-site statements (tests/refsites.py, the
-text pinned against /root/reference by test_tf_compat_cpu.py) executed unchanged with
+text pinned against the reference's own lines by test_tf_compat_cpu.py) executed unchanged with
 ``tf = mmla_audio_amd.tf_compat`` on the GPU path:
 
 * OD real time ``record_on_pc.py:88`` (load) + ``:156-160`` (PNG read -> decode -> stack -> predict ->

@@ -2,6 +2,8 @@
 against the reference's own ``plt.imsave`` files (od_png_golden.npz) and against PIL for every colour
 type / bit depth / scanline filter, ``tf.stack(...).numpy()``, ``tf.keras.models.load_model``'s
 missing-weights behaviour, and that the call-site text the GPU test executes is the reference's."""
+import hashlib
+import json
 import os
 import struct
 import zlib
@@ -15,17 +17,20 @@ import refsites
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(REPO, 'tests', 'golden')
-REFERENCE = '/root/reference'
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason='reference checkout absent')
 @pytest.mark.parametrize('site', refsites.ALL, ids=lambda s: f'{os.path.basename(s[0])}:{s[1]}')
 def test_call_site_text_matches_reference(site):
+    """the statements' text, line for line and stripped of surrounding white space, has the SHA-256
+    digest recorded from the reference's own lines at that place (golden/make_refsites.py)"""
     path, line, text = site
-    lines = open(os.path.join(REFERENCE, path)).read().split('\n')
+    pinned = {(e['file'], e['line']): e for e in
+              json.load(open(os.path.join(GOLDEN, 'refsites_sha256.json')))}
+    ref = pinned[(path, line)]
     want = text.rstrip('\n').split('\n')
-    got = lines[line - 1:line - 1 + len(want)]
-    assert [g.strip() for g in got] == [w.strip() for w in want]
+    assert len(want) == ref['lines']
+    got = hashlib.sha256('\n'.join(w.strip() for w in want).encode('utf-8')).hexdigest()
+    assert got == ref['sha256']
 
 
 def test_decode_png_of_reference_files(od_golden):
