@@ -89,5 +89,5 @@ MMLA_DEV T wave_sum(T v) {
 MMLA_DEV void wave_stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // Kernel launch wrappers are declared extern "C++" here and defined in the .hip files; the C ABI
-// (capi.cpp) calls them.
+// (net_runners.cpp, pipeline.cpp, capi.cpp) calls them.
 struct OdFeTables;  // device constant tables for the OD front-end

@@ -33,7 +33,7 @@ struct ConvH3Args {
   int sc_cin;            // multiple of 16
   int sc_h;              // Conv1D: input rows per clip
   // 1 / (2^4 activation scale x the power-of-two weight scale of conv_h3_split_weights): per weight
-  // tensor, so that any finite checkpoint fits the fp16 split (capi.cpp pick_wscale)
+  // tensor, so that any finite checkpoint fits the fp16 split (weights.cpp pick_wscale)
   float unscale;
   float sc_unscale;
 };

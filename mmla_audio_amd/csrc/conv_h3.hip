@@ -43,7 +43,7 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 constexpr int NT = 256;
 constexpr int BM = 128;
 constexpr float ACT_SCALE = 16.0f;      // 2^4: staged activations
-// weights are split at a per-tensor power-of-two scale (conv_h3_split_weights, capi.cpp pick_wscale:
+// weights are split at a per-tensor power-of-two scale (conv_h3_split_weights, weights.cpp pick_wscale:
 // 2^8 for the usual |w| in [1/16, 255.9)); the epilogue multiplies by a.unscale = 2^-4 / that scale
 constexpr float ACT_RANGE = 65504.0f / ACT_SCALE;   // largest finite fp16 / the activation scale
 // The B fragments by raw buffer loads from a wave-uniform descriptor (voffset = the

@@ -1,0 +1,294 @@
+// libmmla internals shared by the C ABI's translation units: the context, the weight structs, the
+// workspace slots and the error / launch macros.
+//   context.cpp      context, profiler, workspace; create / destroy / setters / profile entry points
+//   weights.cpp      take_*, mmla_load_weights
+//   net_runners.cpp  conv_spatial, lstm_run, run_od_net, run_si_net (which kernel runs which block)
+//   pipeline.cpp     staging, micro-batching, the range guard; feature / forward / pipeline entry points
+//   capi.cpp         the auxiliary entry points
+// All but mmla_ctx (the type include/mmla.h names) lives in namespace mmla, which is not exported.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/mmla.h"
+#include "nr.h"
+#include "od_fe.h"
+#include "si_fe.h"
+#include "vad.h"
+
+namespace mmla __attribute__((visibility("hidden"))) {
+
+constexpr int OD_H = 128, OD_W = 151, OD_PIX = OD_H * OD_W;
+constexpr int OD_IMG = OD_PIX * 3;
+constexpr int SI_T = 256, SI_D = 39;
+constexpr int SI_NEED_SAMPLES = 160 * 259 + 400;   // frames 0..259 (delta-delta reach)
+constexpr int CH[9] = {32, 32, 32, 64, 64, 64, 128, 128, 128};
+constexpr bool POOL[9] = {true, false, false, true, false, false, true, false, false};
+
+struct ConvW {
+  float* wt = nullptr;
+  float* bias = nullptr;
+  uint16_t* wh = nullptr;   // 3xFP16 split weights [tap][cout_pad][cin_pad] (spatial convs only)
+  uint16_t* wl = nullptr;
+  uint16_t* fh = nullptr;   // fused res_block layout [cout][kpad], k = tap * cin + ci (resblk.hip)
+  uint16_t* fl = nullptr;
+  int kh = 0, kw = 0, cin = 0, cout = 0, cout_pad = 0, cin_pad = 0, kpad = 0;
+  float wscale = 256.0f;    // power-of-two scale of the fp16 hi/lo split (pick_wscale)
+  float unscale() const { return 1.0f / (16.0f * wscale); }   // x the 2^4 activation scale
+};
+struct BnW {
+  float* scale = nullptr;
+  float* shift = nullptr;
+  int c = 0;
+};
+struct LstmW {
+  float* wcat[2] = {nullptr, nullptr};
+  float* bias[2] = {nullptr, nullptr};
+  uint16_t* wth[2] = {nullptr, nullptr};   // 3xFP16 split, transposed [1024][256 + D] (nets.hip)
+  uint16_t* wtl[2] = {nullptr, nullptr};
+  float ws[2] = {256.0f, 256.0f};          // per-direction split scale (pick_wscale)
+};
+// one res unit of either network: BN -> act -> ca -> BN -> act -> cb (+ sc, the 1x1 stride-2 shortcut
+// of the pool units).  OD: ca = Conv2D(3x3), cb = Conv2D((4,1)); SI: both Conv1D(3)
+struct ResUnitW {
+  BnW bn_in, bn_mid;
+  ConvW ca, cb, sc;
+};
+struct OdNet {
+  ConvW stem;
+  ResUnitW blk[9];
+  LstmW lstm;
+  float* head_w = nullptr;
+  float* head_b = nullptr;
+};
+struct SiNet {
+  ConvW stem;
+  ResUnitW unit[9];
+  BnW final_bn;
+  LstmW lstm;
+  ConvW dense;
+  int k = 0, head = 0;
+};
+
+struct ProfRec {
+  int stage;
+  hipEvent_t a, b;
+  double work;
+};
+
+// Micro-batch caps (clips per internal pass).  The default (mmla_set_microbatch 0) is sized from
+// the device's free memory at call time, capped here: 16384 OD clips = 124 GB of activations
+// (4096: -2.4 % clips/s), 65536 SI clips = 9 GB (16384: -4 %).  A micro-batch whose workspace
+// allocation fails is halved and retried (down to kMinMicrobatch) instead of failing the call.
+constexpr int64_t kOdMicrobatch = 16384;
+constexpr int64_t kSiMicrobatch = 65536;
+constexpr int64_t kMinMicrobatch = 64;
+
+// host-pinned staging of small host-pointer calls (mmla_ctx::pin_small)
+constexpr size_t kPinSlotBytes = 64u << 10;
+constexpr size_t kPinInBytes = 1u << 20;
+constexpr int kPinSlots = 4;   // S_OUT0 .. S_OUT3
+
+}  // namespace mmla
+
+struct mmla_ctx {
+  bool prof_on = false;
+  std::vector<mmla::ProfRec> prof_pending;
+  std::vector<hipEvent_t> prof_pool;
+  double prof_ms[MMLA_NSTAGES] = {0};
+  double prof_work[MMLA_NSTAGES] = {0};
+  int64_t prof_n[MMLA_NSTAGES] = {0};
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipStream_t own_stream = nullptr;
+  std::string err;
+  OdFeTables* od_tables = nullptr;
+  SiFeTables* si_tables = nullptr;
+  bool od_loaded = false, si_loaded = false;
+  mmla::OdNet od;
+  mmla::SiNet si;
+  std::vector<void*> od_allocs, si_allocs;
+  std::vector<void*> ws;
+  std::vector<size_t> ws_size;
+  std::vector<size_t> ws_guard;   // MMLA_WS_GUARD: guard bytes before and after each slot (0 = none)
+  int64_t od_mb = 0, si_mb = 0;            // user caps (0 = sized from free memory)
+  int64_t od_mb_cap = mmla::kOdMicrobatch, si_mb_cap = mmla::kSiMicrobatch;   // default caps of the automatic size
+  int debug_fail_allocs = 0;   // test hook (env MMLA_DEBUG_FAIL_ALLOC at create): fail this many workspace allocations
+  int precision = MMLA_PREC_F16X3;
+  // SI res units without pooling as one fused kernel each (siu.hip); env MMLA_NO_SIU=1 at create:
+  // the two conv_h3 launches (A/B)
+  bool siu = true;
+  // ... and the pool units too (siu.hip POOL); env MMLA_NO_SIPU=1 at create: the conv_h3 pair
+  bool sipu = true;
+  // ... and the last one with the final BN + ReLU + AvgPool4 (siu.hip FIN); env MMLA_NO_SIFIN=1: the
+  // unit writes its output and bn_relu_avgpool4 runs as its own launch
+  bool sifin = true;
+  // ... and two consecutive units without pooling (2-3, 5-6, 8-9) as one kernel (siu.hip
+  // siu_chain_kernel without a pool unit: the first unit's output stays on chip); env MMLA_NO_SIPAIR=1:
+  // one launch each
+  bool sipair = true;
+  // ... and a pool unit with the two units after it (1-3, 4-6, 7-9) as one kernel (siu.hip
+  // siu_chain_kernel POOL); env MMLA_NO_SICHAIN=1: the pool unit alone, then the pair
+  bool sichain = true;
+  // fused SI pipeline: si_fe writes 40-float feature rows for the stem (env MMLA_NO_SIPAD=1: 39)
+  bool si_pad_feat = true;
+  // OD blocks 4-9 as one fused kernel each (odu.hip: t1 on chip); env MMLA_NO_ODU=1 at create: the
+  // conv_h3 pairs (A/B, bit-identical)
+  bool odu = true;
+  // OD blocks 1-3 as rolling column strips (rbs.hip); env MMLA_RB_TILE=1 at create: the 16 x 16 tile
+  // kernels of resblk.hip instead
+  bool rbs = true;
+  // batches of <= lstm_split_max clips: the 3xFP16 BiLSTM with each direction's hidden units on eight workgroups
+  // (nets.hip bilstm_h3_split_kernel); env MMLA_NO_LSTM_SPLIT=1 at create: one workgroup per direction
+  bool lstm_split = true;
+  // measured (tools/lat_split_sweep.py): OD 1.62 -> 1.53 ms at 128 clips, even at 192, +1 % at 256
+  int lstm_split_max = 128;   // env MMLA_LSTM_SPLIT_MAX (A/B; the kernel takes up to 256)
+  // test hook (env MMLA_DEBUG_LSTM_SPIN at create): the split BiLSTM's wait bound in polls (0 = default,
+  // < 0 = give up at the first wait)
+  int lstm_spin = 0;
+  // 3xFP16 range guard: kernels set range_dev[0] (device-pointer calls; sticky until
+  // mmla_range_check) or range_dev[1] (host-pointer micro-batches: re-run in exact f32) when an
+  // operand they split into fp16 is >= 65504 in magnitude or not finite.  The split BiLSTM's wait
+  // timeout (bilstm_h3_split_kernel) likewise: range_dev[3] (device-pointer calls, sticky) or
+  // range_dev[2] (host-pointer micro-batches: re-run on the one-workgroup-per-direction kernel)
+  int* range_dev = nullptr;
+  int* range_host = nullptr;                // pinned copy of range_dev[1..2]
+  // small host-pointer calls (the real-time loops' batch-1 case): the range flag and the outputs live
+  // in host-mapped coherent memory that the kernels write over the bus, so a micro-batch ends with one
+  // stream synchronisation and host memcpys instead of three or four device-to-host copies, a flag
+  // memset and a second synchronisation (each copy ≈ 20 µs of a 0.55 ms call).  env MMLA_NO_PIN_OUT=1
+  // at create: staging slots in HBM + hipMemcpyAsync (A/B)
+  bool pin_small = true;
+  int* range_map = nullptr;       // host view: [0] range flag, [1] split-BiLSTM timeout
+  int* range_map_dev = nullptr;   // device view of the same words
+  char* pin_out = nullptr;        // kPinSlots x kPinSlotBytes, host view
+  char* pin_out_dev = nullptr;
+  char* pin_in = nullptr;         // kPinInBytes of pinned input staging: one DMA for PCM + lens
+  int* range_ptr = nullptr;                 // what the current launches write (null: unguarded)
+  int* timeout_ptr = nullptr;               // where the split BiLSTM reports a timeout (null: nowhere)
+  int64_t lstm_split_reruns = 0;
+  int64_t range_reruns = 0;
+  bool od_f32_only = false, si_f32_only = false;   // weights outside the fp16 range
+  bool loading_f16_bad = false;                     // mmla_load_weights scratch
+  VadState* vad_state = nullptr;   // mmla_vad_reset: webrtcvad.Vad(mode) per stream (device)
+  int64_t vad_streams = 0;
+  NrTables* nr_tables = nullptr;   // noise gate (nr.hip): tables + the noise profile's threshold
+  float* nr_thresh = nullptr;
+  bool nr_ready = false;
+};
+
+namespace mmla __attribute__((visibility("hidden"))) {
+
+int fail(mmla_ctx* c, int code, const char* fmt, ...);
+
+#define HIPCHK(ctx, expr)                                                                        \
+  do {                                                                                           \
+    hipError_t e_ = (expr);                                                                      \
+    if (e_ != hipSuccess)                                                                        \
+      return mmla::fail(ctx, MMLA_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
+                        __FILE__, __LINE__);                                                     \
+  } while (0)
+
+#define CHK(expr)              \
+  do {                         \
+    int r_ = (expr);           \
+    if (r_ != MMLA_OK) return r_; \
+  } while (0)
+
+// ---- tracing: hipEvents around each launch when enabled (context.cpp) --------------------------
+int prof_begin(mmla_ctx* c, int stage);
+void prof_end(mmla_ctx* c, int idx, double work);
+int prof_collect(mmla_ctx* c);
+
+// launch `expr` (a hipError_t-returning launcher) as stage `st` with algorithmic work `wk`
+#define LAUNCH(c, st, wk, expr)                  \
+  do {                                           \
+    const int pi_ = mmla::prof_begin((c), (st)); \
+    HIPCHK((c), (expr));                         \
+    mmla::prof_end((c), pi_, (wk));              \
+  } while (0)
+
+// ---- growable device workspace slots (context.cpp) ---------------------------------------------
+enum Slot {
+  S_PCM = 0, S_LENS, S_IMG, S_X, S_T1, S_T2, S_T3, S_SEQ, S_HOUT, S_LOGIT, S_FEAT, S_SILENT,
+  S_OUT0, S_OUT1, S_OUT2, S_OUT3, S_IN,
+  S_NR_S, S_NR_BITS, S_NR_FMAX, S_NR_FRAMES, S_NR_ITEMS, S_NR_Y, S_NR_ROWS,
+  S_VAD_SPEECH, S_VAD_OUT, S_VAD_LENS, S_RS_TR, S_RS_WIN, S_LSTM
+};
+
+int ws_get(mmla_ctx* c, int slot, size_t bytes, void** out);
+int ws_release(mmla_ctx* c);   // free every workspace slot (after the stream drains)
+int64_t microbatch(mmla_ctx* c, bool od);
+// the end of every entry point that launched: the last error, host-mode synchronisation, guard bands
+int finish(mmla_ctx* c, bool dev);
+void free_allocs(std::vector<void*>& al);   // weights.cpp
+
+// device view of `count` input elements: the caller's pointer (device mode) or a copy in `slot`
+template <typename T>
+int in_ptr(mmla_ctx* c, const T* user, size_t count, bool dev, int slot, const T** d) {
+  *d = user;
+  if (dev || !user) return MMLA_OK;
+  void* p = nullptr;
+  CHK(ws_get(c, slot, count * sizeof(T), &p));
+  HIPCHK(c, hipMemcpyAsync(p, user, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
+  *d = static_cast<const T*>(p);
+  return MMLA_OK;
+}
+
+// device destination for an output chunk: the caller's pointer (device mode), a host-mapped slot
+// (small host-mode outputs, mmla_ctx::pin_small) or a staging slot in HBM
+template <typename T>
+int out_ptr(mmla_ctx* c, T* user, int64_t off, size_t count, bool dev, int slot, T** d) {
+  if (!user) {
+    *d = nullptr;
+    return MMLA_OK;
+  }
+  if (dev) {
+    *d = user + off;
+    return MMLA_OK;
+  }
+  if (c->pin_small && c->pin_out_dev && slot >= S_OUT0 && slot < S_OUT0 + kPinSlots &&
+      count * sizeof(T) <= kPinSlotBytes) {
+    *d = reinterpret_cast<T*>(c->pin_out_dev + (size_t)(slot - S_OUT0) * kPinSlotBytes);
+    return MMLA_OK;
+  }
+  void* p = nullptr;
+  CHK(ws_get(c, slot, count * sizeof(T), &p));
+  *d = static_cast<T*>(p);
+  return MMLA_OK;
+}
+
+template <typename T>
+int copy_back(mmla_ctx* c, T* user, int64_t off, const T* d, size_t count, bool dev) {
+  if (!user || dev) return MMLA_OK;
+  const char* dc = reinterpret_cast<const char*>(d);
+  if (c->pin_out_dev && dc >= c->pin_out_dev && dc < c->pin_out_dev + kPinSlots * kPinSlotBytes) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // the kernels wrote host memory: wait, then copy
+    std::memcpy(user + off, c->pin_out + (dc - c->pin_out_dev), count * sizeof(T));
+    return MMLA_OK;
+  }
+  HIPCHK(c, hipMemcpyAsync(user + off, d, count * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+  return MMLA_OK;
+}
+
+// ---- network runners (net_runners.cpp): device pointers, one micro-batch -----------------------
+
+// the OD 'silent' gate (record_on_pc.py:141-154) of one micro-batch: device lens (nullable) or
+// clip_len; silent output (nullable)
+struct OdGate {
+  const int32_t* lens = nullptr;
+  int clip_len = -1;   // < 0: no gate (network-only calls)
+  uint8_t* silent = nullptr;
+};
+
+int run_od_net(mmla_ctx* c, const uint8_t* img_u8, const float* img_f32, int64_t n, float* probs,
+               int32_t* argmax, OdGate gate = OdGate(), int stop = -1, const float** tap = nullptr,
+               int64_t* tap_n = nullptr);
+int run_si_net(mmla_ctx* c, const float* x, int64_t n, float* probs, int32_t* argmax,
+               const uint8_t* silent, int ldx = SI_D);
+
+}  // namespace mmla

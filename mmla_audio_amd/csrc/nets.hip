@@ -230,7 +230,7 @@ MMLA_DEV __amdgpu_buffer_rsrc_t lstm_rsrc(const void* p, uint32_t bytes) {
                                            (int)bytes, 0x00020000);
 }
 
-// weights: a per-direction power-of-two scale ws (bilstm_h3_split_weights; capi.cpp pick_wscale)
+// weights: a per-direction power-of-two scale ws (bilstm_h3_split_weights; weights.cpp pick_wscale)
 constexpr float LSTM_AS = 64.0f;    // [h | x] scale
 
 MMLA_DEV void split1(float v, _Float16& h, _Float16& l) {   // v * 2^6 = hi + lo
@@ -470,7 +470,7 @@ __global__ void __launch_bounds__(512, MT == 1 ? 4 : 2) bilstm_h3_kernel(const f
 // on the stream) and exchange buffers.  Waits are bounded at `spin` polls (LSTM_SPLIT_SPIN unless a
 // debug limit is given): thread 0 polls and the decision is broadcast through LDS, so a workgroup gives
 // up as a whole -- it sets sync[63] and *timeout_flag, writes NaN for its units and exits, and the grid
-// always drains.  The host reads the flag (capi.cpp guarded(): a host call re-runs the micro-batch on
+// always drains.  The host reads the flag (pipeline.cpp guarded(): a host call re-runs the micro-batch on
 // bilstm_h3_kernel, bit-identical; a device-pointer call reports MMLA_E_HIP at mmla_synchronize).
 // Publication: each wave's h stores, its agent-scope release fence, the workgroup barrier, then
 // thread 0's counter increment as an agent-scope RELEASE read-modify-write; the reader's thread 0

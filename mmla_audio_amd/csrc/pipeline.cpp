@@ -1,0 +1,471 @@
+// libmmla feature, forward and pipeline entry points: PCM staging, micro-batching and the 3xFP16
+// range guard around the front-end kernels and the network runners (net_runners.cpp).
+#include <algorithm>
+#include <cmath>
+#include <type_traits>
+
+#include "internal.h"
+
+using namespace mmla;
+
+namespace {
+
+// ---- PCM staging -------------------------------------------------------------------------------
+
+template <typename T>
+struct PcmT {
+  const T* p;
+  int64_t stride;
+  const int32_t* lens;
+  int32_t clip_len;
+};
+using Pcm = PcmT<int16_t>;
+
+// Device view of clips [c0, c0 + cnt): offsets in device mode, a dense copy of the first
+// `need` samples per clip in host mode.
+template <typename T>
+int stage_pcm(mmla_ctx* c, const T* pcm, int64_t c0, int64_t cnt, int64_t stride,
+              const int32_t* lens, int32_t clip_len, int need, bool dev, PcmT<T>* out) {
+  if (dev) {
+    *out = {pcm + c0 * stride, stride, lens ? lens + c0 : nullptr, clip_len};
+    return MMLA_OK;
+  }
+  int64_t width = lens ? std::min<int64_t>(need, stride) : std::min<int64_t>(need, clip_len);
+  if (width < 1) width = 1;
+  void* dp = nullptr;
+  const bool overlap = !lens && stride < width;
+  const size_t pbytes = (size_t)(overlap ? (cnt - 1) * stride + width : cnt * width) * sizeof(T);
+  const size_t loff = (pbytes + 255) & ~(size_t)255;
+  const size_t tot = loff + (lens ? cnt * sizeof(int32_t) : 0);
+  if (c->pin_small && c->pin_in && tot <= kPinInBytes) {
+    // small calls: gather into pinned memory on the host, one asynchronous DMA (host-mode bodies
+    // end with a stream synchronisation, so the staging is free again when the next one starts)
+    if (overlap) {
+      std::memcpy(c->pin_in, pcm + c0 * stride, pbytes);
+    } else {
+      for (int64_t i = 0; i < cnt; ++i)
+        std::memcpy(c->pin_in + (size_t)i * width * sizeof(T), pcm + (c0 + i) * stride, width * sizeof(T));
+    }
+    if (lens) std::memcpy(c->pin_in + loff, lens + c0, cnt * sizeof(int32_t));
+    CHK(ws_get(c, S_PCM, tot, &dp));
+    HIPCHK(c, hipMemcpyAsync(dp, c->pin_in, tot, hipMemcpyHostToDevice, c->stream));
+    const int32_t* dl = lens ? reinterpret_cast<const int32_t*>(static_cast<char*>(dp) + loff) : nullptr;
+    *out = {static_cast<T*>(dp), overlap ? stride : width, dl, (int32_t)std::min<int64_t>(clip_len, width)};
+    return MMLA_OK;
+  }
+  if (overlap) {
+    // overlapping windows of one signal (segmentation with step < window): copy the covered span
+    // once and let the kernels read window c at c * stride
+    const int64_t span = (cnt - 1) * stride + width;
+    CHK(ws_get(c, S_PCM, (size_t)span * sizeof(T), &dp));
+    HIPCHK(c, hipMemcpyAsync(dp, pcm + c0 * stride, span * sizeof(T), hipMemcpyHostToDevice,
+                             c->stream));
+    *out = {static_cast<T*>(dp), stride, nullptr, (int32_t)std::min<int64_t>(clip_len, width)};
+    return MMLA_OK;
+  }
+  CHK(ws_get(c, S_PCM, (size_t)cnt * width * sizeof(T), &dp));
+  HIPCHK(c, hipMemcpy2DAsync(dp, width * sizeof(T), pcm + c0 * stride, stride * sizeof(T),
+                             width * sizeof(T), cnt, hipMemcpyHostToDevice, c->stream));
+  int32_t* dl = nullptr;
+  if (lens) {
+    void* lp = nullptr;
+    CHK(ws_get(c, S_LENS, (size_t)cnt * sizeof(int32_t), &lp));
+    HIPCHK(c, hipMemcpyAsync(lp, lens + c0, cnt * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    dl = static_cast<int32_t*>(lp);
+  }
+  *out = {static_cast<T*>(dp), width, dl, (int32_t)std::min<int64_t>(clip_len, width)};
+  return MMLA_OK;
+}
+
+// ---- micro-batching and the 3xFP16 range guard -------------------------------------------------
+
+// body(c0, cnt) over clips [0, n) in micro-batches.  A workspace allocation failure (MMLA_E_OOM)
+// frees the context's workspaces, halves the micro-batch (unless the caller fixed it with
+// mmla_set_microbatch) and retries the same clips; the halving holds for the rest of this call only
+// (a transient OOM, e.g. while another context held memory, must not cap every later call).
+template <class F>
+int for_microbatches(mmla_ctx* c, bool od, int64_t n, F&& body) {
+  int64_t c0 = 0;
+  int64_t mb = microbatch(c, od);   // fixed for the call (unless an allocation fails)
+  while (c0 < n) {
+    const int64_t cnt = std::min(mb, n - c0);
+    const int rc = body(c0, cnt);
+    if (rc == MMLA_E_OOM && (od ? c->od_mb : c->si_mb) == 0 && cnt > kMinMicrobatch) {
+      CHK(ws_release(c));
+      mb = std::max(kMinMicrobatch, cnt / 2);   // this call only: the next call re-reads free memory
+      continue;
+    }
+    CHK(rc);
+    c0 += cnt;
+  }
+  return MMLA_OK;
+}
+
+// one micro-batch of a network call under the 3xFP16 range guard.  Device-pointer calls let the
+// kernels flag into range_dev[0] (sticky, reported by mmla_range_check / mmla_synchronize);
+// host-pointer calls check range_dev[1] after the micro-batch and re-run it in exact f32 when an
+// operand left the fp16 range.  f32_only: the model's weights are outside the fp16 range.
+template <class F>
+int guarded(mmla_ctx* c, bool dev, bool f32_only, F&& body) {
+  struct Restore {   // precision, split switch and flag targets of the context, restored on every return
+    mmla_ctx* c;
+    int prec;
+    bool split;
+    ~Restore() {
+      c->precision = prec;
+      c->lstm_split = split;
+      c->range_ptr = nullptr;
+      c->timeout_ptr = nullptr;
+    }
+  } restore{c, c->precision, c->lstm_split};
+  if (f32_only) c->precision = MMLA_PREC_F32;
+  if (c->precision != MMLA_PREC_F16X3) {
+    c->range_ptr = nullptr;
+    return body();
+  }
+  if (dev) {
+    c->range_ptr = c->range_dev;
+    c->timeout_ptr = c->range_dev + 3;
+    return body();
+  }
+  // one pass of the micro-batch; -> its range flag and split-BiLSTM timeout flag
+  auto pass = [&](bool* flagged, bool* timed_out) -> int {
+    if (c->pin_small && c->range_map) {   // the flags in host-mapped memory: no memset, no copy
+      c->range_ptr = c->range_map_dev;
+      c->timeout_ptr = c->range_map_dev + 1;
+      reinterpret_cast<volatile int*>(c->range_map)[0] = 0;   // host calls leave the stream idle
+      reinterpret_cast<volatile int*>(c->range_map)[1] = 0;
+      CHK(body());
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      *flagged = reinterpret_cast<volatile int*>(c->range_map)[0] != 0;
+      *timed_out = reinterpret_cast<volatile int*>(c->range_map)[1] != 0;
+    } else {
+      c->range_ptr = c->range_dev + 1;
+      c->timeout_ptr = c->range_dev + 2;
+      HIPCHK(c, hipMemsetAsync(c->range_ptr, 0, 2 * sizeof(int), c->stream));
+      CHK(body());
+      HIPCHK(c, hipMemcpyAsync(c->range_host, c->range_ptr, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      *flagged = c->range_host[0] != 0;
+      *timed_out = c->range_host[1] != 0;
+    }
+    return MMLA_OK;
+  };
+  bool flagged = false, timed_out = false;
+  CHK(pass(&flagged, &timed_out));
+  if (timed_out) {   // a split-BiLSTM workgroup gave up waiting (NaN outputs): the unsplit kernel,
+    c->lstm_split = false;   // the same arithmetic bit for bit
+    c->lstm_split_reruns += 1;
+    CHK(pass(&flagged, &timed_out));
+    if (timed_out) return fail(c, MMLA_E_HIP, "BiLSTM timed out without the split kernel");
+  }
+  if (flagged) {
+    c->precision = MMLA_PREC_F32;
+    c->range_ptr = nullptr;
+    c->timeout_ptr = nullptr;
+    c->range_reruns += 1;
+    CHK(body());
+  }
+  return MMLA_OK;
+}
+
+// The skeleton of the entry points over clips [0, n): null check, argument check (bad_args: the
+// message, or null), hipSetDevice, then body(c0, cnt, dev) per micro-batch with the host-mode
+// synchronisation behind it, then finish.
+//   FEATURES_*  a front-end call: in device mode one launch over the caller's buffers
+//   NET_*       a network call: needs that model's weights; every micro-batch under the range guard
+enum CallKind { FEATURES_OD, FEATURES_SI, NET_OD, NET_SI };
+
+template <class F>
+int clip_call(mmla_ctx* c, CallKind kind, int64_t n, uint32_t flags, const char* bad_args, F&& body) {
+  if (!c) return MMLA_E_INVALID;
+  if (bad_args) return fail(c, MMLA_E_INVALID, "%s", bad_args);
+  const bool od = kind == FEATURES_OD || kind == NET_OD, net = kind == NET_OD || kind == NET_SI;
+  if (net && !(od ? c->od_loaded : c->si_loaded))
+    return fail(c, MMLA_E_NOWEIGHTS, "%s weights not loaded", od ? "OD" : "SI");
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool dev = flags & MMLA_DEVICE_PTR;
+  auto once = [&](int64_t c0, int64_t cnt) -> int {
+    CHK(body(c0, cnt, dev));
+    if (!dev) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MMLA_OK;
+  };
+  if (net) {
+    CHK(for_microbatches(c, od, n, [&](int64_t c0, int64_t cnt) -> int {
+      return guarded(c, dev, od ? c->od_f32_only : c->si_f32_only, [&]() -> int { return once(c0, cnt); });
+    }));
+  } else if (dev) {
+    if (n > 0) CHK(once(0, n));
+  } else {
+    CHK(for_microbatches(c, od, n, once));
+  }
+  return finish(c, dev);
+}
+
+// algorithmic HBM bytes of one front-end launch: PCM actually consumed + outputs
+double od_fe_bytes(int64_t n, const OdFeArgs& a) {
+  const double in = a.lens ? (double)MMLA_OD_CLIP * 2 : (double)std::min(a.clip_len, MMLA_OD_CLIP) * 2;
+  const double out = (a.db ? OD_PIX * 4.0 : 0) + (a.norm ? OD_PIX * 4.0 : 0) +
+                     (a.zcr ? OD_W * 4.0 : 0) + (a.img ? (double)OD_IMG : 0);
+  return (double)n * (in + out);
+}
+
+double si_fe_bytes(int64_t n, const SiFeArgs& a) {
+  const double in = a.lens ? (double)SI_NEED_SAMPLES * 2 : (double)std::min(a.clip_len, SI_NEED_SAMPLES) * 2;
+  return (double)n * (in + SI_T * SI_D * 4.0 + (a.silent ? 1.0 : 0.0));
+}
+
+bool bad_pcm_args(const void* pcm, int64_t n, int64_t stride, const int32_t* lens, int32_t clip_len) {
+  if (n < 0 || (n > 0 && !pcm)) return true;
+  if (!lens && clip_len < 0) return true;
+  if (!lens && n > 1 && stride < 1) return true;   // stride < clip_len: overlapping windows
+  return false;
+}
+
+template <typename T>
+int od_features_common(mmla_ctx* c, const T* pcm, int64_t n, int64_t stride, const int32_t* lens,
+                       int32_t clip_len, float* db, float* norm, float* zcr, uint8_t* img,
+                       uint32_t flags) {
+  // float PCM: the front-end splits y 2^3 into fp16 hi + lo, so the kernel checks every sample it
+  // reads (the first min(len, 24000) of each clip) into a range word: device-pointer calls into the
+  // sticky word (mmla_range_check / mmla_synchronize report it), host-pointer calls into their own
+  // word, read after the micro-batch's synchronisation; only then is the micro-batch re-scanned on
+  // the host, to name the first offending sample
+  auto host_range_error = [&](int64_t c0, int64_t cnt) -> int {
+    if constexpr (std::is_same<T, float>::value) {
+      for (int64_t i = c0; i < c0 + cnt; ++i) {
+        const int64_t len = std::min<int64_t>(lens ? lens[i] : clip_len, MMLA_OD_CLIP);
+        for (int64_t j = 0; j < len; ++j)
+          if (!(std::fabs(pcm[i * stride + j]) < 8188.0f))
+            return fail(c, MMLA_E_RANGE,
+                        "float PCM clip %lld sample %lld = %g: the front-end needs |y| < 8188 (y * 8 is "
+                        "split into fp16)", (long long)i, (long long)j, (double)pcm[i * stride + j]);
+      }
+    }
+    return fail(c, MMLA_E_RANGE, "float PCM outside |y| < 8188 in clips %lld..%lld", (long long)c0,
+                (long long)(c0 + cnt - 1));
+  };
+  return clip_call(c, FEATURES_OD, n, flags, bad_pcm_args(pcm, n, stride, lens, clip_len) ? "bad pcm args" : nullptr,
+                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+    PcmT<T> p;
+    CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, MMLA_OD_CLIP, dev, &p));
+    OdFeArgs a{};
+    if constexpr (std::is_same<T, float>::value) {
+      a.pcm_f32 = p.p;
+      a.range_flag = dev ? c->range_dev : c->range_dev + 1;
+      if (!dev) HIPCHK(c, hipMemsetAsync(a.range_flag, 0, sizeof(int), c->stream));
+    } else {
+      a.pcm = p.p;
+    }
+    a.clip_stride = p.stride;
+    a.lens = p.lens;
+    a.clip_len = p.clip_len;
+    a.tables = c->od_tables;
+    CHK(out_ptr(c, db, c0 * OD_PIX, cnt * OD_PIX, dev, S_OUT0, &a.db));
+    CHK(out_ptr(c, norm, c0 * OD_PIX, cnt * OD_PIX, dev, S_OUT1, &a.norm));
+    CHK(out_ptr(c, zcr, c0 * OD_W, cnt * OD_W, dev, S_OUT2, &a.zcr));
+    CHK(out_ptr(c, img, c0 * OD_IMG, cnt * OD_IMG, dev, S_OUT3, &a.img));
+    LAUNCH(c, MMLA_STAGE_OD_FE, od_fe_bytes(cnt, a), od_fe_launch(a, cnt, c->stream));
+    CHK(copy_back(c, db, c0 * OD_PIX, a.db, cnt * OD_PIX, dev));
+    CHK(copy_back(c, norm, c0 * OD_PIX, a.norm, cnt * OD_PIX, dev));
+    CHK(copy_back(c, zcr, c0 * OD_W, a.zcr, cnt * OD_W, dev));
+    CHK(copy_back(c, img, c0 * OD_IMG, a.img, cnt * OD_IMG, dev));
+    if (std::is_same<T, float>::value && !dev) {   // the range word, once the launch has drained
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      int flag = 0;
+      HIPCHK(c, hipMemcpy(&flag, c->range_dev + 1, sizeof(int), hipMemcpyDeviceToHost));
+      if (flag) return host_range_error(c0, cnt);
+    }
+    return MMLA_OK;
+  });
+}
+
+// OD-NET over float NHWC (x_f32) or uint8 (x_u8) images
+int od_forward_common(mmla_ctx* c, const float* x_f32, const uint8_t* x_u8, int64_t n, float* probs,
+                      uint32_t flags) {
+  const bool bad = n < 0 || (n > 0 && ((!x_f32 && !x_u8) || !probs));
+  return clip_call(c, NET_OD, n, flags, bad ? "bad od_forward args" : nullptr,
+                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+    const float* df = nullptr;
+    const uint8_t* du = nullptr;
+    if (x_f32) CHK(in_ptr(c, x_f32 + c0 * OD_IMG, cnt * OD_IMG, dev, S_IN, &df));
+    else CHK(in_ptr(c, x_u8 + c0 * OD_IMG, cnt * OD_IMG, dev, S_IMG, &du));
+    float* dp;
+    CHK(out_ptr(c, probs, c0 * 2, cnt * 2, dev, S_OUT0, &dp));
+    CHK(run_od_net(c, du, df, cnt, dp, nullptr));
+    return copy_back(c, probs, c0 * 2, dp, cnt * 2, dev);
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int mmla_od_features(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
+                     const int32_t* lens, int32_t clip_len, float* db, float* norm, float* zcr,
+                     uint8_t* img, uint32_t flags) {
+  return od_features_common(c, pcm, n, stride, lens, clip_len, db, norm, zcr, img, flags);
+}
+
+int mmla_od_features_f32(mmla_ctx* c, const float* y, int64_t n, int64_t stride,
+                         const int32_t* lens, int32_t clip_len, float* db, float* norm, float* zcr,
+                         uint8_t* img, uint32_t flags) {
+  return od_features_common(c, y, n, stride, lens, clip_len, db, norm, zcr, img, flags);
+}
+
+int mmla_si_features(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
+                     const int32_t* lens, int32_t clip_len, float* feat, uint8_t* silent,
+                     uint32_t flags) {
+  const bool bad = bad_pcm_args(pcm, n, stride, lens, clip_len) || (n > 0 && !feat);
+  return clip_call(c, FEATURES_SI, n, flags, bad ? "bad pcm/feat args" : nullptr,
+                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+    Pcm p;
+    CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, SI_NEED_SAMPLES, dev, &p));
+    SiFeArgs a{};
+    a.pcm = p.p;
+    a.clip_stride = p.stride;
+    a.lens = p.lens;
+    a.clip_len = lens ? 0 : clip_len;   // true length decides T even if fewer samples are staged
+    a.tables = c->si_tables;
+    CHK(out_ptr(c, feat, c0 * SI_T * SI_D, cnt * SI_T * SI_D, dev, S_OUT0, &a.feat));
+    CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT1, &a.silent));
+    LAUNCH(c, MMLA_STAGE_SI_FE, si_fe_bytes(cnt, a), si_fe_launch(a, cnt, c->stream));
+    CHK(copy_back(c, feat, c0 * SI_T * SI_D, a.feat, cnt * SI_T * SI_D, dev));
+    return copy_back(c, silent, c0, a.silent, cnt, dev);
+  });
+}
+
+int mmla_si_features_seq(mmla_ctx* c, const int16_t* pcm, int64_t n_samples, int64_t n_windows,
+                         float* feat, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  if (n_samples < 1 || !pcm || !feat) return fail(c, MMLA_E_INVALID, "bad si_features_seq args");
+  const int64_t T = n_samples <= 400 ? 1 : 1 + (n_samples - 400 + 159) / 160;
+  if (n_windows != (T + SI_T - 1) / SI_T)
+    return fail(c, MMLA_E_INVALID, "n_windows must be ceil(T/256) = %lld", (long long)((T + 255) / 256));
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool dev = flags & MMLA_DEVICE_PTR;
+  SiFeArgs a{};
+  CHK(in_ptr(c, pcm, n_samples, dev, S_PCM, &a.pcm));
+  a.seq_len = n_samples;
+  a.tables = c->si_tables;
+  CHK(out_ptr(c, feat, 0, n_windows * SI_T * SI_D, dev, S_OUT0, &a.feat));
+  LAUNCH(c, MMLA_STAGE_SI_FE, (double)n_samples * 2 + (double)n_windows * SI_T * SI_D * 4,
+         si_fe_launch(a, n_windows, c->stream));
+  CHK(copy_back(c, feat, 0, a.feat, n_windows * SI_T * SI_D, dev));
+  return finish(c, dev);
+}
+
+int mmla_od_forward(mmla_ctx* c, const float* x, int64_t n, float* probs, uint32_t flags) {
+  return od_forward_common(c, x, nullptr, n, probs, flags);
+}
+
+int mmla_od_forward_u8(mmla_ctx* c, const uint8_t* img, int64_t n, float* probs, uint32_t flags) {
+  return od_forward_common(c, nullptr, img, n, probs, flags);
+}
+
+int mmla_si_forward(mmla_ctx* c, const float* x, int64_t n, float* probs, uint32_t flags) {
+  const bool bad = n < 0 || (n > 0 && (!x || !probs));
+  return clip_call(c, NET_SI, n, flags, bad ? "bad si_forward args" : nullptr,
+                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+    const int k = c->si.k;
+    const float* dx;
+    CHK(in_ptr(c, x + c0 * SI_T * SI_D, cnt * SI_T * SI_D, dev, S_IN, &dx));
+    float* dp;
+    CHK(out_ptr(c, probs, c0 * k, cnt * k, dev, S_OUT0, &dp));
+    CHK(run_si_net(c, dx, cnt, dp, nullptr, nullptr));
+    return copy_back(c, probs, c0 * k, dp, cnt * k, dev);
+  });
+}
+
+int mmla_od_pipeline(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
+                     const int32_t* lens, int32_t clip_len, float* probs, int32_t* argmax,
+                     uint8_t* silent, uint32_t flags) {
+  return clip_call(c, NET_OD, n, flags, bad_pcm_args(pcm, n, stride, lens, clip_len) ? "bad pcm args" : nullptr,
+                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+    Pcm p;
+    CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, MMLA_OD_CLIP, dev, &p));
+    void* pimg = nullptr;
+    CHK(ws_get(c, S_IMG, cnt * OD_IMG, &pimg));
+    OdFeArgs a{};
+    a.pcm = p.p;
+    a.clip_stride = p.stride;
+    a.lens = p.lens;
+    a.clip_len = p.clip_len;
+    a.tables = c->od_tables;
+    a.img = static_cast<uint8_t*>(pimg);
+    LAUNCH(c, MMLA_STAGE_OD_FE, od_fe_bytes(cnt, a), od_fe_launch(a, cnt, c->stream));
+    float* dp;
+    int32_t* da;
+    uint8_t* ds;
+    CHK(out_ptr(c, probs, c0 * 2, cnt * 2, dev, S_OUT0, &dp));
+    CHK(out_ptr(c, argmax, c0, cnt, dev, S_OUT1, &da));
+    CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT2, &ds));
+    OdGate g;
+    g.lens = p.lens;
+    g.clip_len = lens ? 0 : clip_len;   // the true length decides, not the staged width
+    g.silent = ds;
+    CHK(run_od_net(c, a.img, nullptr, cnt, dp, da, g));
+    CHK(copy_back(c, probs, c0 * 2, dp, cnt * 2, dev));
+    CHK(copy_back(c, argmax, c0, da, cnt, dev));
+    return copy_back(c, silent, c0, ds, cnt, dev);
+  });
+}
+
+int mmla_si_pipeline(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
+                     const int32_t* lens, int32_t clip_len, float* probs, int32_t* argmax,
+                     uint8_t* silent, uint32_t flags) {
+  return clip_call(c, NET_SI, n, flags, bad_pcm_args(pcm, n, stride, lens, clip_len) ? "bad pcm args" : nullptr,
+                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+    const int k = c->si.k;
+    Pcm p;
+    CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, SI_NEED_SAMPLES, dev, &p));
+    void* pf;
+    // the features stay on the device: rows of 40 floats when the 3xFP16 stem reads them
+    const int ldf = c->precision == MMLA_PREC_F16X3 && c->si.stem.wh && c->si.stem.cin_pad > SI_D &&
+                            c->si_pad_feat ? SI_D + 1 : SI_D;
+    CHK(ws_get(c, S_FEAT, cnt * SI_T * ldf * sizeof(float), &pf));
+    uint8_t* pso = nullptr;   // host mode: the caller's 'silent' flags through an output slot
+    if (!dev && silent) CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT2, &pso));
+    void* ps = pso;
+    if (!ps) CHK(ws_get(c, S_SILENT, cnt, &ps));
+    SiFeArgs a{};
+    a.pcm = p.p;
+    a.clip_stride = p.stride;
+    a.lens = p.lens;
+    a.clip_len = lens ? 0 : clip_len;
+    a.tables = c->si_tables;
+    a.feat = static_cast<float*>(pf);
+    a.ldf = ldf;
+    a.silent = static_cast<uint8_t*>(ps);
+    LAUNCH(c, MMLA_STAGE_SI_FE, si_fe_bytes(cnt, a), si_fe_launch(a, cnt, c->stream));
+    float* dp;
+    int32_t* da;
+    CHK(out_ptr(c, probs, c0 * k, cnt * k, dev, S_OUT0, &dp));
+    CHK(out_ptr(c, argmax, c0, cnt, dev, S_OUT1, &da));
+    CHK(run_si_net(c, a.feat, cnt, dp, da, a.silent, ldf));
+    CHK(copy_back(c, probs, c0 * k, dp, cnt * k, dev));
+    CHK(copy_back(c, argmax, c0, da, cnt, dev));
+    if (silent && dev)
+      HIPCHK(c, hipMemcpyAsync(silent + c0, a.silent, cnt, hipMemcpyDeviceToDevice, c->stream));
+    else if (silent)
+      CHK(copy_back(c, silent, c0, pso, cnt, dev));
+    return MMLA_OK;
+  });
+}
+
+int mmla_debug_od_trace(mmla_ctx* c, const float* x, int64_t n, int stage, float* out,
+                        int64_t out_floats) {
+  if (!c || !x || !out || n < 1 || stage < 0 || stage > 11) return MMLA_E_INVALID;
+  if (!c->od_loaded) return fail(c, MMLA_E_NOWEIGHTS, "OD weights not loaded");
+  HIPCHK(c, hipSetDevice(c->device));
+  const float *dx, *tap = nullptr;
+  int64_t tn = 0;
+  CHK(in_ptr(c, x, n * OD_IMG, false, S_IN, &dx));
+  CHK(run_od_net(c, nullptr, dx, n, nullptr, nullptr, OdGate(), stage, &tap, &tn));
+  if (tn > out_floats) return fail(c, MMLA_E_SHAPE, "trace stage %d needs %lld floats", stage, (long long)tn);
+  HIPCHK(c, hipMemcpyAsync(out, tap, tn * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return MMLA_OK;
+}
+
+}  // extern "C"

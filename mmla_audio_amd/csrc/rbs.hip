@@ -29,7 +29,7 @@
 // LDS (hi and lo planes): 16-B channel groups of a pixel XOR-swizzled by column (and, for block 1's
 // t1 read in pool-window order, by row parity), rows padded to a multiple of 256 B, so every
 // ds_read_b128 of the GEMMs is conflict-free (model: the MI355X guide's lane groups).  Blocks 2-3:
-// 47 KB -> three workgroups per CU; block 1: 38 KB -> four.
+// 47 KB; block 1: 51 KB, 16 KB of it GEMM 2's weights (sw2) -> three workgroups per CU (SG::MINB).
 //
 // 3xFP16 as conv_h3.hip: activations x 2^4 and weights x their power-of-two scale split into hi + lo,
 // ONE f32 accumulator per tile (hi*lo + lo*hi + hi*hi); the 2^4 is folded into the BN coefficients
@@ -103,8 +103,8 @@ struct SG {
   static constexpr int MAXT0 = (4 * XW * QPP + NT - 1) / NT;     // the prologue's 4 rows
   static constexpr int KPT = CIN / 16;                  // 16-deep k-steps per tap
   static constexpr int KS1 = 9 * KPT, KS2 = 8;
-  // block 1 keeps GEMM 2's weights in LDS to fit 3 workgroups per CU; blocks 2-3 keep them in
-  // registers at 2 (measured: deeper weight prefetch or LDS-resident GEMM 1 weights do not pay)
+  // block 1 keeps GEMM 2's weights in LDS (sw2; 51 KB in all) to fit the registers of 3 workgroups per CU;
+  // blocks 2-3 keep them in registers at 2 (measured: deeper weight prefetch or LDS-resident GEMM 1 weights do not pay)
   static constexpr bool W2L = CIN == 16;                // GEMM 2's weights in LDS
   static constexpr int MINB = CIN == 16 ? 3 : 2;        // resident workgroups per CU
   static constexpr int PF = 3;                          // GEMM 1 weight k-steps in flight

@@ -152,7 +152,7 @@ def test_small_batch_lstm_split_bit_identical(monkeypatch, n):
 @pytest.mark.parametrize('n', [1, 3, 40])
 def test_host_mapped_outputs_bit_identical(monkeypatch, n):
     """Small host-pointer calls gather their PCM (+ lens) into pinned memory for one DMA and write
-    their outputs and the range flag into host-mapped memory (capi.cpp pin_small); env
+    their outputs and the range flag into host-mapped memory (internal.h pin_small); env
     MMLA_NO_PIN_OUT=1 copies from pageable memory and stages outputs in HBM.  Same results for the
     pipelines, ragged (lens) input, overlapping windows, the front-end images and the network-only
     entry."""

@@ -1,4 +1,4 @@
-"""Out-of-bounds stores: every workspace slot framed by guard bands (MMLA_WS_GUARD=1, capi.cpp
+"""Out-of-bounds stores: every workspace slot framed by guard bands (MMLA_WS_GUARD=1, context.cpp
 ws_get); a call fails if any kernel wrote into one.  Micro-batches and batch sizes that leave
 partial tiles at the end of each buffer, OD and SI pipelines, front-ends and the noise gate."""
 import os
