@@ -70,12 +70,32 @@ MMLA_DEV float amax4(float r, float4 v) {
   return fmaxf(r, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
 }
 
+// a group's issue order, for the scheduler: NR LDS reads (a later group's fragments), then 3 MFMAs
+template <int LA, int NR>
+MMLA_DEV void odu_pin_group() {
+  if constexpr (LA > 0) {
+    if constexpr (NR > 0) __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);   // DS_READ
+    __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);                          // MFMA
+    // the region ends here: without it the scheduler fits the groups of the whole unrolled tap loop
+    // at once, sinks the reads below the MFMAs again and shares their registers
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 // H x W image, CIN -> C channels, strips of TW columns, 4 waves: WN = C / 32 waves along the output
 // channels (one 32-channel tile each, so no weight fragment is fetched twice per workgroup), WM along
 // the strip's H * TW pixels, MT 32-pixel tiles per wave
-template <int H, int W, int CIN, int C, int TW, bool POOL, int NW, int MINW>
+//
+// LA (GEMM a), LB (GEMM b): the LDS operand pipeline.  A (tap, k-step, tile) group is two
+// ds_read_b128 (hi, lo) and three MFMAs; its fragments are read LA groups ahead into LA + 1 register
+// sets and every group is pinned as "the reads of group g + LA, then the MFMAs of group g"
+// (odu_pin_group), so a read has 3 LA MFMAs before its s_waitcnt.  Depth 0 reads a group's fragments
+// right before its MFMAs and leaves the order to the scheduler (every MFMA triple then starts with an
+// LDS round trip that only the SIMD's other waves can hide).
+template <int H, int W, int CIN, int C, int TW, bool POOL, int NW, int MINW, int LA, int LB>
 __global__ void __launch_bounds__(64 * NW, MINW) odu_kernel(OduArgs a) {
   constexpr int NT = 64 * NW;
+  constexpr int NB = LA + 1;                              // GEMM a's fragment register sets
   constexpr int WN = C / 32, WM = NW / WN;
   constexpr int M = H * TW;
   constexpr int MT = M / (WM * 32);
@@ -201,9 +221,22 @@ __global__ void __launch_bounds__(64 * NW, MINW) odu_kernel(OduArgs a) {
         load_stage(ch, 0);
         __syncthreads();
       }
+      // group g = (tap * KS + s) * MT + mt of this chunk: its A fragments' LDS offset
+      constexpr int NG = 9 * KS * MT;
+      auto aoff = [&](int g) {
+        const int mt = g % MT, s = (g / MT) % KS, tap = g / (MT * KS);
+        const int dy = tap / 3, dx = tap - (tap / 3) * 3;
+        const int m = mpix[mt];
+        return buf * XBUF + (m / TW + dy) * XRP + (m % TW + dx) * LDX + 16 * s + (dx & 1 ? kx1 : kx0);
+      };
+      f16x8 fah[NB], fal[NB];
+#pragma unroll
+      for (int d = 0; d < LA; ++d) {
+        fah[d] = *reinterpret_cast<const f16x8*>(lhi + aoff(d));
+        fal[d] = *reinterpret_cast<const f16x8*>(llo + aoff(d));
+      }
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
-        const int dy = tap / 3, dx = tap - (tap / 3) * 3;
         f16x8 nbh[KS], nbl[KS];
         if (tap + 1 < 9) {   // the next tap's fragments under this tap's MFMAs
 #pragma unroll
@@ -217,13 +250,16 @@ __global__ void __launch_bounds__(64 * NW, MINW) odu_kernel(OduArgs a) {
         for (int s = 0; s < KS; ++s)
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
-            const int m = mpix[mt];
-            const int off = buf * XBUF + (m / TW + dy) * XRP + (m % TW + dx) * LDX + 16 * s + (dx & 1 ? kx1 : kx0);
-            const f16x8 ah = *reinterpret_cast<const f16x8*>(lhi + off);
-            const f16x8 al = *reinterpret_cast<const f16x8*>(llo + off);
+            const int g = (tap * KS + s) * MT + mt;
+            if (g + LA < NG) {
+              fah[(g + LA) % NB] = *reinterpret_cast<const f16x8*>(lhi + aoff(g + LA));
+              fal[(g + LA) % NB] = *reinterpret_cast<const f16x8*>(llo + aoff(g + LA));
+            }
+            const f16x8 ah = fah[g % NB], al = fal[g % NB];
             acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[s], ah, acc[mt], 0, 0, 0);
             acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s], al, acc[mt], 0, 0, 0);
             acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s], ah, acc[mt], 0, 0, 0);
+            if (g + LA < NG) odu_pin_group<LA, 2>(); else odu_pin_group<LA, 0>();
           }
         if (tap + 1 < 9) {
 #pragma unroll
@@ -313,6 +349,19 @@ __global__ void __launch_bounds__(64 * NW, MINW) odu_kernel(OduArgs a) {
         bh[s] = odu_frag(rh, (size_t)(ch * KS + s) * kstr, lofs);
         bl[s] = odu_frag(rl, (size_t)(ch * KS + s) * kstr, lofs);
       }
+      // group g = (tap * KS + s) * MT + mt of this chunk, as in GEMM a
+      constexpr int NG = 4 * KS * MT;
+      auto boff = [&](int g) {
+        const int mt = g % MT, s = (g / MT) % KS, tap = g / (MT * KS);
+        const int m = mpix[mt];
+        return ((m / TW + tap) * TW + m % TW) * LDT + ch * CK + 16 * s + koff;
+      };
+      f16x8 fah[LB + 1], fal[LB + 1];
+#pragma unroll
+      for (int d = 0; d < LB; ++d) {
+        fah[d] = *reinterpret_cast<const f16x8*>(lhi + boff(d));
+        fal[d] = *reinterpret_cast<const f16x8*>(llo + boff(d));
+      }
 #pragma unroll
       for (int tap = 0; tap < 4; ++tap) {
         f16x8 nbh[KS], nbl[KS];
@@ -328,10 +377,12 @@ __global__ void __launch_bounds__(64 * NW, MINW) odu_kernel(OduArgs a) {
         for (int s = 0; s < KS; ++s)
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
-            const int m = mpix[mt];
-            const int off = ((m / TW + tap) * TW + m % TW) * LDT + ch * CK + 16 * s + koff;
-            const f16x8 ah = *reinterpret_cast<const f16x8*>(lhi + off);
-            const f16x8 al = *reinterpret_cast<const f16x8*>(llo + off);
+            const int g = (tap * KS + s) * MT + mt;
+            if (g + LB < NG) {
+              fah[(g + LB) % (LB + 1)] = *reinterpret_cast<const f16x8*>(lhi + boff(g + LB));
+              fal[(g + LB) % (LB + 1)] = *reinterpret_cast<const f16x8*>(llo + boff(g + LB));
+            }
+            const f16x8 ah = fah[g % (LB + 1)], al = fal[g % (LB + 1)];
             if constexpr (POOL) {   // pixel rows: a register quad is one pool window
               acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[s], acc[mt], 0, 0, 0);
               acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[s], acc[mt], 0, 0, 0);
@@ -341,6 +392,7 @@ __global__ void __launch_bounds__(64 * NW, MINW) odu_kernel(OduArgs a) {
               acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s], al, acc[mt], 0, 0, 0);
               acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[s], ah, acc[mt], 0, 0, 0);
             }
+            if (g + LB < NG) odu_pin_group<LB, 2>(); else odu_pin_group<LB, 0>();
           }
         if (tap + 1 < 4) {
 #pragma unroll
@@ -427,11 +479,11 @@ __global__ void __launch_bounds__(64 * NW, MINW) odu_kernel(OduArgs a) {
   if (!(rmax < SPLIT_MAX) && a.range_flag) *a.range_flag = 1;
 }
 
-template <int H, int W, int CIN, int C, int TW, bool POOL, int NW = 4, int MINW = 2>
+template <int H, int W, int CIN, int C, int TW, bool POOL, int NW, int MINW, int LA, int LB>
 hipError_t launch(const OduArgs& a, hipStream_t s) {
   constexpr int TLW = (W + TW - 1) / TW;
   const int64_t blocks = (int64_t)a.n * TLW;
-  hipLaunchKernelGGL((odu_kernel<H, W, CIN, C, TW, POOL, NW, MINW>), dim3((unsigned)blocks), dim3(64 * NW), 0, s, a);
+  hipLaunchKernelGGL((odu_kernel<H, W, CIN, C, TW, POOL, NW, MINW, LA, LB>), dim3((unsigned)blocks), dim3(64 * NW), 0, s, a);
   return hipGetLastError();
 }
 
@@ -452,9 +504,12 @@ hipError_t odu_launch(const OduArgs& a, int h, int w, int cin, int c, bool pool,
   // strips and register budgets, measured per kernel (rocprof, one box, per 16 384-clip launch):
   // blocks 5-6 TW 4 at 3 waves per SIMD (<= 168 VGPRs, 1 spilled) 8.56 -> 7.55 ms; TW 2 with two-wave
   // workgroups 8.16 ms; 4 waves per SIMD (<= 128 VGPRs) spill 20-44 VGPRs: block 7 15.5 -> 17.2 ms,
-  // blocks 5-6 10.6 ms.  Blocks 4 and 8-9 are LDS-bound at 3 workgroups per CU (42 / 41 KB)
-  if (h == 64 && pool) return launch<64, 76, 32, 64, 2, true, 4, 4>(a, s);
-  if (h == 32 && c == 64) return launch<32, 38, 64, 64, 4, false, 4, 3>(a, s);
-  if (h == 32 && pool) return launch<32, 38, 64, 128, 2, true>(a, s);
-  return launch<16, 19, 128, 128, 4, false>(a, s);
+  // blocks 5-6 10.6 ms.  Blocks 4 and 8-9 are LDS-bound at 3 workgroups per CU (42 / 41 KB).
+  // Operand pipeline depths (LA, LB): one group ahead pays 2.2-2.4 % in blocks 5-9
+  // (168 / 133 / 165 VGPRs, no spills); block 4, with four waves per SIMD to cover its reads, gains
+  // nothing from GEMM a's and would spill 5 VGPRs at its 128 cap with GEMM b's
+  if (h == 64 && pool) return launch<64, 76, 32, 64, 2, true, 4, 4, 0, 0>(a, s);
+  if (h == 32 && c == 64) return launch<32, 38, 64, 64, 4, false, 4, 3, 1, 1>(a, s);
+  if (h == 32 && pool) return launch<32, 38, 64, 128, 2, true, 4, 2, 1, 1>(a, s);
+  return launch<16, 19, 128, 128, 4, false, 4, 2, 1, 1>(a, s);
 }

@@ -88,6 +88,16 @@ MMLA_DEV float amax4(float a, float b, float c, float d) {
   return fmaxf(fmaxf(fabsf(a), fabsf(b)), fmaxf(fabsf(c), fabsf(d)));
 }
 
+// one k-step's issue order, for the scheduler: NR LDS reads (the next step's fragments), then the
+// step's three MFMAs; the sched_barrier ends the region, so nothing is hoisted across k-steps and the
+// register footprint stays at the two fragment sets
+template <int NR>
+MMLA_DEV void rbs_pin_step() {
+  if constexpr (NR > 0) __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);   // DS_READ
+  __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);                          // MFMA
+  __builtin_amdgcn_sched_barrier(0);
+}
+
 template <int H, int W, int CIN, bool POOL>
 struct SG {
   static constexpr int XW = TW + 2;                     // halo columns w0 - 1 .. w0 + 16
@@ -106,6 +116,13 @@ struct SG {
   // block 1 keeps GEMM 2's weights in LDS (sw2; 51 KB in all) to fit the registers of 3 workgroups per CU;
   // blocks 2-3 keep them in registers at 2 (measured: deeper weight prefetch or LDS-resident GEMM 1 weights do not pay)
   static constexpr bool W2L = CIN == 16;                // GEMM 2's weights in LDS
+  // ... where a GEMM 2 k-step reads four fragments from LDS (t1 and sw2, hi and lo).  Those of step
+  // s + 1 go to a second register set and each k-step is pinned as "the reads for step s + 1, then
+  // the three MFMAs of step s" (rbs_pin_step), so a ds_read_b128 has 3 MFMAs (96 cycles) before its
+  // s_waitcnt; left to the scheduler, a source-order prefetch shares registers between the two steps
+  // and issues the reads after the first or second MFMA.  Block 1's GEMM 2: 1 540 -> 1 370 cycles per
+  // chunk.  GEMM 1 of either kernel and blocks 2-3's GEMM 2 (two reads per step) do not gain from the
+  // same pinning and keep the source-order prefetch
   static constexpr int MINB = CIN == 16 ? 3 : 2;        // resident workgroups per CU
   static constexpr int PF = 3;                          // GEMM 1 weight k-steps in flight
   static constexpr int PD = CIN == 16 ? 1 : 2;                      // input prefetch distance (chunks)
@@ -456,6 +473,10 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) rbs_kernel(Re
   // block 1's shortcut pixel of a chunk: this lane's pool window's top-left, conv row 8 k + 2 wave
   const int win = n >> 2;
   const int sc_col = w0 + 2 * win;
+  // its shortcut bias, read once: a global load inside the chunk loop would queue behind the next
+  // chunk's image prefetch (vector loads complete in issue order)
+  float bsc = 0.0f;
+  if constexpr (POOL) bsc = a.bs[n];
 
 #if RBS_TRACE
   unsigned long long tt[8];
@@ -504,7 +525,7 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) rbs_kernel(Re
     }
     __syncthreads();
     RBS_T(5);
-    // ---- GEMM 2 (weights in registers) -----------------------------------------------------------
+    // ---- GEMM 2 (weights in registers or sw2) ----------------------------------------------------
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
@@ -517,32 +538,8 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) rbs_kernel(Re
         tr[dy] = (int)min(sl, sl - (uint32_t)G::TRING);
       }
       auto to = [&](int s) { return toff<POOL>(tr[s >> 1], tj[s >> 1], pc, 2 * (s & 1) + h); };
-      f16x8 nxh = *reinterpret_cast<const f16x8*>(st + to(0));
-      f16x8 nxl = *reinterpret_cast<const f16x8*>(st + G::TPLANE + to(0));
-      f16x8 ngh, ngl;
-      if constexpr (G::W2L) {
-        ngh = *reinterpret_cast<const f16x8*>(sw2 + lofs);
-        ngl = *reinterpret_cast<const f16x8*>(sw2 + G::KS2 * 512 + lofs);
-      }
-#pragma unroll
-      for (int s = 0; s < G::KS2; ++s) {
-        const f16x8 xh = nxh, xl = nxl;
-        f16x8 gh, gl;
-        if constexpr (G::W2L) {
-          gh = ngh;
-          gl = ngl;
-        } else {
-          gh = w2h[s];
-          gl = w2l[s];
-        }
-        if (s + 1 < G::KS2) {   // the next step's fragments under this step's MFMAs
-          nxh = *reinterpret_cast<const f16x8*>(st + to(s + 1));
-          nxl = *reinterpret_cast<const f16x8*>(st + G::TPLANE + to(s + 1));
-          if constexpr (G::W2L) {
-            ngh = *reinterpret_cast<const f16x8*>(sw2 + (s + 1) * 512 + lofs);
-            ngl = *reinterpret_cast<const f16x8*>(sw2 + (G::KS2 + s + 1) * 512 + lofs);
-          }
-        }
+      // one k-step's MFMAs
+      auto step2 = [&](f16x8 xh, f16x8 xl, f16x8 gh, f16x8 gl) {
         if constexpr (POOL) {   // y: pixel rows (a register quad = one 2x2 window), channel = lane
           acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, gl, acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl, gh, acc, 0, 0, 0);
@@ -552,7 +549,37 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) rbs_kernel(Re
           acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(gh, xl, acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(gh, xh, acc, 0, 0, 0);
         }
-        __builtin_amdgcn_sched_barrier(0);
+      };
+      if constexpr (G::W2L) {
+        // block 1: the t1 and sw2 fragments of step s + 1 in a second register set, each step pinned
+        // as "four reads, three MFMAs" (SG::W2L)
+        f16x8 fxh[2], fxl[2], fgh[2], fgl[2];
+        auto fetch = [&](int s) {
+          fxh[s & 1] = *reinterpret_cast<const f16x8*>(st + to(s));
+          fxl[s & 1] = *reinterpret_cast<const f16x8*>(st + G::TPLANE + to(s));
+          fgh[s & 1] = *reinterpret_cast<const f16x8*>(sw2 + s * 512 + lofs);
+          fgl[s & 1] = *reinterpret_cast<const f16x8*>(sw2 + (G::KS2 + s) * 512 + lofs);
+        };
+        fetch(0);
+#pragma unroll
+        for (int s = 0; s < G::KS2; ++s) {
+          if (s + 1 < G::KS2) fetch(s + 1);
+          step2(fxh[s & 1], fxl[s & 1], fgh[s & 1], fgl[s & 1]);
+          if (s + 1 < G::KS2) rbs_pin_step<4>(); else rbs_pin_step<0>();
+        }
+      } else {
+        f16x8 nxh = *reinterpret_cast<const f16x8*>(st + to(0));
+        f16x8 nxl = *reinterpret_cast<const f16x8*>(st + G::TPLANE + to(0));
+#pragma unroll
+        for (int s = 0; s < G::KS2; ++s) {
+          const f16x8 xh = nxh, xl = nxl;
+          if (s + 1 < G::KS2) {   // the next step's fragments under this step's MFMAs
+            nxh = *reinterpret_cast<const f16x8*>(st + to(s + 1));
+            nxl = *reinterpret_cast<const f16x8*>(st + G::TPLANE + to(s + 1));
+          }
+          step2(xh, xl, w2h[s], w2l[s]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
       }
     }
     RBS_T(6);
@@ -599,7 +626,7 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) rbs_kernel(Re
       }
       constexpr int HP = H / 2, WP = (W + 1) / 2;
       const int co = n;
-      const float b2 = sp[2 * C + co], bs = a.bs[co];
+      const float b2 = sp[2 * C + co], bs = bsc;
       const int prow = (R / 2) * k + wave;
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {
