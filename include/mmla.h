@@ -53,6 +53,10 @@ enum mmla_head { MMLA_HEAD_SOFTMAX = 0, MMLA_HEAD_SIGMOID = 1 };
 #define MMLA_SI_FRAMES 256
 #define MMLA_SI_DIMS 39
 #define MMLA_SI_SILENT_LEN 4000
+/* speaker registration (speaker_identification.py:401-432): width of the embedding the sigmoid head is
+ * trained on, and the largest head mmla_si_head_fit trains */
+#define MMLA_SI_EMBED 512
+#define MMLA_SI_TRAIN_MAX_CLASSES 32
 
 typedef struct mmla_ctx mmla_ctx;
 
@@ -193,6 +197,42 @@ int mmla_od_forward_u8(mmla_ctx* ctx, const uint8_t* img, int64_t n, float* prob
  * speaker_identification_post_processing.py:272). */
 int mmla_si_forward(mmla_ctx* ctx, const float* x, int64_t n, float* probs, uint32_t flags);
 
+/* SI-NET up to the Bidirectional LSTM output (base_model.layers[-2].output,
+ * speaker_identification.py:403): x [n,256,39] f32 -> emb [n,512] f32.  Host or device pointers;
+ * micro-batching and the range guard as in mmla_si_forward (a host-pointer micro-batch that leaves the
+ * fp16 range re-runs in exact f32, a device-pointer call flags it).  Needs SI weights; the loaded head
+ * (K, softmax or sigmoid) does not enter the result: the Dense and head launches are skipped. */
+int mmla_si_embed(mmla_ctx* ctx, const float* x, int64_t n, float* emb, uint32_t flags);
+
+/*
+ * Speaker registration, stage 1 of transfer_learning (speaker_identification.py:407-432): fit
+ * Dense(n_classes, sigmoid) on frozen-base embeddings with categorical_crossentropy and RMSprop, as one
+ * kernel launch (si_train.hip): restart r is one workgroup that runs all epochs x ceil(n_train / batch)
+ * steps with the head and the optimiser state on chip.  Float32 arithmetic, Keras 2.6 semantics:
+ *   forward  z = e W + b, s = 1 / (1 + exp(-z))
+ *   loss     p = s / sum_k s_k, -log(clip(p_c, 1e-7, 1 - 1e-7)), mean over the batch (the last batch of
+ *            an epoch is short when n_train % batch != 0)
+ *   gradient dz_k = s_k (1 - s_k) (1 / S - [k = c] / s_c) / B, zero for a sample whose p_c is outside
+ *            the clip range; gW = E^T dz, gb = sum dz
+ *   RMSprop  rho 0.9, momentum 0, epsilon 1e-7 outside the root, accumulators from 0
+ *   history  [R, epochs, 4] = loss, acc (each batch with the weights before its update), val_loss,
+ *            val_acc (weights at the end of the epoch; NaN when n_val == 0); acc = first-index argmax
+ * (stated from Keras' published source; TensorFlow is not available here: parity with TF unpinned).
+ * emb [n_train,512], labels [n_train] in [0, n_classes); val_* [n_val] (n_val may be 0, pointers then
+ * unused); w0 [R,512,K], b0 [R,K] initial head of each restart; perm [R,epochs,n_train] the sample
+ * order of every epoch; w [R,512,K], b [R,K] the trained heads; history nullable.  Bit-reproducible,
+ * and restart r's result does not depend on n_restarts.  MMLA_E_INVALID: n_classes outside
+ * [1, MMLA_SI_TRAIN_MAX_CLASSES], batch < 1, n_train < 1, n_val < 0, n_restarts < 1, epochs < 0, and in
+ * host-pointer calls a label outside [0, K) or a perm row that is not a permutation -- with device
+ * pointers the caller guarantees both (the kernel only clamps a perm entry into [0, n_train), so a
+ * broken contract gives a wrong fit, not a read outside emb).
+ */
+int mmla_si_head_fit(mmla_ctx* ctx, const float* emb, const int32_t* labels, int64_t n_train,
+                     const float* val_emb, const int32_t* val_labels, int64_t n_val,
+                     int32_t n_classes, int32_t n_restarts, int32_t epochs, int32_t batch, float lr,
+                     const float* w0, const float* b0, const int32_t* perm, float* w, float* b,
+                     float* history, uint32_t flags);
+
 /* Fused WAV->class pipelines (no PNG, no host round trip): probs [n,K] f32 (nullable),
  * argmax [n] i32 (nullable; -1 for 'silent' clips), silent [n] u8 (nullable).  'silent' = fewer
  * than 4000 samples (lens[c], or clip_len without lens): OD record_on_pc.py:141-154 logs it and
@@ -282,7 +322,7 @@ enum mmla_stage {
   MMLA_STAGE_CONV = 2,  /* work = FLOPs (2 * MACs, unpadded) */
   MMLA_STAGE_LSTM = 3,  /* work = FLOPs */
   MMLA_STAGE_GLUE = 4,  /* stem, pooling, mean: work = FLOPs */
-  MMLA_STAGE_HEAD = 5,  /* dense + softmax / sigmoid: work = FLOPs */
+  MMLA_STAGE_HEAD = 5,  /* dense + softmax / sigmoid, mmla_si_head_fit: work = FLOPs */
   MMLA_STAGE_NR = 6     /* noise gate: work = algorithmic HBM bytes (signal in + out) */
 };
 int mmla_profile_enable(mmla_ctx* ctx, int on);

@@ -6,7 +6,8 @@ here with ctypes under the reference's own names:
 
   overlap_features_generator.OverlapFeaturesGenerator   (reference overlap_features_generator.py)
   speaker_identification.input_feature_gen / delta /
-      make_feature_experiment                           (reference speaker_identification.py)
+      make_feature_experiment / transfer_learning /
+      transfer_learning_on_experiment                   (reference speaker_identification.py)
   models.load_model(path).predict(x) / .predict_wavs    (tf.keras.models.load_model)
   distributed.sharded_predict                           (1/2/4/8 GPUs, RCCL all-gather of logits)
 
@@ -16,7 +17,7 @@ and raises if it (or a HIP device) is missing -- there is no CPU fallback.
 from . import weights, tfbundle  # noqa: F401
 
 __all__ = ['weights', 'tfbundle', 'load_model', 'OverlapFeaturesGenerator', 'input_feature_gen',
-           'delta']
+           'delta', 'transfer_learning', 'transfer_learning_on_experiment']
 
 
 def __getattr__(name):
@@ -26,7 +27,8 @@ def __getattr__(name):
     if name == 'OverlapFeaturesGenerator':
         from .overlap_features_generator import OverlapFeaturesGenerator
         return OverlapFeaturesGenerator
-    if name in ('input_feature_gen', 'delta', 'make_feature_experiment'):
+    if name in ('input_feature_gen', 'delta', 'make_feature_experiment', 'transfer_learning',
+                'transfer_learning_on_experiment'):
         from . import speaker_identification
         return getattr(speaker_identification, name)
     raise AttributeError(name)

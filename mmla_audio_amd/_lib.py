@@ -21,6 +21,7 @@ PREC_F32, PREC_F16X3 = 0, 1
 
 OD_MELS, OD_FRAMES, OD_CLIP = 128, 151, 24000
 SI_FRAMES, SI_DIMS, SI_SILENT_LEN = 256, 39, 4000
+SI_EMBED, SI_TRAIN_MAX_CLASSES = 512, 32
 
 MMLA_E_RANGE = -6
 _ERRORS = {-1: 'MMLA_E_INVALID', -2: 'MMLA_E_HIP', -3: 'MMLA_E_NOWEIGHTS', -4: 'MMLA_E_OOM',
@@ -55,6 +56,9 @@ SIGNATURES = {
     'mmla_od_forward': [_P, _P, _I64, _P, _U32],
     'mmla_od_forward_u8': [_P, _P, _I64, _P, _U32],
     'mmla_si_forward': [_P, _P, _I64, _P, _U32],
+    'mmla_si_embed': [_P, _P, _I64, _P, _U32],
+    'mmla_si_head_fit': [_P, _P, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _I32, ctypes.c_float,
+                         _P, _P, _P, _P, _P, _P, _U32],
     'mmla_od_pipeline': [_P, _P, _I64, _I64, _P, _I32, _P, _P, _P, _U32],
     'mmla_si_pipeline': [_P, _P, _I64, _I64, _P, _I32, _P, _P, _P, _U32],
     'mmla_profile_enable': [_P, ctypes.c_int],
@@ -463,6 +467,48 @@ class Context:
         self._check(self.lib.mmla_si_forward(self.h, _ptr(x), n, _ptr(probs), 0), 'mmla_si_forward')
         return probs
 
+    def si_embed(self, x):
+        """SI-NET up to the BiLSTM output (base_model.layers[-2].output): [n,256,39] -> float32
+        [n,512].  Whatever head is loaded does not enter the result."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n = x.shape[0]
+        emb = np.empty((n, SI_EMBED), np.float32)
+        self._check(self.lib.mmla_si_embed(self.h, _ptr(x), n, _ptr(emb), 0), 'mmla_si_embed')
+        return emb
+
+    def si_head_fit(self, emb, labels, val_emb, val_labels, w0, b0, perm, epochs, batch=16, lr=1e-4):
+        """Fit R sigmoid heads side by side in one launch (mmla_si_head_fit).  emb [n,512], labels
+        [n] ints; val_* likewise (None or empty: no validation set); w0 [R,512,K], b0 [R,K]; perm
+        [R,epochs,n].  -> (w [R,512,K], b [R,K], history [R,epochs,4] = loss, acc, val_loss, val_acc)"""
+        emb = np.ascontiguousarray(emb, dtype=np.float32)
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        w0 = np.ascontiguousarray(w0, dtype=np.float32)
+        b0 = np.ascontiguousarray(b0, dtype=np.float32)
+        perm = np.ascontiguousarray(perm, dtype=np.int32)
+        if w0.ndim != 3 or w0.shape[1] != SI_EMBED or b0.shape != (w0.shape[0], w0.shape[2]):
+            raise ValueError(f'w0 {w0.shape} / b0 {b0.shape}: expected [R,512,K] and [R,K]')
+        R, _, K = w0.shape
+        n = labels.shape[0]
+        if emb.shape != (n, SI_EMBED):
+            raise ValueError(f'emb {emb.shape}: expected [{n},512]')
+        if perm.shape != (R, int(epochs), n):
+            raise ValueError(f'perm {perm.shape}: expected [{R},{int(epochs)},{n}]')
+        nv = 0 if val_labels is None else len(val_labels)
+        ve = vl = None
+        if nv:
+            ve = np.ascontiguousarray(val_emb, dtype=np.float32)
+            vl = np.ascontiguousarray(val_labels, dtype=np.int32)
+            if ve.shape != (nv, SI_EMBED):
+                raise ValueError(f'val_emb {ve.shape}: expected [{nv},512]')
+        w = np.empty_like(w0)
+        b = np.empty_like(b0)
+        hist = np.empty((R, int(epochs), 4), np.float32)
+        self._check(self.lib.mmla_si_head_fit(
+            self.h, _ptr(emb), _ptr(labels), n, _ptr(ve), _ptr(vl), nv, K, R, int(epochs), int(batch),
+            float(lr), _ptr(w0), _ptr(b0), _ptr(perm), _ptr(w), _ptr(b), _ptr(hist), 0),
+            'mmla_si_head_fit')
+        return w, b, hist
+
     def od_pipeline(self, pcm, lens=None):
         """-> (probs [n,2], argmax [n] (-1 = 'silent'), silent [n] bool)."""
         a, ln, L = self._pcm(pcm, lens)
@@ -546,6 +592,18 @@ class Context:
     def si_forward_dev(self, x, n, probs):
         self._check(self.lib.mmla_si_forward(self.h, x, n, probs, MMLA_DEVICE_PTR),
                     'mmla_si_forward(dev)')
+
+    def si_embed_dev(self, x, n, emb):
+        self._check(self.lib.mmla_si_embed(self.h, x, n, emb, MMLA_DEVICE_PTR), 'mmla_si_embed(dev)')
+
+    def si_head_fit_dev(self, emb, labels, n_train, val_emb, val_labels, n_val, n_classes, n_restarts,
+                        epochs, batch, lr, w0, b0, perm, w, b, history=0):
+        """mmla_si_head_fit on device buffers: the caller guarantees labels in [0, K) and that every
+        perm row is a permutation (unchecked: the kernel only clamps a perm entry into range)"""
+        self._check(self.lib.mmla_si_head_fit(
+            self.h, emb, labels, n_train, val_emb or None, val_labels or None, n_val, n_classes,
+            n_restarts, epochs, batch, float(lr), w0, b0, perm, w, b, history or None,
+            MMLA_DEVICE_PTR), 'mmla_si_head_fit(dev)')
 
 
 _default = {}

@@ -4,7 +4,7 @@
 //   weights.cpp      take_*, mmla_load_weights
 //   net_runners.cpp  conv_spatial, lstm_run, run_od_net, run_si_net (which kernel runs which block)
 //   pipeline.cpp     staging, micro-batching, the range guard; feature / forward / pipeline entry points
-//   capi.cpp         the auxiliary entry points
+//   capi.cpp         the auxiliary entry points and the head trainer (mmla_si_head_fit)
 // All but mmla_ctx (the type include/mmla.h names) lives in namespace mmla, which is not exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -217,7 +217,8 @@ enum Slot {
   S_PCM = 0, S_LENS, S_IMG, S_X, S_T1, S_T2, S_T3, S_SEQ, S_HOUT, S_LOGIT, S_FEAT, S_SILENT,
   S_OUT0, S_OUT1, S_OUT2, S_OUT3, S_IN,
   S_NR_S, S_NR_BITS, S_NR_FMAX, S_NR_FRAMES, S_NR_ITEMS, S_NR_Y, S_NR_ROWS,
-  S_VAD_SPEECH, S_VAD_OUT, S_VAD_LENS, S_RS_TR, S_RS_WIN, S_LSTM
+  S_VAD_SPEECH, S_VAD_OUT, S_VAD_LENS, S_RS_TR, S_RS_WIN, S_LSTM,
+  S_TRAIN   // mmla_si_head_fit: every host-pointer operand, carved from one slot
 };
 
 int ws_get(mmla_ctx* c, int slot, size_t bytes, void** out);
@@ -289,6 +290,6 @@ int run_od_net(mmla_ctx* c, const uint8_t* img_u8, const float* img_f32, int64_t
                int32_t* argmax, OdGate gate = OdGate(), int stop = -1, const float** tap = nullptr,
                int64_t* tap_n = nullptr);
 int run_si_net(mmla_ctx* c, const float* x, int64_t n, float* probs, int32_t* argmax,
-               const uint8_t* silent, int ldx = SI_D);
+               const uint8_t* silent, int ldx = SI_D, const float** tap = nullptr);
 
 }  // namespace mmla

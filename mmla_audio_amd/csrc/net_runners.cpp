@@ -443,8 +443,9 @@ namespace mmla __attribute__((visibility("hidden"))) {
 
 // ldx: the features' row stride (39, or 40 from si_fe with a zero 40th column: the stem then stages
 // 16-B aligned rows, conv_h3's float4 path, bit-identical -- its weights' padded channels are zero)
+// tap != null: stop after the BiLSTM and return its output (base_model.layers[-2].output) in *tap
 int run_si_net(mmla_ctx* c, const float* x, int64_t n, float* probs, int32_t* argmax,
-               const uint8_t* silent, int ldx) {
+               const uint8_t* silent, int ldx, const float** tap) {
   const SiNet& W = c->si;
   const size_t big = (size_t)n * SI_T * 32;
   float *X, *T1, *XP, *R, *SEQ, *H, *L;
@@ -546,6 +547,10 @@ int run_si_net(mmla_ctx* c, const float* x, int64_t n, float* probs, int32_t* ar
                                    SEQ, c->stream));
   LAUNCH(c, MMLA_STAGE_LSTM, lstm_flops(n, t / 4, 128),
          lstm_run(c, W.lstm, SEQ, n, t / 4, H));
+  if (tap) {   // mmla_si_embed: the BiLSTM output [n, 512] itself, no Dense, no head
+    *tap = H;
+    return MMLA_OK;
+  }
   if (h3 && W.dense.wh && W.dense.cin % 32 == 0) {
     // Dense(K) as a 1x1 conv over the clips on the 3xFP16 path (conv_h3 Conv1D tiles of 128 clips):
     // all cout_pad columns are written (the padding columns: zero weights and bias), so the logits

@@ -377,6 +377,20 @@ int mmla_si_forward(mmla_ctx* c, const float* x, int64_t n, float* probs, uint32
   });
 }
 
+int mmla_si_embed(mmla_ctx* c, const float* x, int64_t n, float* emb, uint32_t flags) {
+  const bool bad = n < 0 || (n > 0 && (!x || !emb));
+  return clip_call(c, NET_SI, n, flags, bad ? "bad si_embed args" : nullptr,
+                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+    const float *dx, *h = nullptr;
+    CHK(in_ptr(c, x + c0 * SI_T * SI_D, cnt * SI_T * SI_D, dev, S_IN, &dx));
+    CHK(run_si_net(c, dx, cnt, nullptr, nullptr, nullptr, SI_D, &h));
+    // the BiLSTM's own output buffer (S_HOUT) handed out: one copy, to the device or to the host
+    HIPCHK(c, hipMemcpyAsync(emb + c0 * MMLA_SI_EMBED, h, (size_t)cnt * MMLA_SI_EMBED * sizeof(float),
+                             dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    return MMLA_OK;
+  });
+}
+
 int mmla_od_pipeline(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
                      const int32_t* lens, int32_t clip_len, float* probs, int32_t* argmax,
                      uint8_t* silent, uint32_t flags) {

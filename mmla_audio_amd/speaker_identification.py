@@ -3,7 +3,10 @@
 ``input_feature_gen`` (:372-398) and ``delta`` (:141-151) keep their names and return values;
 the MFCC / delta / delta-delta / pad-to-256 path runs in the ``si_fe`` HIP kernel (float64 math).
 ``make_feature_experiment`` (:317-369), used by the registration/transfer-learning callers, keeps
-its chunked output layout.
+its chunked output layout.  ``transfer_learning`` (:401-477) and ``transfer_learning_on_experiment``
+(:480-503), the speaker registration of ``record_on_pc.py:340-346``, run the frozen base once
+(``si_embed``) and fit the sigmoid head in one persistent kernel (``si_train.hip``), then write the
+deployed model with ``tfbundle.save_deployed``.
 """
 import math
 import os
@@ -92,6 +95,144 @@ def make_feature_experiment(wav_files, device=None):
     y = binarizer(train_y, dim=len(set(train_y)))
     speaker_id = {str(int(np.argmax(y[i]))): train_y[i] for i in range(len(train_y))}
     return np.asarray(train_x), y, speaker_id
+
+
+def get_wav_files(wav_path):
+    """speaker_identification.py:57-66: every .wav / .WAV under wav_path of at least 240000 bytes
+    (7.5 s); sorted here, where the reference keeps os.walk's order, so that the speaker numbering
+    does not depend on the file system."""
+    wav_files = []
+    for dirpath, _, filenames in os.walk(wav_path):
+        for filename in filenames:
+            if filename.endswith('.wav') or filename.endswith('.WAV'):
+                path = os.sep.join([dirpath, filename])
+                if os.stat(path).st_size >= 240000:
+                    wav_files.append(path)
+    return sorted(wav_files)
+
+
+def _stratified_split(rng, idx, labels, ratio):
+    """-> (keep, held_out) index arrays: per class round(ratio * n_c) samples held out, but at least
+    one on each side for every class with two or more samples (a class of one stays in `keep`)"""
+    keep, out = [], []
+    for c in np.unique(labels[idx]):
+        members = idx[labels[idx] == c]
+        members = members[rng.permutation(len(members))]
+        n_out = 0
+        if len(members) >= 2:
+            n_out = min(max(int(round(ratio * len(members))), 1), len(members) - 1)
+        out.append(members[:n_out])
+        keep.append(members[n_out:])
+    return np.sort(np.concatenate(keep)), np.sort(np.concatenate(out))
+
+
+def _fit_plan(labels, K, seed, test_split_ratio, epochs, restarts):
+    """Everything random about one registration, drawn with numpy from `seed`: the stratified test
+    split (only when test_split_ratio > 0) and 70/30 validation split, and per restart the
+    Glorot-uniform initial head (limit sqrt(6 / (512 + K)), zero bias) and the sample order of every
+    epoch.  Restart r's draws come from their own generator, so they do not depend on `restarts`.
+    Neither sklearn's train_test_split nor TensorFlow's initialiser and shuffle streams are reproduced:
+    the same seed gives a different (equally distributed) split, head and order than the reference.
+    -> dict(train, val, test index arrays; w0 [R,512,K] f32; b0 [R,K] f32; perm [R,epochs,n_train] i32)"""
+    labels = np.asarray(labels)
+    rng = np.random.default_rng([int(seed), 0])
+    idx = np.arange(len(labels))
+    test = np.zeros(0, np.int64)
+    if test_split_ratio > 0:
+        idx, test = _stratified_split(rng, idx, labels, test_split_ratio)
+    train, val = _stratified_split(rng, idx, labels, 0.3)
+    lim = math.sqrt(6.0 / (_lib.SI_EMBED + K))
+    w0 = np.empty((restarts, _lib.SI_EMBED, K), np.float32)
+    perm = np.empty((restarts, epochs, len(train)), np.int32)
+    for r in range(restarts):
+        rr = np.random.default_rng([int(seed), 1 + r])
+        w0[r] = rr.uniform(-lim, lim, size=(_lib.SI_EMBED, K))
+        for e in range(epochs):
+            perm[r, e] = rr.permutation(len(train))
+    return dict(train=train, val=val, test=test, w0=w0, b0=np.zeros((restarts, K), np.float32), perm=perm)
+
+
+def fit_head(emb, labels, val_emb, val_labels, w0, b0, perm, epochs, batch=16, lr=1e-4, device=None):
+    """Train Dense(K, sigmoid) heads on fixed embeddings, one kernel launch for the whole fit
+    (``mmla_si_head_fit``: categorical_crossentropy + RMSprop as Keras 2.6 defines them, float32).
+    emb [n,512], labels [n] class indices, val_* the validation set (None: none); w0 [R,512,K] /
+    b0 [R,K] the initial head and perm [R,epochs,n] the sample order of each restart.
+    -> (w [R,512,K], b [R,K], history [R,epochs,4] = loss, acc, val_loss, val_acc)."""
+    ctx = _lib.default_context(device) if device is None or isinstance(device, int) else device
+    return ctx.si_head_fit(emb, labels, val_emb, val_labels, w0, b0, perm, epochs, batch, lr)
+
+
+def transfer_learning(_x, _y, seed, _test_split_ratio, base_model_path, final_model_path, *,
+                      epochs=500, restarts=1, allow_synthetic=False, device=None):
+    """speaker_identification.py:401-477, stage 1: freeze the base model below its Dense head, fit
+    Dense(dim, sigmoid, name='customized_dense') on the registration windows (500 epochs, batch 16,
+    RMSprop 1e-4), save the deployed model to final_model_path and return its accuracy (on the test
+    split when _test_split_ratio > 0, else on the validation split, as the reference).  The base runs
+    once (``si_embed``), the whole fit is one kernel launch; `restarts` heads are trained side by side
+    and the one with the best final validation accuracy (ties: lower validation loss) is kept.
+
+    Not done: stage 2 (:438-447), which un-freezes the network for 20 epochs of RMSprop at 1e-6 --
+    the saved base tensors equal the loaded ones bit for bit.  Splits, initial head and shuffles come
+    from numpy (``_fit_plan``), not from sklearn / TensorFlow streams."""
+    from . import models, tfbundle, weights
+    _x = np.asarray(_x)
+    _y = np.asarray(_y)
+    if _y.ndim != 2 or len(_y) != len(_x) or len(_y) == 0:
+        raise ValueError(f'_y {_y.shape}: expected one one-hot row per window of _x {_x.shape}')
+    bad = np.flatnonzero(~(((_y == 0) | (_y == 1)).all(axis=1) & (_y.sum(axis=1) == 1)))
+    if bad.size:
+        raise ValueError(f'_y row {int(bad[0])} is not one-hot: {_y[bad[0]]}')
+    K = int(np.unique(_y, axis=0).shape[0])
+    labels = _y.argmax(axis=1).astype(np.int32)
+    if labels.max() >= K:
+        raise ValueError(f'_y names class {int(labels.max())} but holds only {K} distinct rows')
+    if epochs < 1 or restarts < 1:
+        raise ValueError('epochs and restarts must be >= 1')
+    base = models.load_model(base_model_path, kind=weights.SI, device=device,
+                             allow_synthetic=allow_synthetic)
+    base._ensure_loaded()
+    emb = base.ctx.si_embed(_x)
+    plan = _fit_plan(labels, K, seed, _test_split_ratio, epochs, restarts)
+    tr, va, te = plan['train'], plan['val'], plan['test']
+    w, b, hist = fit_head(emb[tr], labels[tr], emb[va], labels[va], plan['w0'], plan['b0'],
+                          plan['perm'], epochs, batch=16, lr=1e-4, device=base.ctx)
+    last = hist[:, -1]
+    score = last[:, 2:] if len(va) else last[:, :2]      # (loss, acc) deciding between restarts
+    best = min(range(restarts), key=lambda r: (-score[r, 1], score[r, 0], r))
+    head = weights.si_spec(K)[-2][0].rsplit('/', 1)[0]
+    W = {n: base.W[n] for n, _, _ in weights.si_spec(K)[:-2]}
+    W[head + '/kernel'] = w[best]
+    W[head + '/bias'] = b[best]
+    os.makedirs(final_model_path, exist_ok=True)
+    tfbundle.save_deployed(final_model_path, W, K)
+    accuracy = float(score[best, 1])
+    if len(te):      # model.evaluate(x_test, y_test) on the model just saved
+        deployed = models.load_model(final_model_path, device=base.ctx)
+        accuracy = float((deployed.predict(_x[te]).argmax(axis=1) == labels[te]).mean())
+        print('Accuracy on test set: ', accuracy)
+    return accuracy
+
+
+def transfer_learning_on_experiment(root_dir, **kw):
+    """speaker_identification.py:480-503 with root_dir in the place of the script's Root_Dir: features
+    of root_dir/experiment/corpus -> experiment/experiment_feature.npz + speaker_id_dict.json ->
+    transfer_learning(x, y, 1, 0, root_dir/timit/model, root_dir/experiment/model).  Keyword arguments
+    go to transfer_learning."""
+    import json
+    root_dir = str(root_dir)
+    wav_files = get_wav_files(root_dir + '/experiment/corpus/')
+    print(wav_files)
+    x, y, speaker_id = make_feature_experiment(wav_files, device=kw.get('device'))
+    np.savez(root_dir + '/experiment/experiment_feature', x, y)
+    with open(root_dir + '/experiment/speaker_id_dict.json', 'w') as f:
+        json.dump(speaker_id, f)
+    input_feature = np.load(root_dir + '/experiment/experiment_feature.npz', allow_pickle=True)
+    x = input_feature['arr_0']
+    y = input_feature['arr_1']
+    final_model_path = root_dir + '/experiment/model'
+    if not os.path.exists(final_model_path):
+        os.mkdir(final_model_path)
+    return transfer_learning(x, y, 1, 0, root_dir + '/timit/model', final_model_path, **kw)
 
 
 def conversation_features(sig, device=None):

@@ -1,4 +1,5 @@
-"""TensorFlow tensor-bundle reader (``variables/variables.index`` + ``variables.data-*``).
+"""TensorFlow tensor-bundle reader (``variables/variables.index`` + ``variables.data-*``), and the
+writer of the deployed SI model's bundle (``save_deployed``, what ``transfer_learning`` saves).
 
 SURVEY.md 8(f) row 1.  The reference ships its models as Keras 2.6 SavedModels
 (``save_format='tf'``; ``OverlapDetection/timit/models/timit{1.0,2.0}/``,
@@ -230,6 +231,88 @@ def layout(shapes):
     if missing:
         raise ValueError(f'bundle lacks {len(missing)} variables, e.g. {missing[:3]}')
     return kind, n_classes, head, mapping
+
+
+def _enc_varint(v):
+    out = bytearray()
+    while v >= 0x80:
+        out.append((v & 0x7F) | 0x80)
+        v >>= 7
+    out.append(v)
+    return bytes(out)
+
+
+def _enc_field(num, wire, payload):
+    tag = _enc_varint((num << 3) | wire)
+    if wire == 0:
+        return tag + _enc_varint(payload)
+    if wire == 2:
+        return tag + _enc_varint(len(payload)) + payload
+    return tag + struct.pack('<I', payload)      # wire 5: fixed32
+
+
+def _enc_block(entries):
+    """an uncompressed LevelDB block with a restart point at every entry, + its 5-byte trailer"""
+    body = bytearray()
+    restarts = []
+    for k, v in entries:
+        restarts.append(len(body))
+        body += _enc_varint(0) + _enc_varint(len(k)) + _enc_varint(len(v)) + k + v
+    for r in restarts or [0]:
+        body += struct.pack('<I', r)
+    body += struct.pack('<I', max(len(restarts), 1))
+    body = bytes(body)
+    return body, b'\x00' + struct.pack('<I', masked_crc32c(body + b'\x00'))
+
+
+def save_deployed(model_dir, W, n_classes):
+    """Write the deployed SI model -- what ``transfer_learning`` saves with ``model.save``
+    (speaker_identification.py:456) -- as a SavedModel variable bundle under
+    ``<model_dir>/variables/``, in exactly the key layout ``layout`` documents and reads:
+    ``layer_with_weights-1/{kernel,bias}`` = customized_dense ([512, K], [K]), the nested base
+    model's variables as ``variables/i`` in ``weights.si_spec`` order.  W: {canonical name: array}
+    (``weights.si_spec(n_classes)``; the head under layer_with_weights-42).  Tensors are stored as
+    float32 at 8-byte-aligned offsets with their masked CRC-32C, so ``load_bundle`` /
+    ``models.load_model`` return them bit for bit.  Only the variables are written: there is no
+    ``saved_model.pb`` (the graph), which this package never reads; TensorFlow itself cannot load the
+    directory, and parity of the key layout with a real TF save is unpinned (see ``layout``)."""
+    from . import weights
+    items = weights.si_spec(n_classes)
+    weights.check(weights.SI, W, n_classes)
+    head = items[-2][0].rsplit('/', 1)[0]
+    tensors = {'layer_with_weights-1/kernel': W[head + '/kernel'],
+               'layer_with_weights-1/bias': W[head + '/bias']}
+    for i, (name, _, _) in enumerate(items[:-2]):
+        tensors[f'variables/{i}'] = W[name]
+    data = bytearray()
+    entries = []
+    for key in sorted(tensors):
+        raw = np.ascontiguousarray(tensors[key], dtype='<f4').tobytes()
+        off = (len(data) + 7) // 8 * 8
+        data += b'\0' * (off - len(data)) + raw
+        dims = b''.join(_enc_field(2, 2, _enc_field(1, 0, d)) for d in np.shape(tensors[key]))
+        proto = _enc_field(1, 0, 1) + _enc_field(2, 2, dims)          # DT_FLOAT, shape
+        if off:
+            proto += _enc_field(4, 0, off)
+        proto += _enc_field(5, 0, len(raw)) + _enc_field(6, 5, masked_crc32c(raw))
+        entries.append(((key + '/.ATTRIBUTES/VARIABLE_VALUE').encode(), proto))
+    header = _enc_field(1, 0, 1) + _enc_field(3, 2, _enc_field(1, 0, 1))   # num_shards 1, producer 1
+    entries = [(b'', header)] + sorted(entries)
+    out = bytearray()
+    handles = []
+    for blk in (_enc_block(entries), _enc_block([])):      # data block, empty metaindex block
+        handles.append(_enc_varint(len(out)) + _enc_varint(len(blk[0])))
+        out += blk[0] + blk[1]
+    idx = _enc_block([(entries[-1][0], handles[0])])
+    foot = handles[1] + _enc_varint(len(out)) + _enc_varint(len(idx[0]))
+    out += idx[0] + idx[1]
+    out += foot + b'\0' * (40 - len(foot)) + struct.pack('<Q', _MAGIC)
+    d = os.path.join(model_dir, 'variables')
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(d, 'variables.data-00000-of-00001'), 'wb') as f:
+        f.write(bytes(data))
+    with open(os.path.join(d, 'variables.index'), 'wb') as f:
+        f.write(bytes(out))
 
 
 def canonical_names(shapes, bilstm_layer=None):
