@@ -9,6 +9,7 @@
 #include "internal.h"
 #include "nets.h"
 #include "odu.h"
+#include "odw.h"
 #include "resblk.h"
 #include "siu.h"
 
@@ -152,6 +153,7 @@ enum OdPath {
   OD_STRIPS,   // rbs.hip: the whole block, rolling down 16-column strips (conv_h3 weight layout)
   OD_TILES,    // resblk.hip: the whole block on 16 x 16 tiles (fused fragment layout)
   OD_ODU,      // odu.hip: the whole block, blocks 4-9
+  OD_ODW,      // odw.hip: odu with two strips per workgroup, the blocks it is faster on
   OD_PAIR      // conv_h3 / exact-f32 launches, one per conv
 };
 struct OdChoice {
@@ -181,13 +183,18 @@ bool odu_ok(const ResUnitW& B, bool pool, int h, int w) {
          (!pool || (B.sc.cin == B.ca.cin && B.sc.cout == B.ca.cout && B.sc.cout_pad == B.sc.cout));
 }
 
+// a block odu_ok() admits (odw takes odu's arguments) that odw.hip runs faster: blocks 7 and 8-9
+bool odw_ok(const ResUnitW& B, bool pool, int h, int w) {
+  return odw_supported(h, w, B.ca.cin, B.ca.cout, pool);
+}
+
 // stop: the debug trace's last stage (-1: none); a trace of the stem alone (0) needs it in HBM
 OdChoice od_choose(const mmla_ctx* c, const ResUnitW& B, int b, int h, int w, int stop) {
   OdChoice k{OD_PAIR, false};
   if (c->precision != MMLA_PREC_F16X3) return k;
   if (c->rbs && strips_ok(B, POOL[b], h, w)) k.path = OD_STRIPS;
   else if (tiles_ok(B, POOL[b])) k.path = OD_TILES;
-  else if (c->odu && odu_ok(B, POOL[b], h, w)) k.path = OD_ODU;
+  else if (c->odu && odu_ok(B, POOL[b], h, w)) k.path = c->odw && odw_ok(B, POOL[b], h, w) ? OD_ODW : OD_ODU;
   k.stem = b == 0 && stop != 0 && (k.path == OD_STRIPS || k.path == OD_TILES);
   return k;
 }
@@ -345,10 +352,13 @@ int run_od_net(mmla_ctx* c, const uint8_t* img_u8, const float* img_f32, int64_t
         break;
       }
       case OD_ODU:   // t1 stays in LDS, bit-identical to the pair
+      case OD_ODW: {
+        const OduArgs o = odu_args(B, pool, X, T1, n, c->range_ptr);
         LAUNCH(c, MMLA_STAGE_CONV, flops,
-               odu_launch(odu_args(B, pool, X, T1, n, c->range_ptr), h, w, B.ca.cin, B.ca.cout, pool,
-                          c->stream));
+               k.path == OD_ODW ? odw_launch(o, h, w, B.ca.cin, B.ca.cout, pool, c->stream)
+                                : odu_launch(o, h, w, B.ca.cin, B.ca.cout, pool, c->stream));
         break;
+      }
       case OD_PAIR:
         CHK(od_block_pair(c, B, pool, (int)n, h, w, X, T1, T2, &out));
         break;

@@ -507,7 +507,10 @@ hipError_t odu_launch(const OduArgs& a, int h, int w, int cin, int c, bool pool,
   // blocks 5-6 10.6 ms.  Blocks 4 and 8-9 are LDS-bound at 3 workgroups per CU (42 / 41 KB).
   // Operand pipeline depths (LA, LB): one group ahead pays 2.2-2.4 % in blocks 5-9
   // (168 / 133 / 165 VGPRs, no spills); block 4, with four waves per SIMD to cover its reads, gains
-  // nothing from GEMM a's and would spill 5 VGPRs at its 128 cap with GEMM b's
+  // nothing from GEMM a's and would spill 5 VGPRs at its 128 cap with GEMM b's.
+  // Two strips per workgroup on one weight stream (odw.hip, two workgroups per CU) beat these for
+  // block 7 (14.19 -> 13.47 ms) and blocks 8-9 (5.70 -> 5.35 ms), which run there by default; blocks 4
+  // and 5-6 lose by it (15.46 -> 15.57, 6.49 -> 6.65 ms) and stay here
   if (h == 64 && pool) return launch<64, 76, 32, 64, 2, true, 4, 4, 0, 0>(a, s);
   if (h == 32 && c == 64) return launch<32, 38, 64, 64, 4, false, 4, 3, 1, 1>(a, s);
   if (h == 32 && pool) return launch<32, 38, 64, 128, 2, true, 4, 2, 1, 1>(a, s);
