@@ -121,7 +121,9 @@ int mmla_range_check(mmla_ctx* ctx, int64_t* f32_reruns);
  * retries.  Per-clip device footprint of a micro-batch: OD ~7.6 MB (three n*128*151*32 f32
  * activation buffers + image + front-end scratch), so the 16384-clip default holds ~124 GB;
  * SI ~0.14 MB (65536 clips ~9 GB).  Weights: OD ~12 MB, SI ~10 MB.  Workspaces are kept for
- * reuse until mmla_release_workspace or mmla_destroy.
+ * reuse until mmla_release_workspace or mmla_destroy.  mmla_od_pipeline_gated with nr_passes > 0 adds
+ * per clip the second image (58 KB) and two float clip buffers (2 x 4 x min(clip_len, 24000) bytes,
+ * 192 KB), and per launch of the noise gate (at most 512 clips) ~6.9 MB of gate scratch per clip.
  */
 int mmla_set_microbatch(mmla_ctx* ctx, int64_t od_clips, int64_t si_clips);
 /* The micro-batch sizes the next call would use. */
@@ -246,6 +248,43 @@ int mmla_si_pipeline(mmla_ctx* ctx, const int16_t* pcm, int64_t n_clips, int64_t
                      uint8_t* silent, uint32_t flags);
 
 /*
+ * Mean structural similarity of n pairs of uint8 images a, b [n,h,w,c] -> out [n] f32: replaces
+ * skimage.metrics.structural_similarity(image1, image2, multichannel=True) of compare_images
+ * (OverlapDetection/scripts/record_on_pi.py:39-48) with scikit-image's defaults for uint8 input: uniform
+ * 7 x 7 window, K1 0.01, K2 0.03, data_range 255, sample covariance, the SSIM map cropped by 3 pixels
+ * on every side, the mean over the cropped map per channel and then over channels.  The window sums are
+ * exact integers, the rest is float32 (within 2e-6 of float64); two equal images give exactly 1.  A
+ * pair's result is bit-identical wherever it sits in the batch (fixed-order reduction, no atomics).
+ * (Stated from scikit-image's published source; the library is not available here: parity with it is
+ * unpinned.)  MMLA_E_INVALID for h or w < 7 or c not in {1, 3, 4}.
+ */
+int mmla_ssim_u8(mmla_ctx* ctx, const uint8_t* a, const uint8_t* b, int64_t n, int32_t h, int32_t w,
+                 int32_t c, float* out, uint32_t flags);
+
+/*
+ * mmla_od_pipeline with the denoise-and-compare silence gate of the edge loop
+ * (OverlapDetection/scripts/record_on_pi.py:103-124).  Per clip:
+ *   image A = the front-end on the raw PCM;
+ *   y = pcm / 32768, then nr_passes times (the reference: NOISE_REDUCE_TIMES = 4): the stationary gate
+ *     of mmla_nr_reduce on the clip's first min(clip_len, 24000) samples, written as PCM_16 (mmla_pcm16's
+ *     rule) and read back (/ 32768).  With lens the clip is denoised zero-extended to that length and
+ *     the samples from lens[c] on are zeroed after every pass;
+ *   image B = the front-end on the denoised int16 PCM;  ssim[c] = SSIM(A, B) (mmla_ssim_u8);
+ *   silent[c] = fewer than 4000 samples OR ssim[c] < ssim_threshold (the reference: 0.3);
+ *   probs[c] = OD-NET on image B;  argmax[c] = -1 where silent.
+ * nr_passes = 0: B = A, ssim = 1, the results of mmla_od_pipeline, no noise profile needed.
+ * MMLA_E_INVALID: nr_passes < 0, or nr_passes > 0 before mmla_nr_set_noise.  ssim [n] f32 is nullable.
+ * Micro-batched as mmla_od_pipeline (mmla_set_microbatch lists the extra workspace).  The gate runs at
+ * most 512 clips per launch with a stream synchronisation between launches and between passes, so with
+ * MMLA_DEVICE_PTR and nr_passes > 0 this call synchronises the context stream internally (its last
+ * launches are still only enqueued).
+ */
+int mmla_od_pipeline_gated(mmla_ctx* ctx, const int16_t* pcm, int64_t n_clips, int64_t clip_stride,
+                           const int32_t* lens, int32_t clip_len, int32_t nr_passes,
+                           float ssim_threshold, float* probs, int32_t* argmax, uint8_t* silent,
+                           float* ssim, uint32_t flags);
+
+/*
  * Stationary spectral-gate noise reduction, replaces nr.reduce_noise(y_noise=noise, y=y, sr=sr,
  * stationary=True) (OverlapDetection/scripts/record_on_pc.py:208-212,
  * SpeakerIdentification/scripts/record_on_pc.py:189, speaker_identification_post_processing.py:171)
@@ -317,11 +356,11 @@ int mmla_resample_sinc(mmla_ctx* ctx, const float* x, int64_t n, int32_t sr_orig
  */
 #define MMLA_NSTAGES 7
 enum mmla_stage {
-  MMLA_STAGE_OD_FE = 0, /* work = algorithmic HBM bytes */
+  MMLA_STAGE_OD_FE = 0, /* work = algorithmic HBM bytes; also the SSIM launches (2 images in + 4 B out) */
   MMLA_STAGE_SI_FE = 1, /* work = algorithmic HBM bytes */
   MMLA_STAGE_CONV = 2,  /* work = FLOPs (2 * MACs, unpadded) */
   MMLA_STAGE_LSTM = 3,  /* work = FLOPs */
-  MMLA_STAGE_GLUE = 4,  /* stem, pooling, mean: work = FLOPs */
+  MMLA_STAGE_GLUE = 4,  /* stem, pooling, mean: work = FLOPs; VAD, PCM conversions: bytes */
   MMLA_STAGE_HEAD = 5,  /* dense + softmax / sigmoid, mmla_si_head_fit: work = FLOPs */
   MMLA_STAGE_NR = 6     /* noise gate: work = algorithmic HBM bytes (signal in + out) */
 };

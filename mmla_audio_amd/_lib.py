@@ -61,6 +61,9 @@ SIGNATURES = {
                          _P, _P, _P, _P, _P, _P, _U32],
     'mmla_od_pipeline': [_P, _P, _I64, _I64, _P, _I32, _P, _P, _P, _U32],
     'mmla_si_pipeline': [_P, _P, _I64, _I64, _P, _I32, _P, _P, _P, _U32],
+    'mmla_ssim_u8': [_P, _P, _P, _I64, _I32, _I32, _I32, _P, _U32],
+    'mmla_od_pipeline_gated': [_P, _P, _I64, _I64, _P, _I32, _I32, ctypes.c_float, _P, _P, _P, _P,
+                               _U32],
     'mmla_profile_enable': [_P, ctypes.c_int],
     'mmla_profile_read': [_P, _P, _P, _P, ctypes.c_int],
     'mmla_debug_od_trace': [_P, _P, _I64, ctypes.c_int, _P, _I64],
@@ -521,6 +524,39 @@ class Context:
                     'mmla_od_pipeline')
         return probs, am, silent.astype(bool)
 
+    def od_pipeline_gated(self, pcm, lens=None, passes=4, threshold=0.3):
+        """od_pipeline with the denoise-and-compare silence gate of record_on_pi.py:103-124 (noise
+        profile: nr_set_noise) -> (probs [n,2] of the denoised clips, argmax [n] (-1 = 'silent'),
+        silent [n] bool, ssim [n] of each clip's image against its `passes` x denoised image)."""
+        a, ln, L = self._pcm(pcm, lens)
+        n = a.shape[0]
+        probs = np.empty((n, 2), np.float32)
+        am = np.empty(n, np.int32)
+        silent = np.empty(n, np.uint8)
+        ssim = np.empty(n, np.float32)
+        self._check(self.lib.mmla_od_pipeline_gated(
+            self.h, _ptr(a), n, a.shape[1], _ptr(ln), L, int(passes), float(threshold), _ptr(probs),
+            _ptr(am), _ptr(silent), _ptr(ssim), 0), 'mmla_od_pipeline_gated')
+        return probs, am, silent.astype(bool), ssim
+
+    def ssim_u8(self, a, b):
+        """Mean SSIM (scikit-image defaults, multichannel) of uint8 image pairs a, b [n,h,w,c] (or one
+        pair [h,w,c]) -> float32 [n] (or a scalar)."""
+        a = np.ascontiguousarray(a)
+        b = np.ascontiguousarray(b)
+        if a.dtype != np.uint8 or b.dtype != np.uint8 or a.shape != b.shape or a.ndim not in (3, 4):
+            raise ValueError(f'ssim_u8 takes two uint8 arrays [n,h,w,c] of one shape, got {a.dtype} '
+                             f'{a.shape} and {b.dtype} {b.shape}')
+        single = a.ndim == 3
+        if single:
+            a, b = a[None], b[None]
+        n, h, w, c = a.shape
+        out = np.empty(n, np.float32)
+        self._check(self.lib.mmla_ssim_u8(self.h, _ptr(a) if a.size else None,
+                                          _ptr(b) if b.size else None, n, h, w, c, _ptr(out), 0),
+                    'mmla_ssim_u8')
+        return out[0] if single else out
+
     def od_pipeline_strided(self, signal, n, stride, clip_len):
         """OD pipeline over n windows of one long int16 signal: window c = signal[c*stride :
         c*stride + clip_len] (overlapping when stride < clip_len; no host-side copies)."""
@@ -579,6 +615,18 @@ class Context:
                                               probs or None, argmax or None, silent or None,
                                               MMLA_DEVICE_PTR),
                     'mmla_od_pipeline(dev)')
+
+    def od_pipeline_gated_dev(self, pcm, n, stride, clip_len, passes=4, threshold=0.3, probs=0,
+                              argmax=0, silent=0, ssim=0, lens=0):
+        """synchronises the context stream internally when passes > 0 (see mmla.h)"""
+        self._check(self.lib.mmla_od_pipeline_gated(
+            self.h, pcm, n, stride, lens or None, clip_len, int(passes), float(threshold),
+            probs or None, argmax or None, silent or None, ssim or None, MMLA_DEVICE_PTR),
+            'mmla_od_pipeline_gated(dev)')
+
+    def ssim_u8_dev(self, a, b, n, h, w, c, out):
+        self._check(self.lib.mmla_ssim_u8(self.h, a, b, n, h, w, c, out, MMLA_DEVICE_PTR),
+                    'mmla_ssim_u8(dev)')
 
     def si_pipeline_dev(self, pcm, n, stride, clip_len, probs=0, argmax=0, silent=0, lens=0):
         self._check(self.lib.mmla_si_pipeline(self.h, pcm, n, stride, lens or None, clip_len,

@@ -126,16 +126,13 @@ int mmla_nr_set_noise(mmla_ctx* c, const float* noise, int64_t n_noise, int32_t 
   return MMLA_OK;
 }
 
-int mmla_nr_reduce(mmla_ctx* c, const float* y, int64_t n_signals, int64_t stride, int64_t len,
-                   float* out, uint32_t flags) {
-  if (!c) return MMLA_E_INVALID;
-  if (n_signals < 0 || len < 0 || (n_signals > 0 && (!y || !out)) ||
-      (n_signals > 1 && stride < len))
-    return fail(c, MMLA_E_INVALID, "bad nr_reduce args");
+}  // extern "C"
+
+// the gate of mmla_nr_reduce on device pointers; mmla_od_pipeline_gated runs its passes through it too
+int mmla::nr_reduce_dev(mmla_ctx* c, const float* dy, int64_t n_signals, int64_t stride, int64_t len,
+                        float* dout) {
   if (!c->nr_ready) return fail(c, MMLA_E_INVALID, "mmla_nr_set_noise must be called first");
-  if (n_signals == 0 || len == 0) return MMLA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  const bool dev = flags & MMLA_DEVICE_PTR;
+  if (n_signals <= 0 || len <= 0) return MMLA_OK;
   // SpectralGate.get_traces: one chunk of `len` when len <= chunk_size, else chunk_size pieces
   const int64_t keep = len <= kNrChunk ? len : kNrChunk;
   const int64_t per = (len + keep - 1) / keep;
@@ -149,15 +146,6 @@ int mmla_nr_reduce(mmla_ctx* c, const float* y, int64_t n_signals, int64_t strid
     for (int64_t k = 0; k < per; ++k)
       items.push_back(NrItem{sgl * stride, len, k * keep - kNrPadding, sgl * len + k * keep,
                              std::min(keep, len - k * keep)});
-  // signals: the caller's device pointer, or one host copy per call
-  const float* dy;
-  CHK(in_ptr(c, y, (n_signals - 1) * stride + len, dev, S_NR_Y, &dy));
-  float* dout = out;
-  if (!dev) {
-    void* p = nullptr;
-    CHK(ws_get(c, S_OUT0, (size_t)n_signals * len * sizeof(float), &p));
-    dout = static_cast<float*>(p);
-  }
   for (size_t i0 = 0; i0 < items.size(); i0 += cap) {
     const int64_t ni = std::min<int64_t>(cap, (int64_t)items.size() - (int64_t)i0);
     void *pS, *pB, *pM, *pF, *pI, *pR;
@@ -196,6 +184,31 @@ int mmla_nr_reduce(mmla_ctx* c, const float* y, int64_t n_signals, int64_t strid
     // the item table / scratch of this launch must not be overwritten by the next one's upload
     if (i0 + cap < items.size()) HIPCHK(c, hipStreamSynchronize(c->stream));
   }
+  return MMLA_OK;
+}
+
+extern "C" {
+
+int mmla_nr_reduce(mmla_ctx* c, const float* y, int64_t n_signals, int64_t stride, int64_t len,
+                   float* out, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  if (n_signals < 0 || len < 0 || (n_signals > 0 && (!y || !out)) ||
+      (n_signals > 1 && stride < len))
+    return fail(c, MMLA_E_INVALID, "bad nr_reduce args");
+  if (!c->nr_ready) return fail(c, MMLA_E_INVALID, "mmla_nr_set_noise must be called first");
+  if (n_signals == 0 || len == 0) return MMLA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool dev = flags & MMLA_DEVICE_PTR;
+  // signals: the caller's device pointer, or one host copy per call
+  const float* dy;
+  CHK(in_ptr(c, y, (n_signals - 1) * stride + len, dev, S_NR_Y, &dy));
+  float* dout = out;
+  if (!dev) {
+    void* p = nullptr;
+    CHK(ws_get(c, S_OUT0, (size_t)n_signals * len * sizeof(float), &p));
+    dout = static_cast<float*>(p);
+  }
+  CHK(nr_reduce_dev(c, dy, n_signals, stride, len, dout));
   CHK(copy_back(c, out, 0, dout, (size_t)n_signals * len, dev));
   return finish(c, dev);
 }

@@ -18,6 +18,7 @@
 #include "nr.h"
 #include "od_fe.h"
 #include "si_fe.h"
+#include "ssim.h"
 #include "vad.h"
 
 namespace mmla __attribute__((visibility("hidden"))) {
@@ -221,7 +222,8 @@ enum Slot {
   S_OUT0, S_OUT1, S_OUT2, S_OUT3, S_IN,
   S_NR_S, S_NR_BITS, S_NR_FMAX, S_NR_FRAMES, S_NR_ITEMS, S_NR_Y, S_NR_ROWS,
   S_VAD_SPEECH, S_VAD_OUT, S_VAD_LENS, S_RS_TR, S_RS_WIN, S_LSTM,
-  S_TRAIN   // mmla_si_head_fit: every host-pointer operand, carved from one slot
+  S_TRAIN,  // mmla_si_head_fit: every host-pointer operand, carved from one slot
+  S_IMG2, S_GATE_Y0, S_GATE_Y1, S_SSIM   // mmla_od_pipeline_gated / mmla_ssim_u8
 };
 
 int ws_get(mmla_ctx* c, int slot, size_t bytes, void** out);
@@ -230,6 +232,9 @@ int64_t microbatch(mmla_ctx* c, bool od);
 // the end of every entry point that launched: the last error, host-mode synchronisation, guard bands
 int finish(mmla_ctx* c, bool dev);
 void free_allocs(std::vector<void*>& al);   // weights.cpp
+// the body of mmla_nr_reduce on device pointers (capi.cpp): y [n_signals, stride] -> out [n_signals,
+// len].  At most 512 items per launch with a stream synchronisation between launches.
+int nr_reduce_dev(mmla_ctx* c, const float* y, int64_t n_signals, int64_t stride, int64_t len, float* out);
 
 // device view of `count` input elements: the caller's pointer (device mode) or a copy in `slot`
 template <typename T>
@@ -281,12 +286,15 @@ int copy_back(mmla_ctx* c, T* user, int64_t off, const T* d, size_t count, bool 
 
 // ---- network runners (net_runners.cpp): device pointers, one micro-batch -----------------------
 
-// the OD 'silent' gate (record_on_pc.py:141-154) of one micro-batch: device lens (nullable) or
-// clip_len; silent output (nullable)
+// the OD 'silent' gate of one micro-batch: fewer than 4000 samples (record_on_pc.py:141-154; device
+// lens (nullable) or clip_len), or the similarity of the clip's image to its denoised image below a
+// threshold (record_on_pi.py:103-124; device ssim, nullable); silent output (nullable)
 struct OdGate {
   const int32_t* lens = nullptr;
   int clip_len = -1;   // < 0: no gate (network-only calls)
   uint8_t* silent = nullptr;
+  const float* ssim = nullptr;
+  float ssim_threshold = 0.0f;
 };
 
 int run_od_net(mmla_ctx* c, const uint8_t* img_u8, const float* img_f32, int64_t n, float* probs,

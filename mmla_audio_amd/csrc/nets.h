@@ -44,9 +44,10 @@ void bilstm_h3_split_weights(const float* wcat, int D, uint16_t* hi, uint16_t* l
 // OD head: LeakyReLU(0.3) -> Dense(512 -> 2) -> softmax; probs [n,2], argmax [n] (nullable).
 // The 'silent' gate of record_on_pc.py:141-154: with clip_len >= 0, clips with fewer than 4000
 // samples (lens[i], or clip_len when lens is null) get argmax -1 and silent[i] = 1 (nullable).
+// With ssim [n] (nullable; record_on_pi.py:103-124) a clip is silent too when ssim[i] < ssim_threshold.
 hipError_t od_head_launch(const float* h, int n, const float* w /*[512][2]*/, const float* b,
                           float* probs, int32_t* argmax, const int32_t* lens, int clip_len,
-                          uint8_t* silent, hipStream_t s);
+                          uint8_t* silent, const float* ssim, float ssim_threshold, hipStream_t s);
 // SI head activation on logits [n, ld]: softmax (head 0) or sigmoid (head 1) over the first k;
 // argmax [n] (-1 where silent[i] != 0).
 hipError_t si_head_launch(const float* logits, int n, int k, int ld, int head, float* probs,

@@ -655,7 +655,8 @@ __global__ void __launch_bounds__(256, 1) bilstm_h3_split_kernel(const float* __
 __global__ void od_head_kernel(const float* __restrict__ h, int n, const float* __restrict__ w,
                                const float* __restrict__ b, float* __restrict__ probs,
                                int32_t* __restrict__ argmax, const int32_t* __restrict__ lens,
-                               int clip_len, uint8_t* __restrict__ silent) {
+                               int clip_len, uint8_t* __restrict__ silent,
+                               const float* __restrict__ ssim, float ssim_threshold) {
   // one wave per clip
   const int lane = threadIdx.x & 63;
   const int64_t clip = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -679,7 +680,10 @@ __global__ void od_head_kernel(const float* __restrict__ h, int n, const float* 
       probs[clip * 2 + 1] = e1 / s;
     }
     // record_on_pc.py:141-154: fewer than 4000 samples (after VAD) -> 'silent', no class
-    const bool sil = clip_len >= 0 && (lens ? lens[clip] : clip_len) < 4000;
+    // record_on_pi.py:103-124: ... or the clip's image barely changed by denoising it (its SSIM
+    // against the denoised clip's image below the threshold)
+    const bool sil = clip_len >= 0 && ((lens ? lens[clip] : clip_len) < 4000 ||
+                                       (ssim && ssim[clip] < ssim_threshold));
     if (silent) silent[clip] = sil ? 1 : 0;
     if (argmax) argmax[clip] = sil ? -1 : (e1 / s > e0 / s ? 1 : 0);
   }
@@ -861,10 +865,10 @@ void bilstm_h3_split_weights(const float* wcat, int D, uint16_t* hi, uint16_t* l
 
 hipError_t od_head_launch(const float* h, int n, const float* w, const float* b, float* probs,
                           int32_t* argmax, const int32_t* lens, int clip_len, uint8_t* silent,
-                          hipStream_t s) {
+                          const float* ssim, float ssim_threshold, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(od_head_kernel, dim3(blocks_for((int64_t)n * 64, 256)), dim3(256), 0, s, h, n,
-                     w, b, probs, argmax, lens, clip_len, silent);
+                     w, b, probs, argmax, lens, clip_len, silent, ssim, ssim_threshold);
   return hipGetLastError();
 }
 

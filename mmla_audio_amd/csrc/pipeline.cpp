@@ -297,6 +297,94 @@ int od_forward_common(mmla_ctx* c, const float* x_f32, const uint8_t* x_u8, int6
   });
 }
 
+// the fused OD pipeline; `gated` adds the denoise-and-compare silence gate of record_on_pi.py:103-124
+// (nr_passes gate + PCM_16 round trips, the second image, their SSIM) in front of the network
+int od_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride, const int32_t* lens,
+                       int32_t clip_len, bool gated, int32_t nr_passes, float ssim_threshold,
+                       float* probs, int32_t* argmax, uint8_t* silent, float* ssim, uint32_t flags) {
+  const char* bad = bad_pcm_args(pcm, n, stride, lens, clip_len) ? "bad pcm args" : nullptr;
+  if (c && !bad && gated) {
+    if (nr_passes < 0) bad = "nr_passes < 0";
+    else if (nr_passes > 0 && !c->nr_ready) bad = "nr_passes > 0: mmla_nr_set_noise must be called first";
+  }
+  return clip_call(c, NET_OD, n, flags, bad, [&](int64_t c0, int64_t cnt, bool dev) -> int {
+    Pcm p;
+    CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, MMLA_OD_CLIP, dev, &p));
+    void* pimg = nullptr;
+    CHK(ws_get(c, S_IMG, cnt * OD_IMG, &pimg));
+    OdFeArgs a{};
+    a.pcm = p.p;
+    a.clip_stride = p.stride;
+    a.lens = p.lens;
+    a.clip_len = p.clip_len;
+    a.tables = c->od_tables;
+    a.img = static_cast<uint8_t*>(pimg);
+    LAUNCH(c, MMLA_STAGE_OD_FE, od_fe_bytes(cnt, a), od_fe_launch(a, cnt, c->stream));
+    float* dp;
+    int32_t* da;
+    uint8_t* ds;
+    CHK(out_ptr(c, probs, c0 * 2, cnt * 2, dev, S_OUT0, &dp));
+    CHK(out_ptr(c, argmax, c0, cnt, dev, S_OUT1, &da));
+    CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT2, &ds));
+    OdGate g;
+    g.lens = p.lens;
+    g.clip_len = lens ? 0 : clip_len;   // the true length decides, not the staged width
+    g.silent = ds;
+    const uint8_t* net_img = a.img;
+    float* dss = nullptr;
+    if (gated) {
+      CHK(out_ptr(c, ssim, c0, cnt, dev, S_OUT3, &dss));
+      if (!dss) {
+        void* q = nullptr;
+        CHK(ws_get(c, S_SSIM, cnt * sizeof(float), &q));
+        dss = static_cast<float*>(q);
+      }
+      // the gate sees what the front-end sees: the first 24000 samples at most
+      const int D = (int)std::min<int64_t>(lens ? clip_len : p.clip_len, MMLA_OD_CLIP);
+      if (nr_passes > 0 && D > 0) {
+        // two float clip buffers; the last pass leaves its int16 samples in the first one.  The slack
+        // keeps the front-end's read of a clip whose lens[i] exceeds clip_len inside the buffer
+        const size_t ybytes = (size_t)cnt * D * sizeof(float) + MMLA_OD_CLIP * sizeof(int16_t);
+        void *py0 = nullptr, *py1 = nullptr, *pimg2 = nullptr;
+        CHK(ws_get(c, S_GATE_Y0, ybytes, &py0));
+        CHK(ws_get(c, S_GATE_Y1, ybytes, &py1));
+        CHK(ws_get(c, S_IMG2, cnt * OD_IMG, &pimg2));
+        float *y0 = static_cast<float*>(py0), *y1 = static_cast<float*>(py1);
+        int16_t* yq = static_cast<int16_t*>(py0);
+        LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * 6,
+               pcm_f32_launch(p.p, p.stride, p.lens, D, cnt, y0, c->stream));
+        for (int k = 0; k < nr_passes; ++k) {
+          // a pass re-uses the gate's item table and scratch: the one before it has drained
+          if (k) HIPCHK(c, hipStreamSynchronize(c->stream));
+          CHK(nr_reduce_dev(c, y0, cnt, D, D, y1));
+          const bool last = k == nr_passes - 1;
+          LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * (last ? 6 : 8),
+                 requant_launch(y1, p.lens, D, cnt, last ? nullptr : y0, last ? yq : nullptr, c->stream));
+        }
+        OdFeArgs b = a;
+        b.pcm = yq;
+        b.clip_stride = D;
+        b.clip_len = D;
+        b.img = static_cast<uint8_t*>(pimg2);
+        LAUNCH(c, MMLA_STAGE_OD_FE, od_fe_bytes(cnt, b), od_fe_launch(b, cnt, c->stream));
+        LAUNCH(c, MMLA_STAGE_OD_FE, (double)cnt * (2.0 * OD_IMG + 4),
+               ssim_u8_launch(a.img, b.img, cnt, OD_H, OD_W, 3, dss, c->stream));
+        net_img = b.img;
+      } else {   // not denoised: the second image is the first, their similarity 1
+        LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * 4, fill_f32_launch(dss, cnt, 1.0f, c->stream));
+      }
+      g.ssim = dss;
+      g.ssim_threshold = ssim_threshold;
+    }
+    CHK(run_od_net(c, net_img, nullptr, cnt, dp, da, g));
+    CHK(copy_back(c, probs, c0 * 2, dp, cnt * 2, dev));
+    CHK(copy_back(c, argmax, c0, da, cnt, dev));
+    CHK(copy_back(c, silent, c0, ds, cnt, dev));
+    if (gated) CHK(copy_back(c, ssim, c0, static_cast<const float*>(dss), cnt, dev));
+    return MMLA_OK;
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -394,35 +482,37 @@ int mmla_si_embed(mmla_ctx* c, const float* x, int64_t n, float* emb, uint32_t f
 int mmla_od_pipeline(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
                      const int32_t* lens, int32_t clip_len, float* probs, int32_t* argmax,
                      uint8_t* silent, uint32_t flags) {
-  return clip_call(c, NET_OD, n, flags, bad_pcm_args(pcm, n, stride, lens, clip_len) ? "bad pcm args" : nullptr,
-                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
-    Pcm p;
-    CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, MMLA_OD_CLIP, dev, &p));
-    void* pimg = nullptr;
-    CHK(ws_get(c, S_IMG, cnt * OD_IMG, &pimg));
-    OdFeArgs a{};
-    a.pcm = p.p;
-    a.clip_stride = p.stride;
-    a.lens = p.lens;
-    a.clip_len = p.clip_len;
-    a.tables = c->od_tables;
-    a.img = static_cast<uint8_t*>(pimg);
-    LAUNCH(c, MMLA_STAGE_OD_FE, od_fe_bytes(cnt, a), od_fe_launch(a, cnt, c->stream));
-    float* dp;
-    int32_t* da;
-    uint8_t* ds;
-    CHK(out_ptr(c, probs, c0 * 2, cnt * 2, dev, S_OUT0, &dp));
-    CHK(out_ptr(c, argmax, c0, cnt, dev, S_OUT1, &da));
-    CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT2, &ds));
-    OdGate g;
-    g.lens = p.lens;
-    g.clip_len = lens ? 0 : clip_len;   // the true length decides, not the staged width
-    g.silent = ds;
-    CHK(run_od_net(c, a.img, nullptr, cnt, dp, da, g));
-    CHK(copy_back(c, probs, c0 * 2, dp, cnt * 2, dev));
-    CHK(copy_back(c, argmax, c0, da, cnt, dev));
-    return copy_back(c, silent, c0, ds, cnt, dev);
-  });
+  return od_pipeline_common(c, pcm, n, stride, lens, clip_len, false, 0, 0.0f, probs, argmax, silent,
+                            nullptr, flags);
+}
+
+int mmla_od_pipeline_gated(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
+                           const int32_t* lens, int32_t clip_len, int32_t nr_passes,
+                           float ssim_threshold, float* probs, int32_t* argmax, uint8_t* silent,
+                           float* ssim, uint32_t flags) {
+  return od_pipeline_common(c, pcm, n, stride, lens, clip_len, true, nr_passes, ssim_threshold, probs,
+                            argmax, silent, ssim, flags);
+}
+
+int mmla_ssim_u8(mmla_ctx* c, const uint8_t* a, const uint8_t* b, int64_t n, int32_t h, int32_t w,
+                 int32_t ch, float* out, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  if (h < SSIM_WIN || w < SSIM_WIN || (ch != 1 && ch != 3 && ch != 4))
+    return fail(c, MMLA_E_INVALID, "ssim needs h, w >= 7 and 1, 3 or 4 channels (got %d x %d x %d)", h, w, ch);
+  const int64_t per = (int64_t)h * w * ch;
+  if (n < 0 || n > 0x7fffffff || (int64_t)w * ch > (1 << 30) || (n > 0 && (!a || !b || !out)))
+    return fail(c, MMLA_E_INVALID, "bad ssim args");
+  if (n == 0) return MMLA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool dev = flags & MMLA_DEVICE_PTR;
+  const uint8_t *da, *db;
+  float* ds;
+  CHK(in_ptr(c, a, (size_t)(n * per), dev, S_IMG, &da));
+  CHK(in_ptr(c, b, (size_t)(n * per), dev, S_IMG2, &db));
+  CHK(out_ptr(c, out, 0, (size_t)n, dev, S_OUT0, &ds));
+  LAUNCH(c, MMLA_STAGE_OD_FE, (double)n * (2.0 * per + 4), ssim_u8_launch(da, db, n, h, w, ch, ds, c->stream));
+  CHK(copy_back(c, out, 0, ds, (size_t)n, dev));
+  return finish(c, dev);
 }
 
 int mmla_si_pipeline(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,

@@ -42,3 +42,11 @@ hipError_t vad_speech_launch(const VadArgs& a, hipStream_t s);
 hipError_t vad_collect_launch(const VadArgs& a, hipStream_t s);
 // soundfile's PCM_16 write of float audio (libsndfile f2s: (short) lrintf(x * 0x7FFF)).
 hipError_t pcm16_launch(const float* y, int64_t n, int16_t* out, hipStream_t s);
+// The PCM_16 round trip of the denoise-and-compare gate (mmla_od_pipeline_gated), n clips of `len`
+// samples, zeros from each clip's valid length (lens[i] clamped to [0, len]; null: len) on:
+// pcm_f32: the read (x / 32768) of int16 clips at `stride` into y [n][len];
+// requant: pcm16's write of y [n][len], as int16 into yq [n][len] or, with yq null, read back into yf.
+hipError_t pcm_f32_launch(const int16_t* pcm, int64_t stride, const int32_t* lens, int len, int64_t n,
+                          float* y, hipStream_t s);
+hipError_t requant_launch(const float* y, const int32_t* lens, int len, int64_t n, float* yf,
+                          int16_t* yq, hipStream_t s);

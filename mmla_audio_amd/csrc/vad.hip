@@ -469,6 +469,33 @@ __global__ void pcm16_kernel(const float* __restrict__ y, int64_t n, int16_t* __
   out[i] = (int16_t)(int32_t)__builtin_rintf(32767.0f * y[i]);
 }
 
+// int16 PCM -> float32 as soundfile / librosa read a 16-bit file (x / 32768), each clip's first `len`
+// samples, zeros from the clip's valid length on
+__global__ void pcm_f32_kernel(const int16_t* __restrict__ pcm, int64_t stride,
+                               const int32_t* __restrict__ lens, int len, int64_t n,
+                               float* __restrict__ y) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * len) return;
+  const int64_t clip = i / len;
+  const int j = (int)(i - clip * len);
+  const int valid = lens ? min(max(lens[clip], 0), len) : len;
+  y[i] = j < valid ? (float)pcm[clip * stride + j] * (1.0f / 32768.0f) : 0.0f;
+}
+
+// the PCM_16 write (pcm16_kernel's rule) and read back of n clips of `len` floats, zeros from the
+// clip's valid length on: int16 into yq, or with yq null x / 32768 into yf
+__global__ void requant_kernel(const float* __restrict__ y, const int32_t* __restrict__ lens, int len,
+                               int64_t n, float* __restrict__ yf, int16_t* __restrict__ yq) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * len) return;
+  const int64_t clip = i / len;
+  const int j = (int)(i - clip * len);
+  const int valid = lens ? min(max(lens[clip], 0), len) : len;
+  const int16_t q = j < valid ? (int16_t)(int32_t)__builtin_rintf(32767.0f * y[i]) : (int16_t)0;
+  if (yq) yq[i] = q;
+  else yf[i] = (float)q * (1.0f / 32768.0f);
+}
+
 }  // namespace
 
 bool vad_init_state(VadState* s, int mode) {
@@ -511,5 +538,21 @@ hipError_t vad_collect_launch(const VadArgs& a, hipStream_t s) {
 hipError_t pcm16_launch(const float* y, int64_t n, int16_t* out, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(pcm16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, y, n, out);
+  return hipGetLastError();
+}
+
+hipError_t pcm_f32_launch(const int16_t* pcm, int64_t stride, const int32_t* lens, int len, int64_t n,
+                          float* y, hipStream_t s) {
+  if (n <= 0 || len <= 0) return hipSuccess;
+  hipLaunchKernelGGL(pcm_f32_kernel, dim3((unsigned)((n * len + 255) / 256)), dim3(256), 0, s, pcm,
+                     stride, lens, len, n, y);
+  return hipGetLastError();
+}
+
+hipError_t requant_launch(const float* y, const int32_t* lens, int len, int64_t n, float* yf,
+                          int16_t* yq, hipStream_t s) {
+  if (n <= 0 || len <= 0) return hipSuccess;
+  hipLaunchKernelGGL(requant_kernel, dim3((unsigned)((n * len + 255) / 256)), dim3(256), 0, s, y, lens,
+                     len, n, yf, yq);
   return hipGetLastError();
 }

@@ -79,6 +79,18 @@ class OverlapDetectionModel(_Model):
         self._ensure_loaded()
         return self.ctx.od_pipeline(pcm, lens)
 
+    def predict_wavs_gated(self, pcm, noise, lens=None, passes=4, threshold=0.3):
+        """predict_wavs with the edge loop's silent check (record_on_pi.py:103-124): every clip is
+        denoised `passes` times against the float32 noise clip `noise` (16 kHz), a clip whose feature
+        image has an SSIM below `threshold` with its denoised image is 'silent', and the network reads
+        the denoised image -> (probs [N,2], argmax [N] (-1 = 'silent'), silent [N], ssim [N])."""
+        from . import noisereduce
+        self._ensure_loaded()
+        if passes > 0:
+            yn = np.ascontiguousarray(noise, dtype=np.float32).ravel()
+            noisereduce._set_noise(self.ctx, yn, 16000)
+        return self.ctx.od_pipeline_gated(pcm, lens, passes, threshold)
+
 
 class SpeakerIdModel(_Model):
     """SI-NET (res_model + head, speaker_identification.py:193-218,401-410): predict([N,256,39])."""
