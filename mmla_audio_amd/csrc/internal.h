@@ -140,8 +140,8 @@ struct mmla_ctx {
   // OD blocks 4-9 as one fused kernel each (odu.hip: t1 on chip); env MMLA_NO_ODU=1 at create: the
   // conv_h3 pairs (A/B, bit-identical)
   bool odu = true;
-  // ... with two strips per workgroup on one weight stream where that measured faster (odw.hip); env
-  // MMLA_NO_ODW=1 at create: odu for every block (A/B, bit-identical)
+  // ... with two strips per workgroup on one weight stream where that measured faster (odu.hip
+  // odu_two_strips); env MMLA_NO_ODW=1 at create: one strip for every block (A/B, bit-identical)
   bool odw = true;
   // OD blocks 1-3 as rolling column strips (rbs.hip); env MMLA_RB_TILE=1 at create: the 16 x 16 tile
   // kernels of resblk.hip instead

@@ -9,7 +9,6 @@
 #include "internal.h"
 #include "nets.h"
 #include "odu.h"
-#include "odw.h"
 #include "resblk.h"
 #include "siu.h"
 
@@ -153,7 +152,6 @@ enum OdPath {
   OD_STRIPS,   // rbs.hip: the whole block, rolling down 16-column strips (conv_h3 weight layout)
   OD_TILES,    // resblk.hip: the whole block on 16 x 16 tiles (fused fragment layout)
   OD_ODU,      // odu.hip: the whole block, blocks 4-9
-  OD_ODW,      // odw.hip: odu with two strips per workgroup, the blocks it is faster on
   OD_PAIR      // conv_h3 / exact-f32 launches, one per conv
 };
 struct OdChoice {
@@ -161,6 +159,8 @@ struct OdChoice {
   // block 1 only: Conv2D(16, 1x1) on the PNG image (overlap_detector_temp.py:282) computed inside
   // the block's staging (rbs.hip / resblk.hip STEM) instead of as its own launch
   bool stem;
+  // OD_ODU only: strips per workgroup, two for the blocks that are faster so (odu_two_strips)
+  int strips;
 };
 
 bool strips_ok(const ResUnitW& B, bool pool, int h, int w) {
@@ -183,18 +183,16 @@ bool odu_ok(const ResUnitW& B, bool pool, int h, int w) {
          (!pool || (B.sc.cin == B.ca.cin && B.sc.cout == B.ca.cout && B.sc.cout_pad == B.sc.cout));
 }
 
-// a block odu_ok() admits (odw takes odu's arguments) that odw.hip runs faster: blocks 7 and 8-9
-bool odw_ok(const ResUnitW& B, bool pool, int h, int w) {
-  return odw_supported(h, w, B.ca.cin, B.ca.cout, pool);
-}
-
 // stop: the debug trace's last stage (-1: none); a trace of the stem alone (0) needs it in HBM
 OdChoice od_choose(const mmla_ctx* c, const ResUnitW& B, int b, int h, int w, int stop) {
-  OdChoice k{OD_PAIR, false};
+  OdChoice k{OD_PAIR, false, 1};
   if (c->precision != MMLA_PREC_F16X3) return k;
   if (c->rbs && strips_ok(B, POOL[b], h, w)) k.path = OD_STRIPS;
   else if (tiles_ok(B, POOL[b])) k.path = OD_TILES;
-  else if (c->odu && odu_ok(B, POOL[b], h, w)) k.path = c->odw && odw_ok(B, POOL[b], h, w) ? OD_ODW : OD_ODU;
+  else if (c->odu && odu_ok(B, POOL[b], h, w)) {
+    k.path = OD_ODU;
+    k.strips = c->odw && odu_two_strips(h, w, B.ca.cin, B.ca.cout, POOL[b]) ? 2 : 1;
+  }
   k.stem = b == 0 && stop != 0 && (k.path == OD_STRIPS || k.path == OD_TILES);
   return k;
 }
@@ -351,12 +349,10 @@ int run_od_net(mmla_ctx* c, const uint8_t* img_u8, const float* img_f32, int64_t
                      : rbs_launch(r, B.ca.cin, B.ca.cout, pool, c->stream));
         break;
       }
-      case OD_ODU:   // t1 stays in LDS, bit-identical to the pair
-      case OD_ODW: {
+      case OD_ODU: {   // t1 stays in LDS, bit-identical to the pair
         const OduArgs o = odu_args(B, pool, X, T1, n, c->range_ptr);
         LAUNCH(c, MMLA_STAGE_CONV, flops,
-               k.path == OD_ODW ? odw_launch(o, h, w, B.ca.cin, B.ca.cout, pool, c->stream)
-                                : odu_launch(o, h, w, B.ca.cin, B.ca.cout, pool, c->stream));
+               odu_launch(o, h, w, B.ca.cin, B.ca.cout, pool, k.strips, c->stream));
         break;
       }
       case OD_PAIR:

@@ -29,4 +29,8 @@ struct OduArgs {
 
 // block geometry (h, w, cin, c, pool) handled by odu_launch
 bool odu_supported(int h, int w, int cin, int c, bool pool);
-hipError_t odu_launch(const OduArgs& a, int h, int w, int cin, int c, bool pool, hipStream_t stream);
+// ... of those, the blocks that measured faster with two strips per workgroup on one weight stream
+bool odu_two_strips(int h, int w, int cin, int c, bool pool);
+// strips: strips per workgroup, 1 or (where odu_two_strips) 2.  Same arguments, same bits
+hipError_t odu_launch(const OduArgs& a, int h, int w, int cin, int c, bool pool, int strips,
+                      hipStream_t stream);

@@ -34,20 +34,15 @@
 // 3xFP16 as conv_h3.hip: activations x 2^4 and weights x their power-of-two scale split into hi + lo,
 // ONE f32 accumulator per tile (hi*lo + lo*hi + hi*hi); the 2^4 is folded into the BN coefficients
 // (exact power-of-two scaling), ELU(u) * 16 = u16 > 0 ? u16 : 16 exp(u) - 16.
-#include "common.h"
+#include "f16x3.h"
 #include "resblk.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NT = 256;            // 4 waves
 constexpr int TW = 16;             // strip width (output columns)
 constexpr int R = 8;               // output rows per chunk (4 waves x 2 rows)
 constexpr int C = 32;              // output channels of blocks 1-3
-constexpr float SPLIT_MAX = 65504.0f;                    // largest finite fp16
 #ifndef RBS_TRACE
 #define RBS_TRACE 0
 #endif
@@ -61,42 +56,6 @@ __device__ unsigned long long rbs_trace_buf[2048 * 4 * 4 * 8];
 #define RBS_T(i) do { } while (0)
 #define RBS_TFLUSH() do { } while (0)
 #endif
-
-MMLA_DEV __amdgpu_buffer_rsrc_t rbs_rsrc(const void* p) {
-  const uint64_t u = reinterpret_cast<uint64_t>(p);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), (short)0,
-                                           (int)0x7fffffff, 0x00020000);
-}
-// 16 B of a split weight (conv_h3_split_weights order): wave-uniform half index u + this lane's lofs
-MMLA_DEV f16x8 rbs_frag(__amdgpu_buffer_rsrc_t r, int u, int lofs) {
-  return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(r, (uint32_t)lofs * 2u, u * 2, 0));
-}
-
-// v' (already x 2^4) = hi + lo, both fp16 (RNE); lo = f16(v' - hi) exactly rounded once (v_fma_mix)
-MMLA_DEV void split4(float a, float b, float c, float d, f16x4& h, f16x4& l) {
-  h[0] = (_Float16)a;
-  h[1] = (_Float16)b;
-  h[2] = (_Float16)c;
-  h[3] = (_Float16)d;
-  const uint2 hu = __builtin_bit_cast(uint2, h);
-  l = __builtin_bit_cast(f16x4, make_uint2(split_lo2(a, b, hu.x), split_lo2(c, d, hu.y)));
-}
-
-MMLA_DEV float amax4(float a, float b, float c, float d) {
-  return fmaxf(fmaxf(fabsf(a), fabsf(b)), fmaxf(fabsf(c), fabsf(d)));
-}
-
-// one k-step's issue order, for the scheduler: NR LDS reads (the next step's fragments), then the
-// step's three MFMAs; the sched_barrier ends the region, so nothing is hoisted across k-steps and the
-// register footprint stays at the two fragment sets
-template <int NR>
-MMLA_DEV void rbs_pin_step() {
-  if constexpr (NR > 0) __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);   // DS_READ
-  __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);                          // MFMA
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 template <int H, int W, int CIN, bool POOL>
 struct SG {
@@ -118,7 +77,7 @@ struct SG {
   static constexpr bool W2L = CIN == 16;                // GEMM 2's weights in LDS
   // ... where a GEMM 2 k-step reads four fragments from LDS (t1 and sw2, hi and lo).  Those of step
   // s + 1 go to a second register set and each k-step is pinned as "the reads for step s + 1, then
-  // the three MFMAs of step s" (rbs_pin_step), so a ds_read_b128 has 3 MFMAs (96 cycles) before its
+  // the three MFMAs of step s" (pin_group<1, NR>), so a ds_read_b128 has 3 MFMAs (96 cycles) before its
   // s_waitcnt; left to the scheduler, a source-order prefetch shares registers between the two steps
   // and issues the reads after the first or second MFMA.  Block 1's GEMM 2: 1 540 -> 1 370 cycles per
   // chunk.  GEMM 1 of either kernel and blocks 2-3's GEMM 2 (two reads per step) do not gain from the
@@ -185,7 +144,7 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) rbs_kernel(Re
   // GEMM 2's weights (8 k-steps, hi / lo) stay in registers for the whole strip: GEMM 2 then issues no
   // vector loads, so the next chunk's input loads can be in flight across it (vector loads complete
   // in issue order: a weight load behind them would wait for HBM)
-  const __amdgpu_buffer_rsrc_t rw1h = rbs_rsrc(a.w1h), rw1l = rbs_rsrc(a.w1l);
+  const __amdgpu_buffer_rsrc_t rw1h = w_rsrc(a.w1h), rw1l = w_rsrc(a.w1l);
   f16x8 w2h[G::W2L ? 1 : G::KS2], w2l[G::W2L ? 1 : G::KS2];
   if constexpr (G::W2L) {
     for (int e = tid; e < 2 * G::KS2 * 64; e += NT) {   // 16-B pieces
@@ -193,17 +152,17 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) rbs_kernel(Re
       *reinterpret_cast<f16x8*>(sw2 + 8 * e) = *reinterpret_cast<const f16x8*>((pl ? a.w2l : a.w2h) + 8 * i);
     }
   } else {
-    const __amdgpu_buffer_rsrc_t rw2h = rbs_rsrc(a.w2h), rw2l = rbs_rsrc(a.w2l);
+    const __amdgpu_buffer_rsrc_t rw2h = w_rsrc(a.w2h), rw2l = w_rsrc(a.w2l);
 #pragma unroll
     for (int s = 0; s < G::KS2; ++s) {
-      w2h[s] = rbs_frag(rw2h, s * 512, lofs);
-      w2l[s] = rbs_frag(rw2l, s * 512, lofs);
+      w2h[s] = w_frag(rw2h, s * 512, lofs);
+      w2l[s] = w_frag(rw2l, s * 512, lofs);
     }
   }
   f16x8 wsh_, wsl_;   // block 1's shortcut weights
   if constexpr (POOL) {
-    wsh_ = rbs_frag(rbs_rsrc(a.wsh), 0, lofs);
-    wsl_ = rbs_frag(rbs_rsrc(a.wsl), 0, lofs);
+    wsh_ = w_frag(w_rsrc(a.wsh), 0, lofs);
+    wsl_ = w_frag(w_rsrc(a.wsl), 0, lofs);
   }
   // this thread's staging quad: BN1 x 2^4 (exact); block 1: folded into the stem weights
   const int q = tid % G::QPP;
@@ -228,12 +187,12 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) rbs_kernel(Re
   // source: a per-clip buffer, so rows / columns outside the image read zeros with no branches
   // (offsets past the clip or negative, wrapped, are out of range)
   constexpr uint32_t ROWB = STEM ? 0u : (uint32_t)W * CIN * 4;
-  const __amdgpu_buffer_rsrc_t rx = STEM ? rbs_rsrc(nullptr) :
+  const __amdgpu_buffer_rsrc_t rx = STEM ? w_rsrc(nullptr) :
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x) + (int64_t)clip * H * W * CIN, (short)0,
                                         (int)(H * ROWB), 0x00020000);
   // block 1: the clip's image (u8 or float NHWC) through a buffer descriptor as well
   const bool im8 = STEM && a.img8 != nullptr;
-  const __amdgpu_buffer_rsrc_t rimg = !STEM ? rbs_rsrc(nullptr) :
+  const __amdgpu_buffer_rsrc_t rimg = !STEM ? w_rsrc(nullptr) :
       __builtin_amdgcn_make_buffer_rsrc(im8 ? (void*)(a.img8 + (int64_t)clip * H * W * 3)
                                             : (void*)(a.imgf + (int64_t)clip * H * W * 3),
                                         (short)0, (int)(H * W * 3 * (im8 ? 1 : 4)), 0x00020000);
@@ -361,8 +320,8 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) rbs_kernel(Re
   auto gemm1_issue = [&]() {
 #pragma unroll
     for (int s = 0; s < G::PF; ++s) {
-      w1h[s] = rbs_frag(rw1h, s * 512, lofs);
-      w1l[s] = rbs_frag(rw1l, s * 512, lofs);
+      w1h[s] = w_frag(rw1h, s * 512, lofs);
+      w1l[s] = w_frag(rw1l, s * 512, lofs);
     }
   };
   auto gemm1 = [&](int j0) -> f32x16 {
@@ -387,8 +346,8 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) rbs_kernel(Re
     for (int s = 0; s < G::KS1; ++s) {
       const f16x8 bh = w1h[s % G::PF], bl = w1l[s % G::PF];
       if (s + G::PF < G::KS1) {
-        w1h[s % G::PF] = rbs_frag(rw1h, (s + G::PF) * 512, lofs);
-        w1l[s % G::PF] = rbs_frag(rw1l, (s + G::PF) * 512, lofs);
+        w1h[s % G::PF] = w_frag(rw1h, (s + G::PF) * 512, lofs);
+        w1l[s % G::PF] = w_frag(rw1l, (s + G::PF) * 512, lofs);
       }
       const f16x8 xh = nxh, xl = nxl;
       if (s + 1 < G::KS1) {
@@ -565,7 +524,7 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) rbs_kernel(Re
         for (int s = 0; s < G::KS2; ++s) {
           if (s + 1 < G::KS2) fetch(s + 1);
           step2(fxh[s & 1], fxl[s & 1], fgh[s & 1], fgl[s & 1]);
-          if (s + 1 < G::KS2) rbs_pin_step<4>(); else rbs_pin_step<0>();
+          if (s + 1 < G::KS2) pin_group<1, 4>(); else pin_group<1, 0>();
         }
       } else {
         f16x8 nxh = *reinterpret_cast<const f16x8*>(st + to(0));

@@ -21,7 +21,7 @@
 // K runs over (tap, channel) with the channel fastest, so CIN = 16 packs two taps per k-step.
 // 3xFP16 as in conv_h3.hip: activations x 2^4 and weights x 2^8 split into hi + lo (lo unscaled),
 // ONE accumulator per tile: acc += hi*hi + hi*lo + lo*hi; value = acc * 2^-12.
-#include "common.h"
+#include "f16x3.h"
 #include "resblk.h"
 
 #define RB_MARK(k)
@@ -32,17 +32,14 @@
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NT = 256;
 constexpr int TW = 16;
 constexpr int TH = 16;                 // output rows per tile (block 1; blocks 2-3: TH_NP)
 constexpr int TH_NP = 16;          // output rows per tile of the non-pool blocks 2-3
-constexpr float ACT_SCALE = 16.0f;     // 2^4: every split activation
 // weights: split at a per-tensor power-of-two scale (resblk_split_weights; the a.u1 / a.u2 / a.us
 // epilogue factors are 2^-4 / that scale)
-constexpr float ACT_RANGE = 65504.0f / ACT_SCALE;
+constexpr float ACT_RANGE = SPLIT_MAX / ACT_SCALE;
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));

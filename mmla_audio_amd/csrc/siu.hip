@@ -22,7 +22,7 @@
 // chunks of 32, then taps, then k-steps, the three 3xFP16 products in conv_h3's order into one
 // accumulator; the transposed product sums the same terms in the same order), the same epilogue
 // arithmetic, and the same zero rows for taps that leave a clip (conv_h3's TW = 1 zero row).
-#include "common.h"
+#include "f16x3.h"
 #include "conv.h"
 #include "siu.h"
 
@@ -30,16 +30,11 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int CK = 32;                 // channel chunk (conv_h3's k order)
 constexpr int KS = CK / 16;
 constexpr int TAPS = 3;
-constexpr float ACT_SCALE = 16.0f;
-constexpr float SPLIT_MAX = 65504.0f;  // largest finite fp16 (operands are compared once scaled)
 
+// not f16x3.h's w_rsrc / w_frag: these descriptors also serve x (no readfirstlane, unbounded records)
 MMLA_DEV __amdgpu_buffer_rsrc_t siu_rsrc(const void* p) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)0xffffffff, 0x00020000);
 }

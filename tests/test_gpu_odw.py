@@ -1,5 +1,5 @@
-"""OD res_blocks on odw.hip (odu.hip's fused block kernel with two strips per workgroup sharing one
-weight stream) against odu.hip itself (env MMLA_NO_ODW=1): byte for byte at every block output of
+"""OD res_blocks on odu.hip's fused block kernel with two strips per workgroup sharing one weight
+stream against the same kernel with one strip (env MMLA_NO_ODW=1): byte for byte at every block output of
 stages 4-9 (debug trace) and at od_forward's probabilities.  The network fixes the kernels' shapes,
 so the clip count is the only size there is: n = 1 gives odd strip totals in blocks 7-9 (19 and 5
 strips per clip), so the last workgroup's second strip does not exist; n = 2 makes a workgroup's

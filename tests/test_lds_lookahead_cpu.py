@@ -96,17 +96,31 @@ def test_outstanding_scalar_read_only_completes_at_zero():
 
 
 # ---- the shipped kernels, compiled here (no GPU): register budgets and the pipelined loops ---------
-# kernel -> the VGPR cap that keeps its workgroups per CU (rbs: 3 and 2; odu: 4, 3, 3, 3)
+# kernel -> the VGPR cap that keeps its workgroups per CU (rbs: 3 and 2; odu with one strip per
+# workgroup: 4, 3, 3, 3, with two: 2 and 2)
+# odu_kernel<H, W, CIN, C, TW, POOL, NS (strips per workgroup), DBUF, NW, MINW, LA, LB>
+ODU_BLOCK_7_TWO_STRIPS = 'odu_kernel<32, 38, 64, 128, 2, true, 2, true, 4, 2, 1, 1>'
+ODU_BLOCKS_8_9_TWO_STRIPS = 'odu_kernel<16, 19, 128, 128, 4, false, 2, false, 4, 2, 1, 1>'
 BUDGET = {
     'rbs_kernel<128, 151, 16, true, true>': 168,
     'rbs_kernel<64, 76, 32, false, false>': 256,
-    'odu_kernel<64, 76, 32, 64, 2, true, 4, 4, 0, 0>': 128,
-    'odu_kernel<32, 38, 64, 64, 4, false, 4, 3, 1, 1>': 168,
-    'odu_kernel<32, 38, 64, 128, 2, true, 4, 2, 1, 1>': 168,
-    'odu_kernel<16, 19, 128, 128, 4, false, 4, 2, 1, 1>': 168,
+    'odu_kernel<64, 76, 32, 64, 2, true, 1, false, 4, 4, 0, 0>': 128,
+    'odu_kernel<32, 38, 64, 64, 4, false, 1, false, 4, 3, 1, 1>': 168,
+    'odu_kernel<32, 38, 64, 128, 2, true, 1, true, 4, 2, 1, 1>': 168,
+    'odu_kernel<16, 19, 128, 128, 4, false, 1, true, 4, 2, 1, 1>': 168,
+    ODU_BLOCK_7_TWO_STRIPS: 256,
+    ODU_BLOCKS_8_9_TWO_STRIPS: 256,
 }
-LDS = {'rbs_kernel<128': 51072, 'rbs_kernel<64': 45952, 'odu_kernel<64': 38592,
-       'odu_kernel<32, 38, 64, 64': 40320, 'odu_kernel<32, 38, 64, 128': 39168, 'odu_kernel<16': 41472}
+LDS = {
+    'rbs_kernel<128, 151, 16, true, true>': 51072,
+    'rbs_kernel<64, 76, 32, false, false>': 45952,
+    'odu_kernel<64, 76, 32, 64, 2, true, 1, false, 4, 4, 0, 0>': 38592,
+    'odu_kernel<32, 38, 64, 64, 4, false, 1, false, 4, 3, 1, 1>': 40320,
+    'odu_kernel<32, 38, 64, 128, 2, true, 1, true, 4, 2, 1, 1>': 39168,
+    'odu_kernel<16, 19, 128, 128, 4, false, 1, true, 4, 2, 1, 1>': 41472,
+    ODU_BLOCK_7_TWO_STRIPS: 78336,
+    ODU_BLOCKS_8_9_TWO_STRIPS: 80512,
+}
 
 
 @pytest.fixture(scope='module')
@@ -130,8 +144,22 @@ def test_register_budgets_no_spills_same_lds(compiled):
         assert m['vgpr_count'] <= cap, (name, m['vgpr_count'])
         assert m['vgpr_spill_count'] == 0 and m['sgpr_spill_count'] == 0, name
         assert m['private_segment_fixed_size'] == 0, name
-        lds = next(v for k, v in LDS.items() if name.startswith(k))
-        assert m['group_segment_fixed_size'] == lds, name
+        assert m['group_segment_fixed_size'] == LDS[name], name
+
+
+def test_two_strip_instantiations_fit_two_workgroups_per_cu(compiled):
+    """exactly two instantiations run two strips per workgroup, blocks 7 and 8-9 (the ones
+    odu_two_strips names); each keeps two workgroups per CU: at most 256 VGPRs (two waves per SIMD),
+    no spills, no scratch, at most 81 920 B of LDS (half of a CU's 160 KB)"""
+    two = {n: m for n, (m, _) in compiled.items()
+           if n.startswith('odu_kernel<') and n.split(', ')[6] == '2'}
+    assert sorted(two) == sorted([ODU_BLOCK_7_TWO_STRIPS, ODU_BLOCKS_8_9_TWO_STRIPS])
+    for name, m in two.items():
+        print(name, m)
+        assert m['vgpr_count'] <= 256, (name, m['vgpr_count'])
+        assert m['vgpr_spill_count'] == 0 and m['sgpr_spill_count'] == 0, name
+        assert m['private_segment_fixed_size'] == 0, name
+        assert m['group_segment_fixed_size'] <= 81920, (name, m['group_segment_fixed_size'])
 
 
 def test_pipelined_loops_read_three_mfmas_ahead(compiled):
