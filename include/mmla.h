@@ -124,6 +124,10 @@ int mmla_range_check(mmla_ctx* ctx, int64_t* f32_reruns);
  * reuse until mmla_release_workspace or mmla_destroy.  mmla_od_pipeline_gated with nr_passes > 0 adds
  * per clip the second image (58 KB) and two float clip buffers (2 x 4 x min(clip_len, 24000) bytes,
  * 192 KB), and per launch of the noise gate (at most 512 clips) ~6.9 MB of gate scratch per clip.
+ * mmla_condition and the conditioned pipelines add per clip two float buffers and one int16 buffer of
+ * clip_len samples (10 x clip_len bytes: 0.41 MB at 40960), a byte per 30 ms frame, and the gate's
+ * scratch (~8.3 MB per clip at 40960 samples, at most 512 clips at a time); their micro-batches are
+ * multiples of items_per_stream (at least one stream, even where a smaller size was set here).
  */
 int mmla_set_microbatch(mmla_ctx* ctx, int64_t od_clips, int64_t si_clips);
 /* The micro-batch sizes the next call would use. */
@@ -326,6 +330,67 @@ int mmla_vad_collect(mmla_ctx* ctx, const int16_t* pcm, int64_t n_items, int64_t
                      const int32_t* lens, int32_t clip_len, const uint8_t* speech, int32_t max_frames,
                      int16_t* out, int32_t* out_lens, uint32_t flags);
 int mmla_pcm16(mmla_ctx* ctx, const float* y, int64_t n, int16_t* out, uint32_t flags);
+
+/*
+ * A bank of noise profiles: one per microphone of a room served by one context (each microphone
+ * records its own ambient noise at start-up: recording(..., noise_reduced=False) -> NOISE_PATH,
+ * OverlapDetection/scripts/record_on_pc.py:133).
+ * mmla_nr_set_noise_bank: profile p = noise + p * stride, its first lens[p] samples (lens nullable:
+ *   len; 2 <= lens[p] <= len, host pointers: checked, device pointers: clamped by the kernels) ->
+ *   thresholds [n_profiles][513] kept in the context, replacing the bank it held.  All profiles come
+ *   from one launch sequence with one stream synchronisation.  mmla_nr_set_noise is a bank of one.
+ * mmla_nr_reduce_bank: mmla_nr_reduce with signal i gated against profile[i] (nullable: profile 0, the
+ *   bits of mmla_nr_reduce).  Host pointers: a profile[i] outside [0, n_profiles) is MMLA_E_INVALID;
+ *   device pointers cannot be checked, the kernels clamp the index into the bank (the convention of
+ *   the VAD's lens).
+ */
+int mmla_nr_set_noise_bank(mmla_ctx* ctx, const float* noise, int64_t n_profiles, int64_t stride,
+                           const int32_t* lens, int32_t len, int32_t sr, uint32_t flags);
+int mmla_nr_reduce_bank(mmla_ctx* ctx, const float* y, int64_t n_signals, int64_t stride, int64_t len,
+                        const int32_t* profile, float* out, uint32_t flags);
+
+/*
+ * The PC loops' pre-conditioning of every recorded clip as one batched call: the batched
+ * save_wave_file(noise_reduce=True, silence_remove=...) of OverlapDetection/scripts/record_on_pc.py:133,
+ * 141-154,200-226, SpeakerIdentification/scripts/record_on_pc.py:117-134,178-205 and
+ * SpeakerIdentification/scripts/record_on_pi.py:101-127,228-240.  Per clip c, over its whole length:
+ *   y = pcm / 32768, then nr_passes times (the loops: 1; standardize_audio: 3) the stationary gate with
+ *     noise profile profile[c] (nullable: profile 0) of the bank, written as PCM_16 (mmla_pcm16's rule)
+ *     and read back.  With lens the clip is gated zero-extended to clip_len and the samples from lens[c]
+ *     on are zeroed after every pass (mmla_od_pipeline_gated's rule);
+ *   silence_remove != 0: mmla_vad_remove_silence on the int16 result with that call's stream layout --
+ *     stream s owns clips [s * items_per_stream, (s + 1) * items_per_stream), in order, on the detector
+ *     state mmla_vad_reset created, which persists across calls;
+ *   kept_len[c] = the samples the rewritten file holds (a multiple of 480 after silence removal, else
+ *     the clip's length); out_pcm [n_clips, clip_len] = those samples, then zeros.  Both nullable.
+ * MMLA_E_INVALID: clip_len outside [1, 600000] (one gate chunk), clip_stride < clip_len, nr_passes < 0,
+ * nr_passes > 0 without a noise bank, n_clips not a multiple of items_per_stream, silence_remove without
+ * an mmla_vad_reset of n_clips / items_per_stream streams, a host profile[c] outside the bank (device
+ * pointers: clamped by the kernels).
+ * Micro-batched in whole streams (multiples of items_per_stream, at least one stream even where
+ * mmla_set_microbatch asks for less); the detectors advance exactly once per clip whatever the
+ * micro-batch size and whether a micro-batch had to be re-run.  The gate runs at most 512 clips per
+ * launch with a stream synchronisation between launches and between passes, so with MMLA_DEVICE_PTR and
+ * nr_passes > 0 these calls synchronise the context stream internally (their last launches are still
+ * only enqueued).
+ * mmla_{od,si}_pipeline_conditioned: the conditioning, then mmla_{od,si}_pipeline on the conditioned
+ * clips with lens = kept_len: silent[c] = kept_len[c] < 4000 (record_on_pc.py:141-154), argmax -1 there.
+ * nr_passes = 0 with silence_remove = 0 is mmla_{od,si}_pipeline bit for bit.
+ */
+int mmla_condition(mmla_ctx* ctx, const int16_t* pcm, int64_t n_clips, int64_t clip_stride,
+                   const int32_t* lens, int32_t clip_len, const int32_t* profile, int32_t nr_passes,
+                   int32_t silence_remove, int64_t items_per_stream, int16_t* out_pcm,
+                   int32_t* kept_len, uint32_t flags);
+int mmla_od_pipeline_conditioned(mmla_ctx* ctx, const int16_t* pcm, int64_t n_clips, int64_t clip_stride,
+                                 const int32_t* lens, int32_t clip_len, const int32_t* profile,
+                                 int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
+                                 int16_t* out_pcm, int32_t* kept_len, float* probs, int32_t* argmax,
+                                 uint8_t* silent, uint32_t flags);
+int mmla_si_pipeline_conditioned(mmla_ctx* ctx, const int16_t* pcm, int64_t n_clips, int64_t clip_stride,
+                                 const int32_t* lens, int32_t clip_len, const int32_t* profile,
+                                 int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
+                                 int16_t* out_pcm, int32_t* kept_len, float* probs, int32_t* argmax,
+                                 uint8_t* silent, uint32_t flags);
 
 /*
  * Rate conversion of the offline pre-conditioning (resample.hip).

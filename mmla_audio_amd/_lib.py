@@ -36,6 +36,13 @@ _U32 = ctypes.c_uint32
 SIGNATURES = {
     'mmla_nr_set_noise': [_P, _P, _I64, ctypes.c_int32, ctypes.c_uint32],
     'mmla_nr_reduce': [_P, _P, _I64, _I64, _I64, _P, ctypes.c_uint32],
+    'mmla_nr_set_noise_bank': [_P, _P, _I64, _I64, _P, _I32, _I32, _U32],
+    'mmla_nr_reduce_bank': [_P, _P, _I64, _I64, _I64, _P, _P, _U32],
+    'mmla_condition': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P, _U32],
+    'mmla_od_pipeline_conditioned': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P,
+                                     _P, _P, _P, _U32],
+    'mmla_si_pipeline_conditioned': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P,
+                                     _P, _P, _P, _U32],
     'mmla_abi_version': [],
     'mmla_crc32c': [_P, _I64, ctypes.POINTER(_U32)],
     'mmla_png_unfilter': [_P, _I64, _I64, _I32, _P],
@@ -267,6 +274,7 @@ class Context:
         a = np.ascontiguousarray(noise, dtype=np.float32).ravel()
         self._check(self.lib.mmla_nr_set_noise(self.h, _ptr(a), a.size, int(sr), 0),
                     'mmla_nr_set_noise')
+        self._nr_key = None     # what noisereduce._set_noise / _set_noise_bank cached is replaced
 
     def nr_reduce(self, y):
         """Gate float32 signals y [n, len] (or [len]) with the current noise profile."""
@@ -282,6 +290,53 @@ class Context:
     def nr_reduce_dev(self, y, n, stride, length, out):
         self._check(self.lib.mmla_nr_reduce(self.h, y, n, stride, length, out, MMLA_DEVICE_PTR),
                     'mmla_nr_reduce(dev)')
+
+    def nr_set_noise_bank(self, noises, sr=16000):
+        """One noise profile per microphone, all from one launch sequence: `noises` is a list of
+        float32 clips (their lengths may differ) or an array [P, len].  Replaces the bank (and the
+        profile of nr_set_noise, which is a bank of one)."""
+        if isinstance(noises, np.ndarray) and noises.ndim == 2:
+            a = np.ascontiguousarray(noises, dtype=np.float32)
+            ln = None
+        else:
+            clips = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in noises]
+            a = np.zeros((len(clips), max([x.size for x in clips] + [1])), np.float32)
+            ln = np.array([x.size for x in clips], np.int32)
+            for i, x in enumerate(clips):
+                a[i, :x.size] = x
+        self._check(self.lib.mmla_nr_set_noise_bank(self.h, _ptr(a), a.shape[0], a.shape[1], _ptr(ln),
+                                                    a.shape[1], int(sr), 0), 'mmla_nr_set_noise_bank')
+        self.nr_bank_builds = getattr(self, 'nr_bank_builds', 0) + 1
+        self._nr_key = None
+
+    def nr_reduce_bank(self, y, profile=None):
+        """nr_reduce with signal i gated against noise profile profile[i] of the bank (an int: every
+        signal against that profile; None: profile 0)."""
+        a = np.ascontiguousarray(y, dtype=np.float32)
+        flat = a.ndim == 1
+        if flat:
+            a = a[None]
+        pr = self._profile(profile, a.shape[0])
+        out = np.empty_like(a)
+        self._check(self.lib.mmla_nr_reduce_bank(self.h, _ptr(a), a.shape[0], a.shape[1], a.shape[1],
+                                                 _ptr(pr), _ptr(out), 0), 'mmla_nr_reduce_bank')
+        return out[0] if flat else out
+
+    def nr_reduce_bank_dev(self, y, n, stride, length, out, profile=0):
+        """profile: device int32 [n] (0: profile 0); indices outside the bank are clamped"""
+        self._check(self.lib.mmla_nr_reduce_bank(self.h, y, n, stride, length, profile or None, out,
+                                                 MMLA_DEVICE_PTR), 'mmla_nr_reduce_bank(dev)')
+
+    @staticmethod
+    def _profile(profile, n):
+        if profile is None:
+            return None
+        if np.ndim(profile) == 0:
+            return np.full(n, int(profile), np.int32)
+        pr = np.ascontiguousarray(profile, dtype=np.int32)
+        if pr.shape != (n,):
+            raise ValueError(f'profile {pr.shape}: expected one index per clip ({n})')
+        return pr
 
     # -- silence removal (SURVEY.md 8f row 2) -----------------------------------------------------
     def vad_reset(self, n_streams=1, mode=3):
@@ -539,6 +594,51 @@ class Context:
             _ptr(am), _ptr(silent), _ptr(ssim), 0), 'mmla_od_pipeline_gated')
         return probs, am, silent.astype(bool), ssim
 
+    # -- the PC loops' pre-conditioning (noise gate + silence removal) in front of the networks ---
+    def _conditioned(self, fn, what, pcm, lens, profile, passes, silence_remove, items_per_stream,
+                     n_classes, return_pcm):
+        a, ln, L = self._pcm(pcm, lens)
+        n = a.shape[0]
+        pr = self._profile(profile, n)
+        out = np.empty_like(a) if return_pcm else None
+        kept = np.empty(n, np.int32)
+        head = (self.h, _ptr(a), n, a.shape[1], _ptr(ln), L, _ptr(pr), int(passes),
+                int(bool(silence_remove)), int(items_per_stream), _ptr(out), _ptr(kept))
+        if n_classes is None:
+            self._check(fn(*head, 0), what)
+            return out, kept
+        probs = np.empty((n, n_classes), np.float32)
+        am = np.empty(n, np.int32)
+        silent = np.empty(n, np.uint8)
+        self._check(fn(*head, _ptr(probs), _ptr(am), _ptr(silent), 0), what)
+        res = (probs, am, silent.astype(bool), kept)
+        return res + (out,) if return_pcm else res
+
+    def condition(self, pcm, lens=None, profile=None, passes=1, silence_remove=True,
+                  items_per_stream=1):
+        """The batched save_wave_file(noise_reduce=True, silence_remove=...) of record_on_pc.py: int16
+        [n, L] (or a list) -> (conditioned int16 [n, L], zeros behind each clip's kept samples; kept_len
+        [n]).  Clip c is gated `passes` times against noise profile profile[c] (nr_set_noise_bank; None:
+        profile 0); silence removal runs on the vad_reset detectors, stream s owning clips
+        [s * items_per_stream, (s + 1) * items_per_stream), and their state persists across calls."""
+        return self._conditioned(self.lib.mmla_condition, 'mmla_condition', pcm, lens, profile, passes,
+                                 silence_remove, items_per_stream, None, True)
+
+    def od_pipeline_conditioned(self, pcm, lens=None, profile=None, passes=1, silence_remove=True,
+                                items_per_stream=1, return_pcm=False):
+        """condition() fused in front of od_pipeline -> (probs [n,2], argmax [n] (-1 = 'silent': fewer
+        than 4000 samples kept), silent [n] bool, kept_len [n]); return_pcm adds the conditioned clips."""
+        return self._conditioned(self.lib.mmla_od_pipeline_conditioned, 'mmla_od_pipeline_conditioned',
+                                 pcm, lens, profile, passes, silence_remove, items_per_stream, 2,
+                                 return_pcm)
+
+    def si_pipeline_conditioned(self, pcm, lens=None, profile=None, passes=1, silence_remove=True,
+                                items_per_stream=1, return_pcm=False):
+        """condition() fused in front of si_pipeline -> (probs [n,K], argmax, silent, kept_len)"""
+        return self._conditioned(self.lib.mmla_si_pipeline_conditioned, 'mmla_si_pipeline_conditioned',
+                                 pcm, lens, profile, passes, silence_remove, items_per_stream,
+                                 self.si_classes or 0, return_pcm)
+
     def ssim_u8(self, a, b):
         """Mean SSIM (scikit-image defaults, multichannel) of uint8 image pairs a, b [n,h,w,c] (or one
         pair [h,w,c]) -> float32 [n] (or a scalar)."""
@@ -623,6 +723,34 @@ class Context:
             self.h, pcm, n, stride, lens or None, clip_len, int(passes), float(threshold),
             probs or None, argmax or None, silent or None, ssim or None, MMLA_DEVICE_PTR),
             'mmla_od_pipeline_gated(dev)')
+
+    def condition_dev(self, pcm, n, stride, clip_len, passes=1, silence_remove=True,
+                      items_per_stream=1, out_pcm=0, kept_len=0, lens=0, profile=0):
+        """synchronises the context stream internally when passes > 0 (see mmla.h)"""
+        self._check(self.lib.mmla_condition(
+            self.h, pcm, n, stride, lens or None, clip_len, profile or None, int(passes),
+            int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
+            MMLA_DEVICE_PTR), 'mmla_condition(dev)')
+
+    def od_pipeline_conditioned_dev(self, pcm, n, stride, clip_len, passes=1, silence_remove=True,
+                                    items_per_stream=1, probs=0, argmax=0, silent=0, out_pcm=0,
+                                    kept_len=0, lens=0, profile=0):
+        """synchronises the context stream internally when passes > 0 (see mmla.h)"""
+        self._check(self.lib.mmla_od_pipeline_conditioned(
+            self.h, pcm, n, stride, lens or None, clip_len, profile or None, int(passes),
+            int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
+            probs or None, argmax or None, silent or None, MMLA_DEVICE_PTR),
+            'mmla_od_pipeline_conditioned(dev)')
+
+    def si_pipeline_conditioned_dev(self, pcm, n, stride, clip_len, passes=1, silence_remove=True,
+                                    items_per_stream=1, probs=0, argmax=0, silent=0, out_pcm=0,
+                                    kept_len=0, lens=0, profile=0):
+        """synchronises the context stream internally when passes > 0 (see mmla.h)"""
+        self._check(self.lib.mmla_si_pipeline_conditioned(
+            self.h, pcm, n, stride, lens or None, clip_len, profile or None, int(passes),
+            int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
+            probs or None, argmax or None, silent or None, MMLA_DEVICE_PTR),
+            'mmla_si_pipeline_conditioned(dev)')
 
     def ssim_u8_dev(self, a, b, n, h, w, c, out):
         self._check(self.lib.mmla_ssim_u8(self.h, a, b, n, h, w, c, out, MMLA_DEVICE_PTR),

@@ -97,40 +97,78 @@ constexpr int64_t kNrChunk = 600000, kNrPadding = 30000;   // noisereduce 2.0 de
 constexpr int64_t kNrItemsPerLaunch = 512;                  // ~3.4 GB of scratch per launch (2.5 s)
 }  // namespace
 
-int mmla_nr_set_noise(mmla_ctx* c, const float* noise, int64_t n_noise, int32_t sr, uint32_t flags) {
-  if (!c) return MMLA_E_INVALID;
-  if (!noise || n_noise < 2) return fail(c, MMLA_E_INVALID, "noise clip needs >= 2 samples");
+// the body of both profile setters: profile p = noise + p * stride, lens[p] (nullable: len) samples
+static int nr_set_bank(mmla_ctx* c, const float* noise, int64_t n_profiles, int64_t stride,
+                       const int32_t* lens, int64_t len, int32_t sr, uint32_t flags) {
+  if (!noise || len < 2) return fail(c, MMLA_E_INVALID, "noise clip needs >= 2 samples");
+  if (n_profiles < 1 || n_profiles > 65535 || (n_profiles > 1 && stride < len))
+    return fail(c, MMLA_E_INVALID, "bad noise bank (%lld profiles of %lld samples at stride %lld)",
+                (long long)n_profiles, (long long)len, (long long)stride);
   if (sr != 16000) return fail(c, MMLA_E_INVALID, "noise gate supports sr = 16000 (got %d)", sr);
-  HIPCHK(c, hipSetDevice(c->device));
   const bool dev = flags & MMLA_DEVICE_PTR;
+  // device-pointer lens cannot be seen here: the kernels clamp them into [2, len]
+  if (lens && !dev)
+    for (int64_t p = 0; p < n_profiles; ++p)
+      if (lens[p] < 2 || lens[p] > len)
+        return fail(c, MMLA_E_INVALID, "noise lens[%lld] = %d outside [2, %lld]", (long long)p, lens[p],
+                    (long long)len);
+  HIPCHK(c, hipSetDevice(c->device));
+  constexpr int64_t bins = NR_NFFT / 2 + 1;
   if (!c->nr_tables) {
     NrTables t;
     nr_build_tables(&t, sr);
     if (t.ngf != NR_NGF || t.ngt != NR_NGT) return fail(c, MMLA_E_INVALID, "smoothing filter shape");
     HIPCHK(c, hipMalloc(&c->nr_tables, sizeof(NrTables)));
-    HIPCHK(c, hipMalloc(&c->nr_thresh, (NR_NFFT / 2 + 1) * sizeof(float)));
     HIPCHK(c, hipMemcpy(c->nr_tables, &t, sizeof(t), hipMemcpyHostToDevice));
   }
-  const int64_t m = std::min(n_noise, kNrChunk);   // clip_noise_stationary: y_noise[:chunk_size]
-  const int64_t Tn = 1 + m / NR_HOP;
-  const float* dn;
+  if (c->nr_profiles != n_profiles) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // a gate still reading the old bank
+    if (c->nr_thresh) HIPCHK(c, hipFree(c->nr_thresh));
+    c->nr_thresh = nullptr;
+    c->nr_profiles = 0;
+    c->nr_ready = false;
+    HIPCHK(c, hipMalloc(&c->nr_thresh, (size_t)n_profiles * bins * sizeof(float)));
+    c->nr_profiles = n_profiles;
+  }
+  const int64_t m = std::min(len, kNrChunk);   // clip_noise_stationary: y_noise[:chunk_size]
+  const int64_t Tmax = 1 + m / NR_HOP;
+  NrNoiseArgs a{};
   void *pdb = nullptr, *pmx = nullptr;
-  CHK(in_ptr(c, noise, m, dev, S_IN, &dn));
-  CHK(ws_get(c, S_NR_FRAMES, (size_t)Tn * (NR_NFFT / 2 + 1) * sizeof(float), &pdb));
-  CHK(ws_get(c, S_NR_FMAX, (size_t)Tn * sizeof(float), &pmx));
-  LAUNCH(c, MMLA_STAGE_NR, (double)m * 4,
-         nr_noise_launch(dn, m, c->nr_tables, static_cast<float*>(pdb), static_cast<float*>(pmx),
-                         1.5f, c->nr_thresh, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  CHK(in_ptr(c, noise, (size_t)((n_profiles - 1) * stride + m), dev, S_IN, &a.noise));
+  CHK(in_ptr(c, lens, (size_t)n_profiles, dev, S_NR_PROF, &a.lens));
+  CHK(ws_get(c, S_NR_FRAMES, (size_t)n_profiles * Tmax * bins * sizeof(float), &pdb));
+  CHK(ws_get(c, S_NR_FMAX, (size_t)n_profiles * Tmax * sizeof(float), &pmx));
+  a.stride = stride;
+  a.m = m;
+  a.n_profiles = (int)n_profiles;
+  a.tables = c->nr_tables;
+  a.db = static_cast<float*>(pdb);
+  a.fmaxv = static_cast<float*>(pmx);
+  a.n_std = 1.5f;
+  a.thresh = c->nr_thresh;
+  LAUNCH(c, MMLA_STAGE_NR, (double)n_profiles * m * 4, nr_noise_launch(a, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // one synchronisation per bank
   c->nr_ready = true;
   return MMLA_OK;
+}
+
+int mmla_nr_set_noise(mmla_ctx* c, const float* noise, int64_t n_noise, int32_t sr, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  // a bank of one, in slot 0 (only the first chunk_size samples enter the profile)
+  return nr_set_bank(c, noise, 1, 0, nullptr, std::min(n_noise, kNrChunk), sr, flags);
+}
+
+int mmla_nr_set_noise_bank(mmla_ctx* c, const float* noise, int64_t n_profiles, int64_t stride,
+                           const int32_t* lens, int32_t len, int32_t sr, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  return nr_set_bank(c, noise, n_profiles, stride, lens, len, sr, flags);
 }
 
 }  // extern "C"
 
 // the gate of mmla_nr_reduce on device pointers; mmla_od_pipeline_gated runs its passes through it too
 int mmla::nr_reduce_dev(mmla_ctx* c, const float* dy, int64_t n_signals, int64_t stride, int64_t len,
-                        float* dout) {
+                        float* dout, const int32_t* dprofile) {
   if (!c->nr_ready) return fail(c, MMLA_E_INVALID, "mmla_nr_set_noise must be called first");
   if (n_signals <= 0 || len <= 0) return MMLA_OK;
   // SpectralGate.get_traces: one chunk of `len` when len <= chunk_size, else chunk_size pieces
@@ -145,7 +183,7 @@ int mmla::nr_reduce_dev(mmla_ctx* c, const float* dy, int64_t n_signals, int64_t
   for (int64_t sgl = 0; sgl < n_signals; ++sgl)
     for (int64_t k = 0; k < per; ++k)
       items.push_back(NrItem{sgl * stride, len, k * keep - kNrPadding, sgl * len + k * keep,
-                             std::min(keep, len - k * keep)});
+                             std::min(keep, len - k * keep), sgl});
   for (size_t i0 = 0; i0 < items.size(); i0 += cap) {
     const int64_t ni = std::min<int64_t>(cap, (int64_t)items.size() - (int64_t)i0);
     void *pS, *pB, *pM, *pF, *pI, *pR;
@@ -170,6 +208,8 @@ int mmla::nr_reduce_dev(mmla_ctx* c, const float* dy, int64_t n_signals, int64_t
     a.t_n = t_hi - a.t_lo + 1;
     a.tables = c->nr_tables;
     a.thresh = c->nr_thresh;
+    a.profile = dprofile;
+    a.n_profiles = (int)c->nr_profiles;
     a.prop_decrease = 1.0;
     a.S = static_cast<double2*>(pS);
     a.bits = static_cast<uint8_t*>(pB);
@@ -189,28 +229,47 @@ int mmla::nr_reduce_dev(mmla_ctx* c, const float* dy, int64_t n_signals, int64_t
 
 extern "C" {
 
-int mmla_nr_reduce(mmla_ctx* c, const float* y, int64_t n_signals, int64_t stride, int64_t len,
-                   float* out, uint32_t flags) {
-  if (!c) return MMLA_E_INVALID;
+static int nr_reduce_common(mmla_ctx* c, const float* y, int64_t n_signals, int64_t stride, int64_t len,
+                            const int32_t* profile, float* out, uint32_t flags) {
   if (n_signals < 0 || len < 0 || (n_signals > 0 && (!y || !out)) ||
       (n_signals > 1 && stride < len))
     return fail(c, MMLA_E_INVALID, "bad nr_reduce args");
   if (!c->nr_ready) return fail(c, MMLA_E_INVALID, "mmla_nr_set_noise must be called first");
+  const bool dev = flags & MMLA_DEVICE_PTR;
+  // device-pointer profile indices cannot be seen here: the kernels clamp them into the bank
+  if (profile && !dev)
+    for (int64_t i = 0; i < n_signals; ++i)
+      if (profile[i] < 0 || profile[i] >= c->nr_profiles)
+        return fail(c, MMLA_E_INVALID, "profile[%lld] = %d outside the bank of %lld", (long long)i,
+                    profile[i], (long long)c->nr_profiles);
   if (n_signals == 0 || len == 0) return MMLA_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  const bool dev = flags & MMLA_DEVICE_PTR;
   // signals: the caller's device pointer, or one host copy per call
   const float* dy;
+  const int32_t* dprof;
   CHK(in_ptr(c, y, (n_signals - 1) * stride + len, dev, S_NR_Y, &dy));
+  CHK(in_ptr(c, profile, (size_t)n_signals, dev, S_NR_PROF, &dprof));
   float* dout = out;
   if (!dev) {
     void* p = nullptr;
     CHK(ws_get(c, S_OUT0, (size_t)n_signals * len * sizeof(float), &p));
     dout = static_cast<float*>(p);
   }
-  CHK(nr_reduce_dev(c, dy, n_signals, stride, len, dout));
+  CHK(nr_reduce_dev(c, dy, n_signals, stride, len, dout, dprof));
   CHK(copy_back(c, out, 0, dout, (size_t)n_signals * len, dev));
   return finish(c, dev);
+}
+
+int mmla_nr_reduce(mmla_ctx* c, const float* y, int64_t n_signals, int64_t stride, int64_t len,
+                   float* out, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  return nr_reduce_common(c, y, n_signals, stride, len, nullptr, out, flags);
+}
+
+int mmla_nr_reduce_bank(mmla_ctx* c, const float* y, int64_t n_signals, int64_t stride, int64_t len,
+                        const int32_t* profile, float* out, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  return nr_reduce_common(c, y, n_signals, stride, len, profile, out, flags);
 }
 
 // ---- silence removal: webrtcvad + vad_collector, soundfile PCM_16 ------------
@@ -225,7 +284,8 @@ int mmla_vad_reset(mmla_ctx* c, int64_t n_streams, int32_t mode) {
   if (c->vad_state) HIPCHK(c, hipFree(c->vad_state));
   c->vad_state = nullptr;
   c->vad_streams = 0;
-  if (hipMalloc(&c->vad_state, n_streams * sizeof(VadState)) != hipSuccess) {
+  // twice the states: [n_streams, 2 n_streams) is the conditioned calls' snapshot (internal.h)
+  if (hipMalloc(&c->vad_state, 2 * n_streams * sizeof(VadState)) != hipSuccess) {
     (void)hipGetLastError();
     return fail(c, MMLA_E_OOM, "VAD state for %lld streams", (long long)n_streams);
   }

@@ -178,10 +178,14 @@ struct mmla_ctx {
   int64_t range_reruns = 0;
   bool od_f32_only = false, si_f32_only = false;   // weights outside the fp16 range
   bool loading_f16_bad = false;                     // mmla_load_weights scratch
-  VadState* vad_state = nullptr;   // mmla_vad_reset: webrtcvad.Vad(mode) per stream (device)
+  // mmla_vad_reset: webrtcvad.Vad(mode) per stream (device), [2 * vad_streams]: the second half
+  // holds the states a conditioned micro-batch started from, for its re-runs (pipeline.cpp)
+  VadState* vad_state = nullptr;
   int64_t vad_streams = 0;
-  NrTables* nr_tables = nullptr;   // noise gate (nr.hip): tables + the noise profile's threshold
+  // noise gate (nr.hip): tables + the bank of noise profiles' thresholds [nr_profiles][513]
+  NrTables* nr_tables = nullptr;
   float* nr_thresh = nullptr;
+  int64_t nr_profiles = 0;
   bool nr_ready = false;
 };
 
@@ -223,7 +227,8 @@ enum Slot {
   S_NR_S, S_NR_BITS, S_NR_FMAX, S_NR_FRAMES, S_NR_ITEMS, S_NR_Y, S_NR_ROWS,
   S_VAD_SPEECH, S_VAD_OUT, S_VAD_LENS, S_RS_TR, S_RS_WIN, S_LSTM,
   S_TRAIN,  // mmla_si_head_fit: every host-pointer operand, carved from one slot
-  S_IMG2, S_GATE_Y0, S_GATE_Y1, S_SSIM   // mmla_od_pipeline_gated / mmla_ssim_u8
+  S_IMG2, S_GATE_Y0, S_GATE_Y1, S_SSIM,   // mmla_od_pipeline_gated / mmla_ssim_u8
+  S_NR_PROF, S_COND_Q, S_COND_KEPT        // profile indices of the gate; mmla_condition's outputs
 };
 
 int ws_get(mmla_ctx* c, int slot, size_t bytes, void** out);
@@ -233,8 +238,10 @@ int64_t microbatch(mmla_ctx* c, bool od);
 int finish(mmla_ctx* c, bool dev);
 void free_allocs(std::vector<void*>& al);   // weights.cpp
 // the body of mmla_nr_reduce on device pointers (capi.cpp): y [n_signals, stride] -> out [n_signals,
-// len].  At most 512 items per launch with a stream synchronisation between launches.
-int nr_reduce_dev(mmla_ctx* c, const float* y, int64_t n_signals, int64_t stride, int64_t len, float* out);
+// len].  At most 512 items per launch with a stream synchronisation between launches.  profile
+// (device, nullable = all 0): signal i is gated with noise profile profile[i] of the bank.
+int nr_reduce_dev(mmla_ctx* c, const float* y, int64_t n_signals, int64_t stride, int64_t len, float* out,
+                  const int32_t* profile = nullptr);
 
 // device view of `count` input elements: the caller's pointer (device mode) or a copy in `slot`
 template <typename T>

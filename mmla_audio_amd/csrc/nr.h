@@ -20,9 +20,10 @@ struct NrTables {
 };
 
 // one buffer of L samples: buffer index u <-> signal index i1 + u (zeros outside [0, n));
-// output = buffer [keep0, keep0 + out_len) -> out[out_off ..]
+// output = buffer [keep0, keep0 + out_len) -> out[out_off ..]; prof: the item's entry of
+// NrArgs::profile (its signal's index), whose value selects the noise profile
 struct NrItem {
-  int64_t sig_off, n, i1, out_off, out_len;
+  int64_t sig_off, n, i1, out_off, out_len, prof;
 };
 
 struct NrArgs {
@@ -35,7 +36,9 @@ struct NrArgs {
                                 // window or whose mask the gate needs (host: nr_frame_range)
   int64_t keep0, keep_len;      // kept interior of every buffer
   const NrTables* tables;
-  const float* thresh;          // [513] noise threshold (dB, float32)
+  const float* thresh;          // [n_profiles][513] noise thresholds (dB, float32)
+  const int32_t* profile;       // nullable (profile 0): profile[item.prof] selects the item's
+  int n_profiles;               //   threshold row, clamped into [0, n_profiles) by the kernels
   double prop_decrease;
   double2* S;                   // scratch [n_items][T][513] complex128
   uint8_t* bits;                // scratch [n_items][T][513] dB > thresh
@@ -47,9 +50,23 @@ struct NrArgs {
 };
 
 void nr_build_tables(NrTables* t, int sr);
-// noise profile: db_scratch [1 + m/256][513], fmax_scratch [1 + m/256] -> thresh [513]
-hipError_t nr_noise_launch(const float* noise, int64_t m, const NrTables* tables, float* db_scratch,
-                           float* fmax_scratch, float n_std, float* thresh, hipStream_t s);
+// A bank of noise profiles in one launch sequence: profile p = noise + p * stride, its first
+// m_p = clamp(lens[p], 2, m) samples (lens nullable: m), Tn_p = 1 + m_p / 256 frames.  With
+// Tmax = 1 + m / 256: db_scratch [n_profiles][Tmax][513], fmax_scratch [n_profiles][Tmax]
+// -> thresh [n_profiles][513].  Frames past a profile's Tn_p do nothing.
+struct NrNoiseArgs {
+  const float* noise;
+  int64_t stride;
+  const int32_t* lens;
+  int64_t m;
+  int n_profiles;
+  const NrTables* tables;
+  float* db;
+  float* fmaxv;
+  float n_std;
+  float* thresh;
+};
+hipError_t nr_noise_launch(const NrNoiseArgs& a, hipStream_t s);
 hipError_t nr_gate_launch(const NrArgs& a, hipStream_t s);
 // [t_lo, t_hi] covering, for every item, the frames whose window overlaps its signal and the frames
 // within the time-smoothing halo of the kept interior

@@ -22,7 +22,9 @@
 //   nr_ola_kernel      overlap-add of the <= 4 frames covering each kept sample, / window
 //                      sum-square, float32 out
 // The noise profile (per-bin threshold) is computed once per noise clip by nr_noise_db_kernel +
-// nr_noise_thresh_kernel in the reference's float32 arithmetic.
+// nr_noise_thresh_kernel in the reference's float32 arithmetic; a bank of profiles (one per
+// microphone) comes from one launch of each, the profile on the grid's y axis.  The two kernels that
+// read thresholds, nr_stft_kernel and nr_rows_kernel, take the row of the item's profile (thresh_of).
 #include "common.h"
 #include "nr.h"
 
@@ -128,6 +130,14 @@ MMLA_DEV int64_t frame_of_block(const NrArgs& a) {
 
 MMLA_DEV double db_of_power(double p) { return 10.0 * log10(fmax(1e-40, p)); }
 
+// the item's threshold row: profile[it.prof] clamped into the bank (a device-pointer caller's
+// profile array cannot be checked on the host); no profile array: row 0
+MMLA_DEV const float* thresh_of(const NrArgs& a, const NrItem& it) {
+  if (!a.profile) return a.thresh;
+  const int p = min(max(a.profile[it.prof], 0), a.n_profiles - 1);
+  return a.thresh + (int64_t)NB * p;
+}
+
 // frame t of the item's buffer: 1024 centred samples, reflect at the buffer edges, zeros outside
 // the signal; returns whether any sample is nonzero (wave-uniform)
 MMLA_DEV bool load_frame(const NrArgs& a, const NrItem& it, int t, cd* buf, int lane) {
@@ -163,6 +173,7 @@ __global__ void __launch_bounds__(NT) nr_stft_kernel(NrArgs a) {
   const int64_t item = fr / a.t_n;
   const int t = a.t_lo + (int)(fr - item * a.t_n);
   const NrItem it = a.items[item];
+  const float* thresh = thresh_of(a, it);
   const NrTables& tb = *a.tables;
   double2* S = a.S + (item * a.T + t) * NB;
   uint8_t* bits = a.bits + (item * a.T + t) * NB;
@@ -175,7 +186,7 @@ __global__ void __launch_bounds__(NT) nr_stft_kernel(NrArgs a) {
     const double dz = db_of_power(0.0);
     const int64_t f_lo = (int64_t)HOP * (t - NG_T / 2) - NFFT / 2, f_hi = (int64_t)HOP * (t + NG_T / 2) + NFFT / 2;
     if (f_lo < a.keep0 + a.keep_len && f_hi > a.keep0)
-      for (int k = lane; k < NB; k += NT) bits[k] = dz > (double)a.thresh[k];
+      for (int k = lane; k < NB; k += NT) bits[k] = dz > (double)thresh[k];
     const int64_t g_lo = (int64_t)HOP * t - NFFT / 2, g_hi = (int64_t)HOP * t + NFFT / 2;
     if (g_lo < a.keep0 + a.keep_len && g_hi > a.keep0)
       for (int k = lane; k < NB; k += NT) S[k] = double2{0.0, 0.0};
@@ -188,7 +199,7 @@ __global__ void __launch_bounds__(NT) nr_stft_kernel(NrArgs a) {
     for (int i = 0; i < KPL; ++i) {
       const int k = min(lane + NT * i, NB - 1);
       wk[i] = cd{tb.w1024[k][0], tb.w1024[k][1]};
-      th[i] = a.thresh[k];
+      th[i] = thresh[k];
     }
     lds_order();
     fft512(buf, tb.w512, lane);
@@ -237,6 +248,7 @@ __global__ void __launch_bounds__(NT) nr_rows_kernel(NrArgs a) {
   const int64_t item = fr / a.t_n;
   const int t = a.t_lo + (int)(fr - item * a.t_n);
   if (!reaches(a, t, NG_T / 2)) return;
+  const float* thresh = thresh_of(a, a.items[item]);
   const NrTables& tb = *a.tables;
   constexpr int HF = NG_F / 2;
   // the item's max dB (nr_gmax_kernel) -> the top_db floor c; mask = max(dB, c) > th
@@ -251,7 +263,7 @@ __global__ void __launch_bounds__(NT) nr_rows_kernel(NrArgs a) {
   for (int i = 0; i < MPL; ++i) {                   // all loads first
     const int kb = min(max(lane + NT * i - HF, 0), NB - 1);
     bv[i] = br[kb];
-    thv[i] = a.thresh[kb];
+    thv[i] = thresh[kb];
   }
   double g[NG_F];
 #pragma unroll
@@ -412,19 +424,23 @@ __global__ void nr_ola_kernel(NrArgs a) {
 // float32 like the reference: librosa.load gives float32, so stft -> complex64, |X| (hypotf),
 // square, 10 log10(max(1e-40, .)) in float32; the global max / top_db clamp and the per-bin
 // mean / std over frames follow in nr_noise_thresh_kernel.
-__global__ void __launch_bounds__(NT) nr_noise_db_kernel(const float* noise, int64_t m, int Tn,
-                                                         const NrTables* tables, float* db,
-                                                         float* fmaxv) {
+__global__ void __launch_bounds__(NT) nr_noise_db_kernel(NrNoiseArgs a) {
   __shared__ cd buf[512];
   const int lane = threadIdx.x;
-  const int t = blockIdx.x;
-  const NrTables& tb = *tables;
+  const int t = blockIdx.x, p = blockIdx.y;
+  const int64_t m = a.lens ? min(max((int64_t)a.lens[p], (int64_t)2), a.m) : a.m;
+  if (t >= 1 + m / HOP) return;             // past this profile's frames
+  const int64_t Tmax = 1 + a.m / HOP;
+  const float* noise = a.noise + p * a.stride;
+  float* db = a.db + p * Tmax * NB;
+  const NrTables& tb = *a.tables;
   for (int q = lane; q < 512; q += NT) {
     double v[2];
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       int64_t u = (int64_t)HOP * t - NFFT / 2 + 2 * q + e;
       if (u < 0) u = -u;
+      u %= 2 * (m - 1);                     // a clip shorter than the padding reflects more than once
       if (u >= m) u = 2 * (m - 1) - u;
       v[e] = (double)noise[u] * tb.win[2 * q + e];
     }
@@ -447,13 +463,17 @@ __global__ void __launch_bounds__(NT) nr_noise_db_kernel(const float* noise, int
     mx = fmaxf(mx, d);
   }
   mx = wave_max(mx);
-  if (lane == 0) fmaxv[t] = mx;
+  if (lane == 0) a.fmaxv[p * Tmax + t] = mx;
 }
 
-__global__ void nr_noise_thresh_kernel(const float* db, const float* fmaxv, int Tn, float n_std,
-                                       float* thresh) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+__global__ void nr_noise_thresh_kernel(NrNoiseArgs a) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x, p = blockIdx.y;
   if (k >= NB) return;
+  const int64_t m = a.lens ? min(max((int64_t)a.lens[p], (int64_t)2), a.m) : a.m;
+  const int Tn = (int)(1 + m / HOP);
+  const int64_t Tmax = 1 + a.m / HOP;
+  const float* db = a.db + p * Tmax * NB;
+  const float* fmaxv = a.fmaxv + p * Tmax;
   float gm = -INFINITY;
   for (int t = 0; t < Tn; ++t) gm = fmaxf(gm, fmaxv[t]);
   const float c = gm - 80.0f;
@@ -466,7 +486,7 @@ __global__ void nr_noise_thresh_kernel(const float* db, const float* fmaxv, int 
     v += (double)d * (double)d;
   }
   const float sd = sqrtf((float)(v / Tn));
-  thresh[k] = mean + sd * n_std;
+  a.thresh[(int64_t)p * NB + k] = mean + sd * a.n_std;
 }
 
 // ---- host --------------------------------------------------------------------------------------
@@ -502,13 +522,11 @@ void nr_build_tables(NrTables* t, int sr) {
   for (int j = 0; j < NG_T; ++j) t->gt[j] = j < (int)g.size() ? g[j] / sg : 0.0;
 }
 
-hipError_t nr_noise_launch(const float* noise, int64_t m, const NrTables* tables, float* db_scratch,
-                           float* fmax_scratch, float n_std, float* thresh, hipStream_t s) {
-  const int Tn = (int)(1 + m / HOP);
-  hipLaunchKernelGGL(nr_noise_db_kernel, dim3(Tn), dim3(NT), 0, s, noise, m, Tn, tables, db_scratch,
-                     fmax_scratch);
-  hipLaunchKernelGGL(nr_noise_thresh_kernel, dim3((NB + 63) / 64), dim3(64), 0, s, db_scratch,
-                     fmax_scratch, Tn, n_std, thresh);
+hipError_t nr_noise_launch(const NrNoiseArgs& a, hipStream_t s) {
+  if (a.n_profiles <= 0) return hipSuccess;
+  const unsigned Tmax = (unsigned)(1 + a.m / HOP);
+  hipLaunchKernelGGL(nr_noise_db_kernel, dim3(Tmax, (unsigned)a.n_profiles), dim3(NT), 0, s, a);
+  hipLaunchKernelGGL(nr_noise_thresh_kernel, dim3((NB + 63) / 64, (unsigned)a.n_profiles), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 

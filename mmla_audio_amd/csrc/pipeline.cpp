@@ -83,16 +83,20 @@ int stage_pcm(mmla_ctx* c, const T* pcm, int64_t c0, int64_t cnt, int64_t stride
 // frees the context's workspaces, halves the micro-batch (unless the caller fixed it with
 // mmla_set_microbatch) and retries the same clips; the halving holds for the rest of this call only
 // (a transient OOM, e.g. while another context held memory, must not cap every later call).
+// granule: micro-batches are multiples of it (the conditioned calls' items_per_stream: a VAD
+// stream's clips stay in one micro-batch), at least one granule even where the cap is smaller.
 template <class F>
-int for_microbatches(mmla_ctx* c, bool od, int64_t n, F&& body) {
+int for_microbatches(mmla_ctx* c, bool od, int64_t n, F&& body, int64_t granule = 1) {
   int64_t c0 = 0;
-  int64_t mb = microbatch(c, od);   // fixed for the call (unless an allocation fails)
+  auto whole = [&](int64_t m) { return std::max(granule, m / granule * granule); };
+  int64_t mb = whole(microbatch(c, od));   // fixed for the call (unless an allocation fails)
   while (c0 < n) {
     const int64_t cnt = std::min(mb, n - c0);
     const int rc = body(c0, cnt);
-    if (rc == MMLA_E_OOM && (od ? c->od_mb : c->si_mb) == 0 && cnt > kMinMicrobatch) {
+    if (rc == MMLA_E_OOM && (od ? c->od_mb : c->si_mb) == 0 && cnt > kMinMicrobatch &&
+        whole(std::max(kMinMicrobatch, cnt / 2)) < cnt) {
       CHK(ws_release(c));
-      mb = std::max(kMinMicrobatch, cnt / 2);   // this call only: the next call re-reads free memory
+      mb = whole(std::max(kMinMicrobatch, cnt / 2));   // this call only: the next call re-reads free memory
       continue;
     }
     CHK(rc);
@@ -177,7 +181,8 @@ int guarded(mmla_ctx* c, bool dev, bool f32_only, F&& body) {
 enum CallKind { FEATURES_OD, FEATURES_SI, NET_OD, NET_SI };
 
 template <class F>
-int clip_call(mmla_ctx* c, CallKind kind, int64_t n, uint32_t flags, const char* bad_args, F&& body) {
+int clip_call(mmla_ctx* c, CallKind kind, int64_t n, uint32_t flags, const char* bad_args, F&& body,
+              int64_t granule = 1) {
   if (!c) return MMLA_E_INVALID;
   if (bad_args) return fail(c, MMLA_E_INVALID, "%s", bad_args);
   const bool od = kind == FEATURES_OD || kind == NET_OD, net = kind == NET_OD || kind == NET_SI;
@@ -193,11 +198,11 @@ int clip_call(mmla_ctx* c, CallKind kind, int64_t n, uint32_t flags, const char*
   if (net) {
     CHK(for_microbatches(c, od, n, [&](int64_t c0, int64_t cnt) -> int {
       return guarded(c, dev, od ? c->od_f32_only : c->si_f32_only, [&]() -> int { return once(c0, cnt); });
-    }));
+    }, granule));
   } else if (dev) {
     if (n > 0) CHK(once(0, n));
   } else {
-    CHK(for_microbatches(c, od, n, once));
+    CHK(for_microbatches(c, od, n, once, granule));
   }
   return finish(c, dev);
 }
@@ -385,6 +390,200 @@ int od_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t strid
   });
 }
 
+// SI front-end + network of one micro-batch on the device view p of its clips (p.clip_len: the clips'
+// true length without lens), results into probs / argmax / silent at clip c0
+int si_fe_net(mmla_ctx* c, const Pcm& p, int64_t c0, int64_t cnt, bool dev, float* probs,
+              int32_t* argmax, uint8_t* silent) {
+  const int k = c->si.k;
+  void* pf;
+  // the features stay on the device: rows of 40 floats when the 3xFP16 stem reads them
+  const int ldf = c->precision == MMLA_PREC_F16X3 && c->si.stem.wh && c->si.stem.cin_pad > SI_D &&
+                          c->si_pad_feat ? SI_D + 1 : SI_D;
+  CHK(ws_get(c, S_FEAT, cnt * SI_T * ldf * sizeof(float), &pf));
+  uint8_t* pso = nullptr;   // host mode: the caller's 'silent' flags through an output slot
+  if (!dev && silent) CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT2, &pso));
+  void* ps = pso;
+  if (!ps) CHK(ws_get(c, S_SILENT, cnt, &ps));
+  SiFeArgs a{};
+  a.pcm = p.p;
+  a.clip_stride = p.stride;
+  a.lens = p.lens;
+  a.clip_len = p.clip_len;
+  a.tables = c->si_tables;
+  a.feat = static_cast<float*>(pf);
+  a.ldf = ldf;
+  a.silent = static_cast<uint8_t*>(ps);
+  LAUNCH(c, MMLA_STAGE_SI_FE, si_fe_bytes(cnt, a), si_fe_launch(a, cnt, c->stream));
+  float* dp;
+  int32_t* da;
+  CHK(out_ptr(c, probs, c0 * k, cnt * k, dev, S_OUT0, &dp));
+  CHK(out_ptr(c, argmax, c0, cnt, dev, S_OUT1, &da));
+  CHK(run_si_net(c, a.feat, cnt, dp, da, a.silent, ldf));
+  CHK(copy_back(c, probs, c0 * k, dp, cnt * k, dev));
+  CHK(copy_back(c, argmax, c0, da, cnt, dev));
+  if (silent && dev)
+    HIPCHK(c, hipMemcpyAsync(silent + c0, a.silent, cnt, hipMemcpyDeviceToDevice, c->stream));
+  else if (silent)
+    CHK(copy_back(c, silent, c0, pso, cnt, dev));
+  return MMLA_OK;
+}
+
+// ---- the PC loop's pre-conditioning: save_wave_file(noise_reduce=True, silence_remove=...) --------
+
+// The arguments of mmla_condition and the state its micro-batches share.  run() conditions clips
+// [c0, c0 + cnt) into the context's workspace: q [cnt][clip_len] int16 (the rewritten file, zeros
+// behind it) and kept [cnt].  The noise gate is stateless, the detectors are not: run() copies the
+// micro-batch's streams' VadState aside the first time it sees c0 and puts the copy back when it is
+// called for the same c0 again (a re-run by guarded() or, with fewer clips, by for_microbatches), so
+// the decisions and the state left behind do not depend on whether a re-run happened.
+struct Conditioner {
+  const int16_t* pcm;
+  int64_t n, stride;
+  const int32_t* lens;
+  int32_t clip_len;
+  const int32_t* profile;
+  int32_t nr_passes, silence_remove;
+  int64_t ips;
+  int16_t* out_pcm;    // nullable
+  int32_t* kept_len;   // nullable
+  int64_t snap_c0 = -1, snap_streams = 0;
+  const int16_t* q = nullptr;      // device results of the last run()
+  const int32_t* kept = nullptr;
+
+  const char* bad(const mmla_ctx* c, bool dev) const {
+    if (bad_pcm_args(pcm, n, stride, lens, clip_len)) return "bad pcm args";
+    if (clip_len < 1 || clip_len > 600000) return "clip_len must be in [1, 600000] (one gate chunk)";
+    if (n > 1 && stride < clip_len) return "clip_stride < clip_len";
+    if (nr_passes < 0) return "nr_passes < 0";
+    if (nr_passes > 0 && !c->nr_ready) return "nr_passes > 0: mmla_nr_set_noise(_bank) must be called first";
+    if (ips < 1 || n % ips) return "n_clips is not a multiple of items_per_stream";
+    if (silence_remove && (!c->vad_state || c->vad_streams != n / ips))
+      return "silence_remove: mmla_vad_reset must have created n_clips / items_per_stream streams";
+    // device-pointer profile indices cannot be seen here: the kernels clamp them into the bank
+    if (profile && !dev && nr_passes > 0)
+      for (int64_t i = 0; i < n; ++i)
+        if (profile[i] < 0 || profile[i] >= c->nr_profiles) return "profile index outside the bank";
+    return nullptr;
+  }
+  bool off() const { return nr_passes == 0 && !silence_remove; }
+
+  int run(mmla_ctx* c, int64_t c0, int64_t cnt, bool dev) {
+    const int D = clip_len;
+    Pcm p;
+    CHK(stage_pcm(c, pcm, c0, cnt, n > 1 ? stride : (int64_t)D, lens, D, D, dev, &p));
+    void *py0 = nullptr, *py1 = nullptr, *pq = nullptr, *pk = nullptr;
+    CHK(ws_get(c, S_COND_Q, (size_t)cnt * D * sizeof(int16_t), &pq));
+    CHK(ws_get(c, S_COND_KEPT, (size_t)cnt * sizeof(int32_t), &pk));
+    int16_t* dq = static_cast<int16_t*>(pq);
+    int32_t* dk = static_cast<int32_t*>(pk);
+    // the input of the silence removal (it cannot rewrite in place): the first float buffer, as int16
+    int16_t* src = silence_remove ? nullptr : dq;
+    if (silence_remove || nr_passes > 0) {
+      CHK(ws_get(c, S_GATE_Y0, (size_t)cnt * D * sizeof(float), &py0));
+      if (silence_remove) src = static_cast<int16_t*>(py0);
+    }
+    if (nr_passes > 0) {
+      CHK(ws_get(c, S_GATE_Y1, (size_t)cnt * D * sizeof(float), &py1));
+      float *y0 = static_cast<float*>(py0), *y1 = static_cast<float*>(py1);
+      const int32_t* dprof;
+      CHK(in_ptr(c, profile ? profile + c0 : nullptr, (size_t)cnt, dev, S_NR_PROF, &dprof));
+      LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * 6,
+             pcm_f32_launch(p.p, p.stride, p.lens, D, cnt, y0, c->stream));
+      for (int k = 0; k < nr_passes; ++k) {
+        // a pass re-uses the gate's item table and scratch: the one before it has drained
+        if (k) HIPCHK(c, hipStreamSynchronize(c->stream));
+        CHK(nr_reduce_dev(c, y0, cnt, D, D, y1, dprof));
+        const bool last = k == nr_passes - 1;
+        LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * (last ? 6 : 8),
+               requant_launch(y1, p.lens, D, cnt, last ? nullptr : y0, last ? src : nullptr, c->stream));
+      }
+    } else {
+      LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * 4,
+             pcm_i16_launch(p.p, p.stride, p.lens, D, cnt, src, c->stream));
+    }
+    const int32_t* vad_lens = nullptr;
+    if (silence_remove) {
+      const int64_t s0 = c0 / ips, ns = cnt / ips;
+      VadState* snap = c->vad_state + c->vad_streams;
+      if (c0 == snap_c0) {
+        HIPCHK(c, hipMemcpyAsync(c->vad_state + s0, snap + s0, snap_streams * sizeof(VadState),
+                                 hipMemcpyDeviceToDevice, c->stream));
+      } else {
+        HIPCHK(c, hipMemcpyAsync(snap + s0, c->vad_state + s0, ns * sizeof(VadState),
+                                 hipMemcpyDeviceToDevice, c->stream));
+        snap_c0 = c0;
+        snap_streams = ns;
+      }
+      void *psp = nullptr, *pvl = nullptr;
+      VadArgs v{};
+      v.pcm = src;
+      v.stride = D;
+      v.lens = p.lens;
+      v.clip_len = D;
+      v.n_items = cnt;
+      v.items_per_stream = ips;
+      v.state = c->vad_state + s0;
+      v.max_frames = std::max(1, vad_frames(D));
+      CHK(ws_get(c, S_VAD_SPEECH, (size_t)cnt * v.max_frames, &psp));
+      CHK(ws_get(c, S_VAD_LENS, (size_t)cnt * sizeof(int32_t), &pvl));
+      v.speech = static_cast<uint8_t*>(psp);
+      v.out = dq;
+      v.out_lens = static_cast<int32_t*>(pvl);
+      LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D, vad_speech_launch(v, c->stream));
+      LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D, vad_collect_launch(v, c->stream));
+      vad_lens = v.out_lens;
+    }
+    LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * 2,
+           cond_finish_launch(dq, vad_lens, p.lens, D, cnt, dk, c->stream));
+    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (out_pcm)
+      HIPCHK(c, hipMemcpyAsync(out_pcm + c0 * D, dq, (size_t)cnt * D * sizeof(int16_t), kind, c->stream));
+    if (kept_len)
+      HIPCHK(c, hipMemcpyAsync(kept_len + c0, dk, (size_t)cnt * sizeof(int32_t), kind, c->stream));
+    q = dq;
+    kept = dk;
+    return MMLA_OK;
+  }
+};
+
+// mmla_condition: FEATURES_* micro-batching (host mode), one pass over the whole batch (device mode)
+int condition_call(mmla_ctx* c, Conditioner& cd, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  return clip_call(c, FEATURES_OD, cd.n, flags, cd.bad(c, flags & MMLA_DEVICE_PTR),
+                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+    return cd.run(c, c0, cnt, dev);
+  }, std::max<int64_t>(cd.ips, 1));
+}
+
+// OD front-end + network on a micro-batch's conditioned clips
+int od_fe_net(mmla_ctx* c, const Conditioner& cd, int64_t c0, int64_t cnt, bool dev, float* probs,
+              int32_t* argmax, uint8_t* silent) {
+  void* pimg = nullptr;
+  CHK(ws_get(c, S_IMG, cnt * OD_IMG, &pimg));
+  OdFeArgs a{};
+  a.pcm = cd.q;
+  a.clip_stride = cd.clip_len;
+  a.lens = cd.kept;
+  a.clip_len = cd.clip_len;
+  a.tables = c->od_tables;
+  a.img = static_cast<uint8_t*>(pimg);
+  LAUNCH(c, MMLA_STAGE_OD_FE, od_fe_bytes(cnt, a), od_fe_launch(a, cnt, c->stream));
+  float* dp;
+  int32_t* da;
+  uint8_t* ds;
+  CHK(out_ptr(c, probs, c0 * 2, cnt * 2, dev, S_OUT0, &dp));
+  CHK(out_ptr(c, argmax, c0, cnt, dev, S_OUT1, &da));
+  CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT2, &ds));
+  OdGate g;
+  g.lens = cd.kept;   // silent = kept_len < 4000
+  g.clip_len = 0;
+  g.silent = ds;
+  CHK(run_od_net(c, a.img, nullptr, cnt, dp, da, g));
+  CHK(copy_back(c, probs, c0 * 2, dp, cnt * 2, dev));
+  CHK(copy_back(c, argmax, c0, da, cnt, dev));
+  return copy_back(c, silent, c0, ds, cnt, dev);
+}
+
 }  // namespace
 
 extern "C" {
@@ -520,41 +719,60 @@ int mmla_si_pipeline(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
                      uint8_t* silent, uint32_t flags) {
   return clip_call(c, NET_SI, n, flags, bad_pcm_args(pcm, n, stride, lens, clip_len) ? "bad pcm args" : nullptr,
                    [&](int64_t c0, int64_t cnt, bool dev) -> int {
-    const int k = c->si.k;
     Pcm p;
     CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, SI_NEED_SAMPLES, dev, &p));
-    void* pf;
-    // the features stay on the device: rows of 40 floats when the 3xFP16 stem reads them
-    const int ldf = c->precision == MMLA_PREC_F16X3 && c->si.stem.wh && c->si.stem.cin_pad > SI_D &&
-                            c->si_pad_feat ? SI_D + 1 : SI_D;
-    CHK(ws_get(c, S_FEAT, cnt * SI_T * ldf * sizeof(float), &pf));
-    uint8_t* pso = nullptr;   // host mode: the caller's 'silent' flags through an output slot
-    if (!dev && silent) CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT2, &pso));
-    void* ps = pso;
-    if (!ps) CHK(ws_get(c, S_SILENT, cnt, &ps));
-    SiFeArgs a{};
-    a.pcm = p.p;
-    a.clip_stride = p.stride;
-    a.lens = p.lens;
-    a.clip_len = lens ? 0 : clip_len;
-    a.tables = c->si_tables;
-    a.feat = static_cast<float*>(pf);
-    a.ldf = ldf;
-    a.silent = static_cast<uint8_t*>(ps);
-    LAUNCH(c, MMLA_STAGE_SI_FE, si_fe_bytes(cnt, a), si_fe_launch(a, cnt, c->stream));
-    float* dp;
-    int32_t* da;
-    CHK(out_ptr(c, probs, c0 * k, cnt * k, dev, S_OUT0, &dp));
-    CHK(out_ptr(c, argmax, c0, cnt, dev, S_OUT1, &da));
-    CHK(run_si_net(c, a.feat, cnt, dp, da, a.silent, ldf));
-    CHK(copy_back(c, probs, c0 * k, dp, cnt * k, dev));
-    CHK(copy_back(c, argmax, c0, da, cnt, dev));
-    if (silent && dev)
-      HIPCHK(c, hipMemcpyAsync(silent + c0, a.silent, cnt, hipMemcpyDeviceToDevice, c->stream));
-    else if (silent)
-      CHK(copy_back(c, silent, c0, pso, cnt, dev));
-    return MMLA_OK;
+    p.clip_len = lens ? 0 : clip_len;   // the true length decides T even if fewer samples are staged
+    return si_fe_net(c, p, c0, cnt, dev, probs, argmax, silent);
   });
+}
+
+int mmla_condition(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride, const int32_t* lens,
+                   int32_t clip_len, const int32_t* profile, int32_t nr_passes, int32_t silence_remove,
+                   int64_t items_per_stream, int16_t* out_pcm, int32_t* kept_len, uint32_t flags) {
+  Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, items_per_stream,
+                 out_pcm, kept_len};
+  return condition_call(c, cd, flags);
+}
+
+int mmla_od_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
+                                 const int32_t* lens, int32_t clip_len, const int32_t* profile,
+                                 int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
+                                 int16_t* out_pcm, int32_t* kept_len, float* probs, int32_t* argmax,
+                                 uint8_t* silent, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, items_per_stream,
+                 out_pcm, kept_len};
+  const char* bad = cd.bad(c, flags & MMLA_DEVICE_PTR);
+  if (!bad && cd.off()) {   // nothing to condition: mmla_od_pipeline itself, then the copies asked for
+    CHK(od_pipeline_common(c, pcm, n, stride, lens, clip_len, false, 0, 0.0f, probs, argmax, silent,
+                           nullptr, flags));
+    return out_pcm || kept_len ? condition_call(c, cd, flags) : MMLA_OK;
+  }
+  return clip_call(c, NET_OD, n, flags, bad, [&](int64_t c0, int64_t cnt, bool dev) -> int {
+    CHK(cd.run(c, c0, cnt, dev));
+    return od_fe_net(c, cd, c0, cnt, dev, probs, argmax, silent);
+  }, std::max<int64_t>(items_per_stream, 1));
+}
+
+int mmla_si_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
+                                 const int32_t* lens, int32_t clip_len, const int32_t* profile,
+                                 int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
+                                 int16_t* out_pcm, int32_t* kept_len, float* probs, int32_t* argmax,
+                                 uint8_t* silent, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, items_per_stream,
+                 out_pcm, kept_len};
+  const char* bad = cd.bad(c, flags & MMLA_DEVICE_PTR);
+  if (!bad && cd.off()) {   // nothing to condition: mmla_si_pipeline itself, then the copies asked for
+    CHK(mmla_si_pipeline(c, pcm, n, stride, lens, clip_len, probs, argmax, silent, flags));
+    return out_pcm || kept_len ? condition_call(c, cd, flags) : MMLA_OK;
+  }
+  return clip_call(c, NET_SI, n, flags, bad, [&](int64_t c0, int64_t cnt, bool dev) -> int {
+    CHK(cd.run(c, c0, cnt, dev));
+    // the conditioned clips with lens = kept_len (a row holds clip_len samples, zeros behind kept_len)
+    const Pcm p{cd.q, cd.clip_len, cd.kept, 0};
+    return si_fe_net(c, p, c0, cnt, dev, probs, argmax, silent);
+  }, std::max<int64_t>(items_per_stream, 1));
 }
 
 int mmla_debug_od_trace(mmla_ctx* c, const float* x, int64_t n, int stage, float* out,

@@ -50,3 +50,11 @@ hipError_t pcm_f32_launch(const int16_t* pcm, int64_t stride, const int32_t* len
                           float* y, hipStream_t s);
 hipError_t requant_launch(const float* y, const int32_t* lens, int len, int64_t n, float* yf,
                           int16_t* yq, hipStream_t s);
+// mmla_condition (n clips of `len` samples, lens as above):
+// pcm_i16: the clips at `stride` copied into q [n][len], zeros from each clip's valid length on;
+// cond_finish: kept[c] = vad_lens[c] (silence removed: q's samples from there on are zeroed) or,
+// with vad_lens null, the clip's valid length.
+hipError_t pcm_i16_launch(const int16_t* pcm, int64_t stride, const int32_t* lens, int len, int64_t n,
+                          int16_t* q, hipStream_t s);
+hipError_t cond_finish_launch(int16_t* q, const int32_t* vad_lens, const int32_t* lens, int len,
+                              int64_t n, int32_t* kept, hipStream_t s);

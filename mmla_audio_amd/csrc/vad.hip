@@ -496,6 +496,35 @@ __global__ void requant_kernel(const float* __restrict__ y, const int32_t* __res
   else yf[i] = (float)q * (1.0f / 32768.0f);
 }
 
+// mmla_condition without a noise gate: each clip's first `len` int16 samples into q [n][len], zeros
+// from the clip's valid length on
+__global__ void pcm_i16_kernel(const int16_t* __restrict__ pcm, int64_t stride,
+                               const int32_t* __restrict__ lens, int len, int64_t n,
+                               int16_t* __restrict__ q) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * len) return;
+  const int64_t clip = i / len;
+  const int j = (int)(i - clip * len);
+  const int valid = lens ? min(max(lens[clip], 0), len) : len;
+  q[i] = j < valid ? pcm[clip * stride + j] : (int16_t)0;
+}
+
+// the end of mmla_condition: kept[c] = the samples the rewritten file holds -- vad_lens[c] after
+// silence removal (the collector leaves q's samples behind them untouched: zero them), else the
+// clip's valid length (q is zero past it already)
+__global__ void cond_finish_kernel(int16_t* __restrict__ q, const int32_t* __restrict__ vad_lens,
+                                   const int32_t* __restrict__ lens, int len, int64_t n,
+                                   int32_t* __restrict__ kept) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * len) return;
+  const int64_t clip = i / len;
+  const int j = (int)(i - clip * len);
+  const int valid = lens ? min(max(lens[clip], 0), len) : len;
+  const int k = vad_lens ? min(max(vad_lens[clip], 0), len) : valid;
+  if (vad_lens && j >= k) q[i] = 0;
+  if (j == 0) kept[clip] = k;
+}
+
 }  // namespace
 
 bool vad_init_state(VadState* s, int mode) {
@@ -554,5 +583,21 @@ hipError_t requant_launch(const float* y, const int32_t* lens, int len, int64_t 
   if (n <= 0 || len <= 0) return hipSuccess;
   hipLaunchKernelGGL(requant_kernel, dim3((unsigned)((n * len + 255) / 256)), dim3(256), 0, s, y, lens,
                      len, n, yf, yq);
+  return hipGetLastError();
+}
+
+hipError_t pcm_i16_launch(const int16_t* pcm, int64_t stride, const int32_t* lens, int len, int64_t n,
+                          int16_t* q, hipStream_t s) {
+  if (n <= 0 || len <= 0) return hipSuccess;
+  hipLaunchKernelGGL(pcm_i16_kernel, dim3((unsigned)((n * len + 255) / 256)), dim3(256), 0, s, pcm,
+                     stride, lens, len, n, q);
+  return hipGetLastError();
+}
+
+hipError_t cond_finish_launch(int16_t* q, const int32_t* vad_lens, const int32_t* lens, int len,
+                              int64_t n, int32_t* kept, hipStream_t s) {
+  if (n <= 0 || len <= 0) return hipSuccess;
+  hipLaunchKernelGGL(cond_finish_kernel, dim3((unsigned)((n * len + 255) / 256)), dim3(256), 0, s, q,
+                     vad_lens, lens, len, n, kept);
   return hipGetLastError();
 }

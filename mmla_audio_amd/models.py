@@ -57,6 +57,33 @@ class _Model:
                                   self.n_classes, self.head)
             setattr(self.ctx, f'_owner_{self.kind}', self)
 
+    def _predict_conditioned(self, call, pcm, noise, mic, lens, passes, silence_remove,
+                             items_per_stream, vad_mode, reset_vad):
+        """the shared body of predict_wavs_conditioned: the bank, the detectors, the fused call"""
+        from . import noisereduce
+        self._ensure_loaded()
+        n = len(pcm) if isinstance(pcm, (list, tuple)) else (1 if np.ndim(pcm) == 1 else len(pcm))
+        ips = int(items_per_stream)
+        if ips < 1 or n % ips:
+            raise ValueError(f'{n} clips are not whole streams of {ips}')
+        one = isinstance(noise, np.ndarray) and noise.ndim == 1
+        noises = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in ([noise] if one else noise)]
+        if mic is None:     # the clip's stream is its microphone
+            mic = np.zeros(n, np.int32) if len(noises) == 1 else np.arange(n, dtype=np.int32) // ips
+        mic = np.ascontiguousarray(mic, dtype=np.int32)
+        if passes > 0:
+            if mic.shape != (n,) or (n and (mic.min() < 0 or mic.max() >= len(noises))):
+                raise ValueError(f'mic must hold one index into the {len(noises)} noise clips per clip')
+            noisereduce._set_noise_bank(self.ctx, noises, 16000)
+        if silence_remove:
+            # the reference's module-level webrtcvad.Vad(3): created once, its state carried from
+            # clip to clip; one per stream here
+            tag = ('conditioned', n // ips, int(vad_mode))
+            if reset_vad or getattr(self.ctx, 'vad_owner', None) != tag:
+                self.ctx.vad_reset(n // ips, vad_mode)
+                self.ctx.vad_owner = tag
+        return call(pcm, lens, mic, passes, silence_remove, ips)
+
 
 class OverlapDetectionModel(_Model):
     """OD-NET (ResLSTM, overlap_detector_temp.py:280-303): predict(float32 [N,128,151,3]) -> [N,2]."""
@@ -91,6 +118,21 @@ class OverlapDetectionModel(_Model):
             noisereduce._set_noise(self.ctx, yn, 16000)
         return self.ctx.od_pipeline_gated(pcm, lens, passes, threshold)
 
+    def predict_wavs_conditioned(self, pcm, noise, mic=None, lens=None, passes=1, silence_remove=True,
+                                 items_per_stream=1, vad_mode=3, reset_vad=False):
+        """predict_wavs behind the PC loop's save_wave_file(noise_reduce=True, silence_remove=True)
+        (record_on_pc.py:141-154,200-226) for a room of microphones: clip c is denoised `passes` times
+        against the ambient-noise clip of its microphone (`noise`: one float32 clip, or a list with one
+        per microphone; `mic[c]` picks the clip's, default its stream), its silence is removed by its
+        stream's webrtcvad.Vad(vad_mode) (stream s owns clips [s * items_per_stream, (s + 1) *
+        items_per_stream); the detectors are created on the first call or when the stream count or
+        the mode changes, and keep their state across calls otherwise; reset_vad=True starts afresh),
+        and a clip with fewer than 4000 samples left is 'silent' -> (probs [N,2], argmax [N] (-1 =
+        'silent'), silent [N], kept_len [N]).  The bank of profiles is rebuilt only when a noise clip
+        changes."""
+        return self._predict_conditioned(self.ctx.od_pipeline_conditioned, pcm, noise, mic, lens, passes,
+                                         silence_remove, items_per_stream, vad_mode, reset_vad)
+
 
 class SpeakerIdModel(_Model):
     """SI-NET (res_model + head, speaker_identification.py:193-218,401-410): predict([N,256,39])."""
@@ -111,6 +153,14 @@ class SpeakerIdModel(_Model):
         """Fused WAV -> speaker: -> (probs [N,K], argmax [N] (-1 = 'silent'), silent [N])."""
         self._ensure_loaded()
         return self.ctx.si_pipeline(pcm, lens)
+
+    def predict_wavs_conditioned(self, pcm, noise, mic=None, lens=None, passes=1, silence_remove=True,
+                                 items_per_stream=1, vad_mode=3, reset_vad=False):
+        """predict_wavs behind save_wave_file(noise_reduce=True, silence_remove=True) (SI
+        record_on_pc.py:117-134,178-205, record_on_pi.py:101-127,228-240); arguments and the returned
+        (probs [N,K], argmax, silent, kept_len) as OverlapDetectionModel.predict_wavs_conditioned."""
+        return self._predict_conditioned(self.ctx.si_pipeline_conditioned, pcm, noise, mic, lens, passes,
+                                         silence_remove, items_per_stream, vad_mode, reset_vad)
 
 
 def load_model(path, kind=None, n_classes=None, head=None, seed=0, device=None,

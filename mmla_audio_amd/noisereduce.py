@@ -20,6 +20,14 @@ def _set_noise(ctx, y_noise, sr):
         ctx._nr_key = key
 
 
+def _set_noise_bank(ctx, noises, sr):
+    """(Re)compute the bank of noise profiles, one per clip of `noises`, when a clip changes."""
+    key = ('bank', tuple((hash(y.tobytes()), y.size) for y in noises), int(sr))
+    if ctx.__dict__.get('_nr_key') != key:
+        ctx.nr_set_noise_bank(noises, sr)
+        ctx._nr_key = key
+
+
 def reduce_noise(y, sr, stationary=False, y_noise=None, prop_decrease=1.0, time_constant_s=2.0,
                  freq_mask_smooth_hz=500, time_mask_smooth_ms=50, thresh_n_mult_nonstationary=2,
                  sigmoid_slope_nonstationary=10, n_std_thresh_stationary=1.5, tmp_folder=None,
