@@ -393,6 +393,30 @@ int mmla_si_pipeline_conditioned(mmla_ctx* ctx, const int16_t* pcm, int64_t n_cl
                                  uint8_t* silent, uint32_t flags);
 
 /*
+ * Both detectors for a room: mmla_od_pipeline_conditioned and mmla_si_pipeline_conditioned on the same
+ * clips from ONE conditioning, so the gate and the silence removal run once and every stream's detector
+ * advances once per clip (two single calls on one context would advance it twice over the same audio).
+ * Arguments, limits and MMLA_E_INVALID cases are mmla_condition's; MMLA_E_NOWEIGHTS names the model that
+ * is not loaded (both must be, in this context).  Per micro-batch (whole streams, OD's micro-batch cap):
+ * the conditioning, then the OD front-end + network, then the SI front-end + network on the same
+ * conditioned clips with lens = kept_len.  silent[c] = kept_len[c] < 4000 is one array (both loops' rule);
+ * od_argmax and si_argmax are -1 there.  od_probs [n_clips, 2], si_probs [n_clips, K].
+ * Every output equals, byte for byte, what the two single calls return, each on a fresh context of its
+ * own with the same bank, mmla_vad_reset and arguments, and the detector state left behind is that of one
+ * of them: under host and device pointers, for any micro-batch size, and when a micro-batch is re-run
+ * (a range-guard or split-BiLSTM re-run repeats that network alone on the conditioning already made; an
+ * allocation failure repeats the micro-batch with fewer clips from the detectors' saved state).
+ * nr_passes = 0 with silence_remove = 0 is mmla_od_pipeline plus mmla_si_pipeline, bit for bit.
+ * Stream synchronisation under MMLA_DEVICE_PTR: as mmla_condition.
+ */
+int mmla_room_pipeline_conditioned(mmla_ctx* ctx, const int16_t* pcm, int64_t n_clips, int64_t clip_stride,
+                                   const int32_t* lens, int32_t clip_len, const int32_t* profile,
+                                   int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
+                                   int16_t* out_pcm, int32_t* kept_len, float* od_probs,
+                                   int32_t* od_argmax, float* si_probs, int32_t* si_argmax,
+                                   uint8_t* silent, uint32_t flags);
+
+/*
  * Rate conversion of the offline pre-conditioning (resample.hip).
  * mmla_ratecv: pydub AudioSegment.set_frame_rate(outrate) on 16-bit PCM, i.e.
  *   audioop.ratecv(data, 2, nch, inrate, outrate, None) (OverlapDetection/scripts/
@@ -445,6 +469,10 @@ int mmla_debug_ws_slot(mmla_ctx* ctx, int slot, void** ptr, size_t* bytes);
  * timed out waiting for the others.  Env MMLA_DEBUG_LSTM_SPIN=<polls> at mmla_create bounds that
  * wait (tests force the timeout path with 1). */
 int mmla_debug_counters(mmla_ctx* ctx, int64_t* f32_reruns, int64_t* lstm_split_reruns);
+/* Debug (tests, tools): *wave = 1 when a detector call of this context over n_streams streams runs the
+ * one-stream-per-wave kernel, 0 for the one-thread-per-stream kernel (the same decisions and states bit
+ * for bit).  Env at mmla_create: MMLA_NO_VADW=1 per thread everywhere, MMLA_VADW=1 per wave everywhere. */
+int mmla_debug_vad_path(mmla_ctx* ctx, int64_t n_streams, int32_t* wave);
 /* ms[MMLA_NSTAGES], launches[MMLA_NSTAGES], work[MMLA_NSTAGES] (each nullable); reset != 0 clears */
 int mmla_profile_read(mmla_ctx* ctx, double* ms, int64_t* launches, double* work, int reset);
 

@@ -43,6 +43,9 @@ SIGNATURES = {
                                      _P, _P, _P, _U32],
     'mmla_si_pipeline_conditioned': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P,
                                      _P, _P, _P, _U32],
+    'mmla_room_pipeline_conditioned': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P,
+                                       _P, _P, _P, _P, _P, _U32],
+    'mmla_debug_vad_path': [_P, _I64, ctypes.POINTER(_I32)],
     'mmla_abi_version': [],
     'mmla_crc32c': [_P, _I64, ctypes.POINTER(_U32)],
     'mmla_png_unfilter': [_P, _I64, _I64, _I32, _P],
@@ -639,6 +642,35 @@ class Context:
                                  pcm, lens, profile, passes, silence_remove, items_per_stream,
                                  self.si_classes or 0, return_pcm)
 
+    def room_pipeline_conditioned(self, pcm, lens=None, profile=None, passes=1, silence_remove=True,
+                                  items_per_stream=1, return_pcm=False):
+        """condition() once in front of od_pipeline and si_pipeline -> (od_probs [n,2], od_argmax [n],
+        si_probs [n,K], si_argmax [n], silent [n] bool, kept_len [n]); return_pcm adds the conditioned
+        clips.  Both argmax are -1 where fewer than 4000 samples were kept."""
+        a, ln, L = self._pcm(pcm, lens)
+        n = a.shape[0]
+        pr = self._profile(profile, n)
+        out = np.empty_like(a) if return_pcm else None
+        kept = np.empty(n, np.int32)
+        od_probs = np.empty((n, 2), np.float32)
+        si_probs = np.empty((n, self.si_classes or 0), np.float32)
+        od_am = np.empty(n, np.int32)
+        si_am = np.empty(n, np.int32)
+        silent = np.empty(n, np.uint8)
+        self._check(self.lib.mmla_room_pipeline_conditioned(
+            self.h, _ptr(a), n, a.shape[1], _ptr(ln), L, _ptr(pr), int(passes),
+            int(bool(silence_remove)), int(items_per_stream), _ptr(out), _ptr(kept), _ptr(od_probs),
+            _ptr(od_am), _ptr(si_probs), _ptr(si_am), _ptr(silent), 0), 'mmla_room_pipeline_conditioned')
+        res = (od_probs, od_am, si_probs, si_am, silent.astype(bool), kept)
+        return res + (out,) if return_pcm else res
+
+    def debug_vad_path(self, n_streams):
+        """True when a detector call over n_streams streams runs the one-stream-per-wave kernel"""
+        wave = _I32()
+        self._check(self.lib.mmla_debug_vad_path(self.h, int(n_streams), ctypes.byref(wave)),
+                    'mmla_debug_vad_path')
+        return bool(wave.value)
+
     def ssim_u8(self, a, b):
         """Mean SSIM (scikit-image defaults, multichannel) of uint8 image pairs a, b [n,h,w,c] (or one
         pair [h,w,c]) -> float32 [n] (or a scalar)."""
@@ -751,6 +783,16 @@ class Context:
             int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
             probs or None, argmax or None, silent or None, MMLA_DEVICE_PTR),
             'mmla_si_pipeline_conditioned(dev)')
+
+    def room_pipeline_conditioned_dev(self, pcm, n, stride, clip_len, passes=1, silence_remove=True,
+                                      items_per_stream=1, od_probs=0, od_argmax=0, si_probs=0,
+                                      si_argmax=0, silent=0, out_pcm=0, kept_len=0, lens=0, profile=0):
+        """synchronises the context stream internally when passes > 0 (see mmla.h)"""
+        self._check(self.lib.mmla_room_pipeline_conditioned(
+            self.h, pcm, n, stride, lens or None, clip_len, profile or None, int(passes),
+            int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
+            od_probs or None, od_argmax or None, si_probs or None, si_argmax or None, silent or None,
+            MMLA_DEVICE_PTR), 'mmla_room_pipeline_conditioned(dev)')
 
     def ssim_u8_dev(self, a, b, n, h, w, c, out):
         self._check(self.lib.mmla_ssim_u8(self.h, a, b, n, h, w, c, out, MMLA_DEVICE_PTR),

@@ -346,7 +346,7 @@ static int vad_run(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride, c
       return fail(c, MMLA_E_INVALID, "%lld items are not %lld streams x items_per_stream %lld",
                   (long long)n, (long long)c->vad_streams, (long long)items_per_stream);
     // the rewrite keeps a frame's bytes or drops it: outputs are never longer than inputs
-    LAUNCH(c, MMLA_STAGE_GLUE, (double)n * width, vad_speech_launch(a, c->stream));
+    LAUNCH(c, MMLA_STAGE_GLUE, (double)n * width, vad_speech_launch(a, vad_use_wave(c, c->vad_streams), c->stream));
   }
   LAUNCH(c, MMLA_STAGE_GLUE, (double)n * width, vad_collect_launch(a, c->stream));
   CHK(copy_back(c, out, 0, a.out, samples, dev));
@@ -363,6 +363,13 @@ int mmla_vad_remove_silence(mmla_ctx* c, const int16_t* pcm, int64_t n_items, in
   if (!c) return MMLA_E_INVALID;
   return vad_run(c, pcm, n_items, stride, lens, clip_len, items_per_stream, nullptr, speech,
                  max_frames, out, out_lens, flags);
+}
+
+int mmla_debug_vad_path(mmla_ctx* c, int64_t n_streams, int32_t* wave) {
+  if (!c || !wave) return MMLA_E_INVALID;
+  if (n_streams < 1) return fail(c, MMLA_E_INVALID, "n_streams must be >= 1");
+  *wave = vad_use_wave(c, n_streams) ? 1 : 0;
+  return MMLA_OK;
 }
 
 int mmla_vad_collect(mmla_ctx* c, const int16_t* pcm, int64_t n_items, int64_t stride,

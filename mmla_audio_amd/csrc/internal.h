@@ -143,6 +143,11 @@ struct mmla_ctx {
   // ... with two strips per workgroup on one weight stream where that measured faster (odu.hip
   // odu_two_strips); env MMLA_NO_ODW=1 at create: one strip for every block (A/B, bit-identical)
   bool odw = true;
+  // the speech detector with one stream per wave where that measured faster (vad.hip
+  // vad_speech_wave_kernel, vad_wave_streams); env MMLA_NO_VADW=1 at create: one thread per stream
+  // everywhere (A/B, bit-identical); env MMLA_VADW=1: one stream per wave everywhere
+  bool vadw = true;
+  int vadw_all = 0;
   // OD blocks 1-3 as rolling column strips (rbs.hip); env MMLA_RB_TILE=1 at create: the 16 x 16 tile
   // kernels of resblk.hip instead
   bool rbs = true;
@@ -228,7 +233,8 @@ enum Slot {
   S_VAD_SPEECH, S_VAD_OUT, S_VAD_LENS, S_RS_TR, S_RS_WIN, S_LSTM,
   S_TRAIN,  // mmla_si_head_fit: every host-pointer operand, carved from one slot
   S_IMG2, S_GATE_Y0, S_GATE_Y1, S_SSIM,   // mmla_od_pipeline_gated / mmla_ssim_u8
-  S_NR_PROF, S_COND_Q, S_COND_KEPT        // profile indices of the gate; mmla_condition's outputs
+  S_NR_PROF, S_COND_Q, S_COND_KEPT,       // profile indices of the gate; mmla_condition's outputs
+  S_ROOM_P, S_ROOM_A                      // mmla_room_pipeline_conditioned: the SI outputs' staging
 };
 
 int ws_get(mmla_ctx* c, int slot, size_t bytes, void** out);
@@ -237,6 +243,10 @@ int64_t microbatch(mmla_ctx* c, bool od);
 // the end of every entry point that launched: the last error, host-mode synchronisation, guard bands
 int finish(mmla_ctx* c, bool dev);
 void free_allocs(std::vector<void*>& al);   // weights.cpp
+// which detector kernel a call with n_streams streams runs (mmla_debug_vad_path reports it)
+inline bool vad_use_wave(const mmla_ctx* c, int64_t n_streams) {
+  return c->vadw && (c->vadw_all > 0 || vad_wave_streams(n_streams));
+}
 // the body of mmla_nr_reduce on device pointers (capi.cpp): y [n_signals, stride] -> out [n_signals,
 // len].  At most 512 items per launch with a stream synchronisation between launches.  profile
 // (device, nullable = all 0): signal i is gated with noise profile profile[i] of the bank.

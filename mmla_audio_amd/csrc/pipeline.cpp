@@ -391,9 +391,10 @@ int od_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t strid
 }
 
 // SI front-end + network of one micro-batch on the device view p of its clips (p.clip_len: the clips'
-// true length without lens), results into probs / argmax / silent at clip c0
+// true length without lens), results into probs / argmax / silent at clip c0 (host mode: staged in
+// the output slots slot_p / slot_a)
 int si_fe_net(mmla_ctx* c, const Pcm& p, int64_t c0, int64_t cnt, bool dev, float* probs,
-              int32_t* argmax, uint8_t* silent) {
+              int32_t* argmax, uint8_t* silent, int slot_p = S_OUT0, int slot_a = S_OUT1) {
   const int k = c->si.k;
   void* pf;
   // the features stay on the device: rows of 40 floats when the 3xFP16 stem reads them
@@ -416,8 +417,8 @@ int si_fe_net(mmla_ctx* c, const Pcm& p, int64_t c0, int64_t cnt, bool dev, floa
   LAUNCH(c, MMLA_STAGE_SI_FE, si_fe_bytes(cnt, a), si_fe_launch(a, cnt, c->stream));
   float* dp;
   int32_t* da;
-  CHK(out_ptr(c, probs, c0 * k, cnt * k, dev, S_OUT0, &dp));
-  CHK(out_ptr(c, argmax, c0, cnt, dev, S_OUT1, &da));
+  CHK(out_ptr(c, probs, c0 * k, cnt * k, dev, slot_p, &dp));
+  CHK(out_ptr(c, argmax, c0, cnt, dev, slot_a, &da));
   CHK(run_si_net(c, a.feat, cnt, dp, da, a.silent, ldf));
   CHK(copy_back(c, probs, c0 * k, dp, cnt * k, dev));
   CHK(copy_back(c, argmax, c0, da, cnt, dev));
@@ -529,7 +530,7 @@ struct Conditioner {
       v.speech = static_cast<uint8_t*>(psp);
       v.out = dq;
       v.out_lens = static_cast<int32_t*>(pvl);
-      LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D, vad_speech_launch(v, c->stream));
+      LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D, vad_speech_launch(v, vad_use_wave(c, ns), c->stream));
       LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D, vad_collect_launch(v, c->stream));
       vad_lens = v.out_lens;
     }
@@ -773,6 +774,47 @@ int mmla_si_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, int
     const Pcm p{cd.q, cd.clip_len, cd.kept, 0};
     return si_fe_net(c, p, c0, cnt, dev, probs, argmax, silent);
   }, std::max<int64_t>(items_per_stream, 1));
+}
+
+// Both networks on one conditioning: per micro-batch (whole streams, OD's cap) Conditioner::run once,
+// then each network's front-end + net under its own range guard, reading the conditioned clips that
+// stay in S_COND_Q / S_COND_KEPT.  A guard re-run repeats that network alone; an allocation failure
+// repeats the micro-batch with fewer clips, the detectors restored by Conditioner::run's snapshot.
+int mmla_room_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
+                                   const int32_t* lens, int32_t clip_len, const int32_t* profile,
+                                   int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
+                                   int16_t* out_pcm, int32_t* kept_len, float* od_probs,
+                                   int32_t* od_argmax, float* si_probs, int32_t* si_argmax,
+                                   uint8_t* silent, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, items_per_stream,
+                 out_pcm, kept_len};
+  const bool dev = flags & MMLA_DEVICE_PTR;
+  if (const char* bad = cd.bad(c, dev)) return fail(c, MMLA_E_INVALID, "%s", bad);
+  if (!c->od_loaded) return fail(c, MMLA_E_NOWEIGHTS, "OD weights not loaded");
+  if (!c->si_loaded) return fail(c, MMLA_E_NOWEIGHTS, "SI weights not loaded");
+  if (cd.off()) {   // nothing to condition: the two plain pipelines, then the copies asked for
+    CHK(od_pipeline_common(c, pcm, n, stride, lens, clip_len, false, 0, 0.0f, od_probs, od_argmax, silent,
+                           nullptr, flags));
+    CHK(mmla_si_pipeline(c, pcm, n, stride, lens, clip_len, si_probs, si_argmax, nullptr, flags));
+    return out_pcm || kept_len ? condition_call(c, cd, flags) : MMLA_OK;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  CHK(for_microbatches(c, true, n, [&](int64_t c0, int64_t cnt) -> int {
+    CHK(cd.run(c, c0, cnt, dev));
+    CHK(guarded(c, dev, c->od_f32_only, [&]() -> int {
+      return od_fe_net(c, cd, c0, cnt, dev, od_probs, od_argmax, silent);
+    }));
+    CHK(guarded(c, dev, c->si_f32_only, [&]() -> int {
+      // the conditioned clips with lens = kept_len, as mmla_si_pipeline_conditioned reads them; its
+      // 'silent' (kept_len < 4000, the rule of OD's gate) stays in the workspace
+      const Pcm p{cd.q, cd.clip_len, cd.kept, 0};
+      return si_fe_net(c, p, c0, cnt, dev, si_probs, si_argmax, nullptr, S_ROOM_P, S_ROOM_A);
+    }));
+    if (!dev) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MMLA_OK;
+  }, std::max<int64_t>(items_per_stream, 1)));
+  return finish(c, dev);
 }
 
 int mmla_debug_od_trace(mmla_ctx* c, const float* x, int64_t n, int stage, float* out,

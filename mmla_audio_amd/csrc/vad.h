@@ -36,8 +36,13 @@ struct VadArgs {
 bool vad_init_state(VadState* s, int mode);
 // Frames of an item of `len` samples (frame_generator: k * 480 + 480 < len).
 __host__ __device__ inline int vad_frames(int64_t len) { return len > 480 ? (int)((len - 1) / 480) : 0; }
-// Per-frame decisions of every item, stream by stream (one thread per stream).
-hipError_t vad_speech_launch(const VadArgs& a, hipStream_t s);
+// Stream counts up to this run on vad_speech_wave_kernel (one stream per wave), larger ones on
+// vad_speech_kernel (one thread per stream); measured, DESIGN.md 4.10.
+constexpr int64_t kVadWaveMaxStreams = 4096;
+inline bool vad_wave_streams(int64_t n_streams) { return n_streams <= kVadWaveMaxStreams; }
+// Per-frame decisions of every item, stream by stream: one stream per wave (wave) or per thread; the
+// same decisions and states bit for bit.
+hipError_t vad_speech_launch(const VadArgs& a, bool wave, hipStream_t s);
 // vad_collector + the rewrite from `speech` (one wave per item).
 hipError_t vad_collect_launch(const VadArgs& a, hipStream_t s);
 // soundfile's PCM_16 write of float audio (libsndfile f2s: (short) lrintf(x * 0x7FFF)).
