@@ -44,6 +44,9 @@ enum mmla_model { MMLA_MODEL_OD = 0, MMLA_MODEL_SI = 1 };
 enum mmla_head { MMLA_HEAD_SOFTMAX = 0, MMLA_HEAD_SIGMOID = 1 };
 
 #define MMLA_DEVICE_PTR 0x1u /* data pointers are device pointers; call is asynchronous */
+/* the calls that take nr_passes (mmla_condition, mmla_{od,si,room}_pipeline_conditioned,
+ * mmla_od_pipeline_gated): the passes run the non-stationary gate of mmla_nr_reduce_ns */
+#define MMLA_NR_NONSTATIONARY 0x2u
 
 /* OD front-end geometry (overlap_features_generator.py:39-42,73-81) */
 #define MMLA_OD_MELS 128
@@ -348,6 +351,42 @@ int mmla_nr_set_noise_bank(mmla_ctx* ctx, const float* noise, int64_t n_profiles
                            const int32_t* lens, int32_t len, int32_t sr, uint32_t flags);
 int mmla_nr_reduce_bank(mmla_ctx* ctx, const float* y, int64_t n_signals, int64_t stride, int64_t len,
                         const int32_t* profile, float* out, uint32_t flags);
+
+/*
+ * Non-stationary spectral gate: noisereduce 2.0.x reduce_noise(y=y, sr=sr) in its default mode
+ * (stationary=False, SpectralGateNonStationary), which needs NO noise recording.  The reference's
+ * scripts never call this mode; it is here for rooms whose microphones have no ambient-noise clip or
+ * whose noise changes during a session.  Parity with the library is unpinned (it is not installed);
+ * the definition is the numpy / scipy restatement in tests/nr_ns_ref.py.  Per chunk buffer (chunks,
+ * padding, STFT, the 33 x 7 mask smoothing, iSTFT and the kept interior are mmla_nr_reduce's):
+ *   A = |STFT|;  t = time_constant_s * sr / 256;  b = (sqrt(1 + 4 t^2) - 1) / (2 t^2);
+ *   smooth = scipy.signal.filtfilt([b], [1, b - 1], A, axis=time, padtype=None), evaluated per bin as
+ *     the sequential recurrence  z = (1-b) A[0];  f[t] = b A[t] + z;  z = (1-b) f[t]  forward, then
+ *     z = (1-b) f[T-1];  g[t] = b f[t] + z;  z = (1-b) g[t]  backward, in float64 without FMA;
+ *   mask = 1 / (1 + exp(-((A - smooth) / smooth - thresh_n_mult) * sigmoid_slope)), smoothed 33 x 7,
+ *   out = istft(STFT * mask), float32.
+ * One deliberate deviation: where smooth == 0 the mask is 0.  That happens only for a buffer of nothing
+ * but zeros, for which the library computes 0 / 0 and returns NaN; here such a buffer comes out as zeros.
+ * mmla_nr_set_nonstationary: the gate's parameters, kept in the context, which starts with noisereduce's
+ *   defaults (2.0 s, 2.0, 10.0, 16000): no call is needed for them.  MMLA_E_INVALID: time_constant_s or
+ *   sigmoid_slope not finite or <= 0, thresh_n_mult not finite, an sr whose smoothing filter is not
+ *   33 x 7 (15360..16000), or an sr that differs from that of a noise bank the context holds.
+ * mmla_nr_reduce_ns: mmla_nr_reduce's contract (chunking, host / device pointers, at most 512 chunk
+ *   buffers per launch) without a noise profile.
+ * MMLA_NR_NONSTATIONARY in the flags of mmla_condition, mmla_{od,si,room}_pipeline_conditioned and
+ *   mmla_od_pipeline_gated: the nr_passes passes run this gate with the context's parameters, `profile`
+ *   is ignored and no noise bank is required; everything else (the PCM_16 round trip per pass, lens,
+ *   micro-batching, re-runs, stream synchronisation) is unchanged.  Without the flag those calls behave
+ *   as before, MMLA_E_INVALID for nr_passes > 0 without a bank included.
+ * The smoothed floor sees the whole buffer: the zero padding and a clip's zero tail pull it down near
+ * the ends, as the library's does for a buffer of that length.  So the fused calls' rule "gated
+ * zero-extended to clip_len" is the definition here too: clip c's result is mmla_nr_reduce_ns of the
+ * clip zero-extended to clip_len, NOT of the clip cut at lens[c].
+ */
+int mmla_nr_set_nonstationary(mmla_ctx* ctx, double time_constant_s, double thresh_n_mult,
+                              double sigmoid_slope, int32_t sr);
+int mmla_nr_reduce_ns(mmla_ctx* ctx, const float* y, int64_t n_signals, int64_t stride, int64_t len,
+                      float* out, uint32_t flags);
 
 /*
  * The PC loops' pre-conditioning of every recorded clip as one batched call: the batched

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, 'libmmla.so')
 
 MMLA_OK = 0
 MMLA_DEVICE_PTR = 0x1
+MMLA_NR_NONSTATIONARY = 0x2
 MODEL_OD, MODEL_SI = 0, 1
 HEAD_SOFTMAX, HEAD_SIGMOID = 0, 1
 PREC_F32, PREC_F16X3 = 0, 1
@@ -38,6 +39,8 @@ SIGNATURES = {
     'mmla_nr_reduce': [_P, _P, _I64, _I64, _I64, _P, ctypes.c_uint32],
     'mmla_nr_set_noise_bank': [_P, _P, _I64, _I64, _P, _I32, _I32, _U32],
     'mmla_nr_reduce_bank': [_P, _P, _I64, _I64, _I64, _P, _P, _U32],
+    'mmla_nr_set_nonstationary': [_P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I32],
+    'mmla_nr_reduce_ns': [_P, _P, _I64, _I64, _I64, _P, _U32],
     'mmla_condition': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P, _U32],
     'mmla_od_pipeline_conditioned': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P,
                                      _P, _P, _P, _U32],
@@ -155,6 +158,11 @@ def _ptr(a):
     if isinstance(a, int):
         return a
     return a.ctypes.data
+
+
+def _ns(nonstationary):
+    """the flag bit of the conditioned calls' nonstationary= keyword"""
+    return MMLA_NR_NONSTATIONARY if nonstationary else 0
 
 
 class MmlaError(RuntimeError):
@@ -329,6 +337,28 @@ class Context:
         """profile: device int32 [n] (0: profile 0); indices outside the bank are clamped"""
         self._check(self.lib.mmla_nr_reduce_bank(self.h, y, n, stride, length, profile or None, out,
                                                  MMLA_DEVICE_PTR), 'mmla_nr_reduce_bank(dev)')
+
+    def nr_set_nonstationary(self, time_constant_s=2.0, thresh_n_mult=2.0, sigmoid_slope=10.0, sr=16000):
+        """Parameters of the non-stationary gate (nr_reduce_ns, nonstationary=True); a context starts
+        with these defaults."""
+        self._check(self.lib.mmla_nr_set_nonstationary(self.h, float(time_constant_s), float(thresh_n_mult),
+                                                       float(sigmoid_slope), int(sr)),
+                    'mmla_nr_set_nonstationary')
+
+    def nr_reduce_ns(self, y):
+        """Gate float32 signals y [n, len] (or [len]) with the non-stationary gate: no noise profile."""
+        a = np.ascontiguousarray(y, dtype=np.float32)
+        flat = a.ndim == 1
+        if flat:
+            a = a[None]
+        out = np.empty_like(a)
+        self._check(self.lib.mmla_nr_reduce_ns(self.h, _ptr(a), a.shape[0], a.shape[1], a.shape[1],
+                                               _ptr(out), 0), 'mmla_nr_reduce_ns')
+        return out[0] if flat else out
+
+    def nr_reduce_ns_dev(self, y, n, stride, length, out):
+        self._check(self.lib.mmla_nr_reduce_ns(self.h, y, n, stride, length, out, MMLA_DEVICE_PTR),
+                    'mmla_nr_reduce_ns(dev)')
 
     @staticmethod
     def _profile(profile, n):
@@ -582,10 +612,11 @@ class Context:
                     'mmla_od_pipeline')
         return probs, am, silent.astype(bool)
 
-    def od_pipeline_gated(self, pcm, lens=None, passes=4, threshold=0.3):
+    def od_pipeline_gated(self, pcm, lens=None, passes=4, threshold=0.3, nonstationary=False):
         """od_pipeline with the denoise-and-compare silence gate of record_on_pi.py:103-124 (noise
-        profile: nr_set_noise) -> (probs [n,2] of the denoised clips, argmax [n] (-1 = 'silent'),
-        silent [n] bool, ssim [n] of each clip's image against its `passes` x denoised image)."""
+        profile: nr_set_noise; nonstationary=True: the gate of nr_reduce_ns, no profile) -> (probs [n,2]
+        of the denoised clips, argmax [n] (-1 = 'silent'), silent [n] bool, ssim [n] of each clip's
+        image against its `passes` x denoised image)."""
         a, ln, L = self._pcm(pcm, lens)
         n = a.shape[0]
         probs = np.empty((n, 2), np.float32)
@@ -594,12 +625,12 @@ class Context:
         ssim = np.empty(n, np.float32)
         self._check(self.lib.mmla_od_pipeline_gated(
             self.h, _ptr(a), n, a.shape[1], _ptr(ln), L, int(passes), float(threshold), _ptr(probs),
-            _ptr(am), _ptr(silent), _ptr(ssim), 0), 'mmla_od_pipeline_gated')
+            _ptr(am), _ptr(silent), _ptr(ssim), _ns(nonstationary)), 'mmla_od_pipeline_gated')
         return probs, am, silent.astype(bool), ssim
 
     # -- the PC loops' pre-conditioning (noise gate + silence removal) in front of the networks ---
     def _conditioned(self, fn, what, pcm, lens, profile, passes, silence_remove, items_per_stream,
-                     n_classes, return_pcm):
+                     n_classes, return_pcm, nonstationary=False):
         a, ln, L = self._pcm(pcm, lens)
         n = a.shape[0]
         pr = self._profile(profile, n)
@@ -608,42 +639,42 @@ class Context:
         head = (self.h, _ptr(a), n, a.shape[1], _ptr(ln), L, _ptr(pr), int(passes),
                 int(bool(silence_remove)), int(items_per_stream), _ptr(out), _ptr(kept))
         if n_classes is None:
-            self._check(fn(*head, 0), what)
+            self._check(fn(*head, _ns(nonstationary)), what)
             return out, kept
         probs = np.empty((n, n_classes), np.float32)
         am = np.empty(n, np.int32)
         silent = np.empty(n, np.uint8)
-        self._check(fn(*head, _ptr(probs), _ptr(am), _ptr(silent), 0), what)
+        self._check(fn(*head, _ptr(probs), _ptr(am), _ptr(silent), _ns(nonstationary)), what)
         res = (probs, am, silent.astype(bool), kept)
         return res + (out,) if return_pcm else res
 
     def condition(self, pcm, lens=None, profile=None, passes=1, silence_remove=True,
-                  items_per_stream=1):
+                  items_per_stream=1, nonstationary=False):
         """The batched save_wave_file(noise_reduce=True, silence_remove=...) of record_on_pc.py: int16
         [n, L] (or a list) -> (conditioned int16 [n, L], zeros behind each clip's kept samples; kept_len
         [n]).  Clip c is gated `passes` times against noise profile profile[c] (nr_set_noise_bank; None:
-        profile 0); silence removal runs on the vad_reset detectors, stream s owning clips
+        profile 0; nonstationary=True: the gate of nr_reduce_ns, no bank, profile ignored); silence removal runs on the vad_reset detectors, stream s owning clips
         [s * items_per_stream, (s + 1) * items_per_stream), and their state persists across calls."""
         return self._conditioned(self.lib.mmla_condition, 'mmla_condition', pcm, lens, profile, passes,
-                                 silence_remove, items_per_stream, None, True)
+                                 silence_remove, items_per_stream, None, True, nonstationary)
 
     def od_pipeline_conditioned(self, pcm, lens=None, profile=None, passes=1, silence_remove=True,
-                                items_per_stream=1, return_pcm=False):
+                                items_per_stream=1, return_pcm=False, nonstationary=False):
         """condition() fused in front of od_pipeline -> (probs [n,2], argmax [n] (-1 = 'silent': fewer
         than 4000 samples kept), silent [n] bool, kept_len [n]); return_pcm adds the conditioned clips."""
         return self._conditioned(self.lib.mmla_od_pipeline_conditioned, 'mmla_od_pipeline_conditioned',
                                  pcm, lens, profile, passes, silence_remove, items_per_stream, 2,
-                                 return_pcm)
+                                 return_pcm, nonstationary)
 
     def si_pipeline_conditioned(self, pcm, lens=None, profile=None, passes=1, silence_remove=True,
-                                items_per_stream=1, return_pcm=False):
+                                items_per_stream=1, return_pcm=False, nonstationary=False):
         """condition() fused in front of si_pipeline -> (probs [n,K], argmax, silent, kept_len)"""
         return self._conditioned(self.lib.mmla_si_pipeline_conditioned, 'mmla_si_pipeline_conditioned',
                                  pcm, lens, profile, passes, silence_remove, items_per_stream,
-                                 self.si_classes or 0, return_pcm)
+                                 self.si_classes or 0, return_pcm, nonstationary)
 
     def room_pipeline_conditioned(self, pcm, lens=None, profile=None, passes=1, silence_remove=True,
-                                  items_per_stream=1, return_pcm=False):
+                                  items_per_stream=1, return_pcm=False, nonstationary=False):
         """condition() once in front of od_pipeline and si_pipeline -> (od_probs [n,2], od_argmax [n],
         si_probs [n,K], si_argmax [n], silent [n] bool, kept_len [n]); return_pcm adds the conditioned
         clips.  Both argmax are -1 where fewer than 4000 samples were kept."""
@@ -660,7 +691,8 @@ class Context:
         self._check(self.lib.mmla_room_pipeline_conditioned(
             self.h, _ptr(a), n, a.shape[1], _ptr(ln), L, _ptr(pr), int(passes),
             int(bool(silence_remove)), int(items_per_stream), _ptr(out), _ptr(kept), _ptr(od_probs),
-            _ptr(od_am), _ptr(si_probs), _ptr(si_am), _ptr(silent), 0), 'mmla_room_pipeline_conditioned')
+            _ptr(od_am), _ptr(si_probs), _ptr(si_am), _ptr(silent), _ns(nonstationary)),
+            'mmla_room_pipeline_conditioned')
         res = (od_probs, od_am, si_probs, si_am, silent.astype(bool), kept)
         return res + (out,) if return_pcm else res
 
@@ -749,50 +781,51 @@ class Context:
                     'mmla_od_pipeline(dev)')
 
     def od_pipeline_gated_dev(self, pcm, n, stride, clip_len, passes=4, threshold=0.3, probs=0,
-                              argmax=0, silent=0, ssim=0, lens=0):
+                              argmax=0, silent=0, ssim=0, lens=0, nonstationary=False):
         """synchronises the context stream internally when passes > 0 (see mmla.h)"""
         self._check(self.lib.mmla_od_pipeline_gated(
             self.h, pcm, n, stride, lens or None, clip_len, int(passes), float(threshold),
-            probs or None, argmax or None, silent or None, ssim or None, MMLA_DEVICE_PTR),
-            'mmla_od_pipeline_gated(dev)')
+            probs or None, argmax or None, silent or None, ssim or None,
+            MMLA_DEVICE_PTR | _ns(nonstationary)), 'mmla_od_pipeline_gated(dev)')
 
     def condition_dev(self, pcm, n, stride, clip_len, passes=1, silence_remove=True,
-                      items_per_stream=1, out_pcm=0, kept_len=0, lens=0, profile=0):
+                      items_per_stream=1, out_pcm=0, kept_len=0, lens=0, profile=0, nonstationary=False):
         """synchronises the context stream internally when passes > 0 (see mmla.h)"""
         self._check(self.lib.mmla_condition(
             self.h, pcm, n, stride, lens or None, clip_len, profile or None, int(passes),
             int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
-            MMLA_DEVICE_PTR), 'mmla_condition(dev)')
+            MMLA_DEVICE_PTR | _ns(nonstationary)), 'mmla_condition(dev)')
 
     def od_pipeline_conditioned_dev(self, pcm, n, stride, clip_len, passes=1, silence_remove=True,
                                     items_per_stream=1, probs=0, argmax=0, silent=0, out_pcm=0,
-                                    kept_len=0, lens=0, profile=0):
+                                    kept_len=0, lens=0, profile=0, nonstationary=False):
         """synchronises the context stream internally when passes > 0 (see mmla.h)"""
         self._check(self.lib.mmla_od_pipeline_conditioned(
             self.h, pcm, n, stride, lens or None, clip_len, profile or None, int(passes),
             int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
-            probs or None, argmax or None, silent or None, MMLA_DEVICE_PTR),
+            probs or None, argmax or None, silent or None, MMLA_DEVICE_PTR | _ns(nonstationary)),
             'mmla_od_pipeline_conditioned(dev)')
 
     def si_pipeline_conditioned_dev(self, pcm, n, stride, clip_len, passes=1, silence_remove=True,
                                     items_per_stream=1, probs=0, argmax=0, silent=0, out_pcm=0,
-                                    kept_len=0, lens=0, profile=0):
+                                    kept_len=0, lens=0, profile=0, nonstationary=False):
         """synchronises the context stream internally when passes > 0 (see mmla.h)"""
         self._check(self.lib.mmla_si_pipeline_conditioned(
             self.h, pcm, n, stride, lens or None, clip_len, profile or None, int(passes),
             int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
-            probs or None, argmax or None, silent or None, MMLA_DEVICE_PTR),
+            probs or None, argmax or None, silent or None, MMLA_DEVICE_PTR | _ns(nonstationary)),
             'mmla_si_pipeline_conditioned(dev)')
 
     def room_pipeline_conditioned_dev(self, pcm, n, stride, clip_len, passes=1, silence_remove=True,
                                       items_per_stream=1, od_probs=0, od_argmax=0, si_probs=0,
-                                      si_argmax=0, silent=0, out_pcm=0, kept_len=0, lens=0, profile=0):
+                                      si_argmax=0, silent=0, out_pcm=0, kept_len=0, lens=0, profile=0,
+                                      nonstationary=False):
         """synchronises the context stream internally when passes > 0 (see mmla.h)"""
         self._check(self.lib.mmla_room_pipeline_conditioned(
             self.h, pcm, n, stride, lens or None, clip_len, profile or None, int(passes),
             int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
             od_probs or None, od_argmax or None, si_probs or None, si_argmax or None, silent or None,
-            MMLA_DEVICE_PTR), 'mmla_room_pipeline_conditioned(dev)')
+            MMLA_DEVICE_PTR | _ns(nonstationary)), 'mmla_room_pipeline_conditioned(dev)')
 
     def ssim_u8_dev(self, a, b, n, h, w, c, out):
         self._check(self.lib.mmla_ssim_u8(self.h, a, b, n, h, w, c, out, MMLA_DEVICE_PTR),

@@ -1,5 +1,5 @@
-// libmmla C ABI, the auxiliary entry points: CRC-32C and PNG helpers (host only), the stationary
-// noise gate, silence removal, PCM conversion and the two resamplers.  The context, the weights, the
+// libmmla C ABI, the auxiliary entry points: CRC-32C and PNG helpers (host only), the stationary and
+// the non-stationary noise gate, silence removal, PCM conversion and the two resamplers.  The context, the weights, the
 // network runners and the feature / pipeline entry points live in the files internal.h lists.
 // See include/mmla.h for the contract and the reference call site each entry point replaces.
 #include <algorithm>
@@ -97,6 +97,18 @@ constexpr int64_t kNrChunk = 600000, kNrPadding = 30000;   // noisereduce 2.0 de
 constexpr int64_t kNrItemsPerLaunch = 512;                  // ~3.4 GB of scratch per launch (2.5 s)
 }  // namespace
 
+// the gate's device tables, built on first use by whichever gate comes first (the 33 x 7 smoothing
+// filter is the same for every sample rate that has one)
+static int nr_tables_ready(mmla_ctx* c, int32_t sr) {
+  if (c->nr_tables) return MMLA_OK;
+  NrTables t;
+  nr_build_tables(&t, sr);
+  if (t.ngf != NR_NGF || t.ngt != NR_NGT) return fail(c, MMLA_E_INVALID, "smoothing filter shape");
+  HIPCHK(c, hipMalloc(&c->nr_tables, sizeof(NrTables)));
+  HIPCHK(c, hipMemcpy(c->nr_tables, &t, sizeof(t), hipMemcpyHostToDevice));
+  return MMLA_OK;
+}
+
 // the body of both profile setters: profile p = noise + p * stride, lens[p] (nullable: len) samples
 static int nr_set_bank(mmla_ctx* c, const float* noise, int64_t n_profiles, int64_t stride,
                        const int32_t* lens, int64_t len, int32_t sr, uint32_t flags) {
@@ -114,13 +126,7 @@ static int nr_set_bank(mmla_ctx* c, const float* noise, int64_t n_profiles, int6
                     (long long)len);
   HIPCHK(c, hipSetDevice(c->device));
   constexpr int64_t bins = NR_NFFT / 2 + 1;
-  if (!c->nr_tables) {
-    NrTables t;
-    nr_build_tables(&t, sr);
-    if (t.ngf != NR_NGF || t.ngt != NR_NGT) return fail(c, MMLA_E_INVALID, "smoothing filter shape");
-    HIPCHK(c, hipMalloc(&c->nr_tables, sizeof(NrTables)));
-    HIPCHK(c, hipMemcpy(c->nr_tables, &t, sizeof(t), hipMemcpyHostToDevice));
-  }
+  CHK(nr_tables_ready(c, sr));
   if (c->nr_profiles != n_profiles) {
     HIPCHK(c, hipStreamSynchronize(c->stream));   // a gate still reading the old bank
     if (c->nr_thresh) HIPCHK(c, hipFree(c->nr_thresh));
@@ -149,6 +155,29 @@ static int nr_set_bank(mmla_ctx* c, const float* noise, int64_t n_profiles, int6
   LAUNCH(c, MMLA_STAGE_NR, (double)n_profiles * m * 4, nr_noise_launch(a, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));   // one synchronisation per bank
   c->nr_ready = true;
+  c->nr_bank_sr = sr;
+  return MMLA_OK;
+}
+
+int mmla_nr_set_nonstationary(mmla_ctx* c, double time_constant_s, double thresh_n_mult,
+                              double sigmoid_slope, int32_t sr) {
+  if (!c) return MMLA_E_INVALID;
+  if (!std::isfinite(time_constant_s) || time_constant_s <= 0 || !std::isfinite(sigmoid_slope) ||
+      sigmoid_slope <= 0 || !std::isfinite(thresh_n_mult))
+    return fail(c, MMLA_E_INVALID, "non-stationary gate: time_constant_s and sigmoid_slope must be finite and > 0, thresh_n_mult finite");
+  if (sr <= 0) return fail(c, MMLA_E_INVALID, "non-stationary gate: sr = %d", sr);
+  NrTables t;
+  nr_build_tables(&t, sr);
+  if (t.ngf != NR_NGF || t.ngt != NR_NGT)
+    return fail(c, MMLA_E_INVALID, "non-stationary gate: the smoothing filter at sr = %d is %d x %d, not %d x %d",
+                sr, t.ngf, t.ngt, NR_NGF, NR_NGT);
+  if (c->nr_ready && c->nr_bank_sr != sr)
+    return fail(c, MMLA_E_INVALID, "non-stationary gate: sr = %d differs from the noise bank's %d", sr,
+                c->nr_bank_sr);
+  c->ns_time_constant_s = time_constant_s;
+  c->ns_thresh_n_mult = thresh_n_mult;
+  c->ns_sigmoid_slope = sigmoid_slope;
+  c->ns_sr = sr;
   return MMLA_OK;
 }
 
@@ -168,9 +197,17 @@ int mmla_nr_set_noise_bank(mmla_ctx* c, const float* noise, int64_t n_profiles, 
 
 // the gate of mmla_nr_reduce on device pointers; mmla_od_pipeline_gated runs its passes through it too
 int mmla::nr_reduce_dev(mmla_ctx* c, const float* dy, int64_t n_signals, int64_t stride, int64_t len,
-                        float* dout, const int32_t* dprofile) {
-  if (!c->nr_ready) return fail(c, MMLA_E_INVALID, "mmla_nr_set_noise must be called first");
+                        float* dout, const int32_t* dprofile, bool nonstationary) {
+  if (!nonstationary && !c->nr_ready) return fail(c, MMLA_E_INVALID, "mmla_nr_set_noise must be called first");
   if (n_signals <= 0 || len <= 0) return MMLA_OK;
+  NrNsParams ns{};
+  if (nonstationary) {
+    CHK(nr_tables_ready(c, c->ns_sr));
+    ns.b = nr_ns_coefficient(c->ns_time_constant_s, c->ns_sr);
+    ns.one_minus_b = -(ns.b - 1.0);   // scipy's lfilter forms -a[1] of a = [1, b - 1]
+    ns.shift = c->ns_thresh_n_mult;
+    ns.slope = c->ns_sigmoid_slope;
+  }
   // SpectralGate.get_traces: one chunk of `len` when len <= chunk_size, else chunk_size pieces
   const int64_t keep = len <= kNrChunk ? len : kNrChunk;
   const int64_t per = (len + keep - 1) / keep;
@@ -188,8 +225,11 @@ int mmla::nr_reduce_dev(mmla_ctx* c, const float* dy, int64_t n_signals, int64_t
     const int64_t ni = std::min<int64_t>(cap, (int64_t)items.size() - (int64_t)i0);
     void *pS, *pB, *pM, *pF, *pI, *pR;
     CHK(ws_get(c, S_NR_S, (size_t)ni * T * bins * sizeof(double2), &pS));
-    CHK(ws_get(c, S_NR_BITS, (size_t)ni * T * bins, &pB));
-    CHK(ws_get(c, S_NR_FMAX, (size_t)ni * (T + 1) * sizeof(double), &pM));
+    pB = pM = nullptr;   // the non-stationary gate has no threshold bits and no dB maxima
+    if (!nonstationary) {
+      CHK(ws_get(c, S_NR_BITS, (size_t)ni * T * bins, &pB));
+      CHK(ws_get(c, S_NR_FMAX, (size_t)ni * (T + 1) * sizeof(double), &pM));
+    }
     CHK(ws_get(c, S_NR_FRAMES, (size_t)ni * T * NR_NFFT * sizeof(double), &pF));
     CHK(ws_get(c, S_NR_ITEMS, (size_t)ni * sizeof(NrItem), &pI));
     CHK(ws_get(c, S_NR_ROWS, (size_t)ni * T * bins * sizeof(double), &pR));
@@ -207,20 +247,21 @@ int mmla::nr_reduce_dev(mmla_ctx* c, const float* dy, int64_t n_signals, int64_t
     nr_frame_range(items.data() + i0, ni, L, T, a.keep0, a.keep_len, &a.t_lo, &t_hi);
     a.t_n = t_hi - a.t_lo + 1;
     a.tables = c->nr_tables;
-    a.thresh = c->nr_thresh;
-    a.profile = dprofile;
-    a.n_profiles = (int)c->nr_profiles;
+    a.thresh = nonstationary ? nullptr : c->nr_thresh;
+    a.profile = nonstationary ? nullptr : dprofile;
+    a.n_profiles = nonstationary ? 0 : (int)c->nr_profiles;
     a.prop_decrease = 1.0;
     a.S = static_cast<double2*>(pS);
     a.bits = static_cast<uint8_t*>(pB);
     a.fmax = static_cast<double*>(pM);
-    a.gmax = static_cast<double*>(pM) + ni * T;
+    a.gmax = pM ? static_cast<double*>(pM) + ni * T : nullptr;
     a.frames = static_cast<double*>(pF);
     a.rows = static_cast<double*>(pR);
     a.out = dout;
     double bytes = 0;
     for (int64_t i = 0; i < ni; ++i) bytes += 8.0 * items[i0 + i].out_len;   // f32 in + f32 out
-    LAUNCH(c, MMLA_STAGE_NR, bytes, nr_gate_launch(a, c->stream));
+    if (nonstationary) LAUNCH(c, MMLA_STAGE_NR, bytes, nr_ns_gate_launch(a, ns, c->stream));
+    else LAUNCH(c, MMLA_STAGE_NR, bytes, nr_gate_launch(a, c->stream));
     // the item table / scratch of this launch must not be overwritten by the next one's upload
     if (i0 + cap < items.size()) HIPCHK(c, hipStreamSynchronize(c->stream));
   }
@@ -230,11 +271,11 @@ int mmla::nr_reduce_dev(mmla_ctx* c, const float* dy, int64_t n_signals, int64_t
 extern "C" {
 
 static int nr_reduce_common(mmla_ctx* c, const float* y, int64_t n_signals, int64_t stride, int64_t len,
-                            const int32_t* profile, float* out, uint32_t flags) {
+                            const int32_t* profile, float* out, uint32_t flags, bool nonstationary = false) {
   if (n_signals < 0 || len < 0 || (n_signals > 0 && (!y || !out)) ||
       (n_signals > 1 && stride < len))
     return fail(c, MMLA_E_INVALID, "bad nr_reduce args");
-  if (!c->nr_ready) return fail(c, MMLA_E_INVALID, "mmla_nr_set_noise must be called first");
+  if (!nonstationary && !c->nr_ready) return fail(c, MMLA_E_INVALID, "mmla_nr_set_noise must be called first");
   const bool dev = flags & MMLA_DEVICE_PTR;
   // device-pointer profile indices cannot be seen here: the kernels clamp them into the bank
   if (profile && !dev)
@@ -255,7 +296,7 @@ static int nr_reduce_common(mmla_ctx* c, const float* y, int64_t n_signals, int6
     CHK(ws_get(c, S_OUT0, (size_t)n_signals * len * sizeof(float), &p));
     dout = static_cast<float*>(p);
   }
-  CHK(nr_reduce_dev(c, dy, n_signals, stride, len, dout, dprof));
+  CHK(nr_reduce_dev(c, dy, n_signals, stride, len, dout, dprof, nonstationary));
   CHK(copy_back(c, out, 0, dout, (size_t)n_signals * len, dev));
   return finish(c, dev);
 }
@@ -270,6 +311,12 @@ int mmla_nr_reduce_bank(mmla_ctx* c, const float* y, int64_t n_signals, int64_t 
                         const int32_t* profile, float* out, uint32_t flags) {
   if (!c) return MMLA_E_INVALID;
   return nr_reduce_common(c, y, n_signals, stride, len, profile, out, flags);
+}
+
+int mmla_nr_reduce_ns(mmla_ctx* c, const float* y, int64_t n_signals, int64_t stride, int64_t len,
+                      float* out, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  return nr_reduce_common(c, y, n_signals, stride, len, nullptr, out, flags, true);
 }
 
 // ---- silence removal: webrtcvad + vad_collector, soundfile PCM_16 ------------

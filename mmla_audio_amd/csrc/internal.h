@@ -192,6 +192,10 @@ struct mmla_ctx {
   float* nr_thresh = nullptr;
   int64_t nr_profiles = 0;
   bool nr_ready = false;
+  int32_t nr_bank_sr = 0;      // the sample rate the bank was built for (0: no bank)
+  // the non-stationary gate's parameters (mmla_nr_set_nonstationary; noisereduce's defaults)
+  double ns_time_constant_s = 2.0, ns_thresh_n_mult = 2.0, ns_sigmoid_slope = 10.0;
+  int32_t ns_sr = 16000;
 };
 
 namespace mmla __attribute__((visibility("hidden"))) {
@@ -250,8 +254,10 @@ inline bool vad_use_wave(const mmla_ctx* c, int64_t n_streams) {
 // the body of mmla_nr_reduce on device pointers (capi.cpp): y [n_signals, stride] -> out [n_signals,
 // len].  At most 512 items per launch with a stream synchronisation between launches.  profile
 // (device, nullable = all 0): signal i is gated with noise profile profile[i] of the bank.
+// nonstationary: the gate of mmla_nr_reduce_ns with the context's parameters instead; no bank is
+// needed and profile is not read.
 int nr_reduce_dev(mmla_ctx* c, const float* y, int64_t n_signals, int64_t stride, int64_t len, float* out,
-                  const int32_t* profile = nullptr);
+                  const int32_t* profile = nullptr, bool nonstationary = false);
 
 // device view of `count` input elements: the caller's pointer (device mode) or a copy in `slot`
 template <typename T>

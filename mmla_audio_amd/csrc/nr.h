@@ -1,4 +1,4 @@
-// Stationary spectral-gate noise reduction kernel interface (see nr.hip).
+// Spectral-gate noise reduction kernel interface, stationary and non-stationary (see nr.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -68,6 +68,16 @@ struct NrNoiseArgs {
 };
 hipError_t nr_noise_launch(const NrNoiseArgs& a, hipStream_t s);
 hipError_t nr_gate_launch(const NrArgs& a, hipStream_t s);
+// The non-stationary gate (noisereduce's stationary=False; nr.hip) on the same items and
+// scratch: thresh / profile / bits / fmax / gmax are not read (nullable).  The noise floor is the
+// magnitude spectrogram smoothed along time per bin by filtfilt([b], [1, b - 1]); one_minus_b is
+// -(b - 1) as scipy forms it; mask = 1 / (1 + exp(-((|S| - floor) / floor - shift) * slope)).
+struct NrNsParams {
+  double b, one_minus_b, shift, slope;
+};
+// b of a time constant in seconds at sample rate sr (noisereduce get_time_smoothed_representation)
+double nr_ns_coefficient(double time_constant_s, int sr);
+hipError_t nr_ns_gate_launch(const NrArgs& a, const NrNsParams& p, hipStream_t s);
 // [t_lo, t_hi] covering, for every item, the frames whose window overlaps its signal and the frames
 // within the time-smoothing halo of the kept interior
 void nr_frame_range(const NrItem* items, int64_t n_items, int64_t L, int T, int64_t keep0,

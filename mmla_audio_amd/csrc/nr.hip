@@ -25,6 +25,8 @@
 // nr_noise_thresh_kernel in the reference's float32 arithmetic; a bank of profiles (one per
 // microphone) comes from one launch of each, the profile on the grid's y axis.  The two kernels that
 // read thresholds, nr_stft_kernel and nr_rows_kernel, take the row of the item's profile (thresh_of).
+// The non-stationary gate (no noise clip; the nr_ns_* kernels further down) replaces the first three
+// kernels and shares nr_gate_kernel and nr_ola_kernel.
 #include "common.h"
 #include "nr.h"
 
@@ -420,6 +422,190 @@ __global__ void nr_ola_kernel(NrArgs a) {
   a.out[it.out_off + i] = (float)acc;
 }
 
+// ---- non-stationary gate (noisereduce SpectralGateNonStationary) -----------------------
+// No noise clip: the noise floor of a bin is its magnitude smoothed along time, forward and backward,
+// by a one-pole filter (scipy filtfilt([b], [1, b - 1], padtype=None)), and the mask is a sigmoid of
+// the relative excess over it.  The mask then takes the stationary gate's way: frequency smoothing
+// (nr_ns_rows_kernel), time smoothing + inverse FFT (nr_gate_kernel), overlap-add (nr_ola_kernel).
+//   nr_ns_stft_kernel    nr_stft_kernel's frame load / FFT / split -> S and the magnitude row A
+//                        (float64, in a.rows) of EVERY launched frame, zeros for an all-zero window
+//   nr_ns_smooth_kernel  one thread per (item, bin), lanes along bins: walks all T frames forward
+//                        (f -> a.frames, free until nr_gate_kernel) and backward (g, the sigmoid ->
+//                        the mask over A in place), in scipy's operation order
+//   nr_ns_rows_kernel    the 33-tap frequency smoothing of a float64 mask row, in place
+
+__global__ void __launch_bounds__(NT) nr_ns_stft_kernel(NrArgs a) {
+  __shared__ cd buf[512];
+  const int lane = threadIdx.x;
+  const int64_t fr = frame_of_block(a);
+  if (fr < 0) return;
+  const int64_t item = fr / a.t_n;
+  const int t = a.t_lo + (int)(fr - item * a.t_n);
+  const NrItem it = a.items[item];
+  const NrTables& tb = *a.tables;
+  double2* S = a.S + (item * a.T + t) * NB;
+  double* A = a.rows + (item * a.T + t) * NB;
+  if (!load_frame(a, it, t, buf, lane)) {
+    // the smoother reads A of every launched frame and the gate S of those reaching the interior;
+    // the scratch holds an earlier call's data, so both are written
+    for (int k = lane; k < NB; k += NT) {
+      S[k] = double2{0.0, 0.0};
+      A[k] = 0.0;
+    }
+    return;
+  }
+  cd wk[KPL];
+#pragma unroll
+  for (int i = 0; i < KPL; ++i) {
+    const int k = min(lane + NT * i, NB - 1);
+    wk[i] = cd{tb.w1024[k][0], tb.w1024[k][1]};
+  }
+  lds_order();
+  fft512(buf, tb.w512, lane);
+#pragma unroll
+  for (int i = 0; i < KPL; ++i) {
+    const int k = lane + NT * i;
+    if (k >= NB) continue;
+    const cd z = buf[k & 511], zr = buf[(512 - k) & 511];
+    const cd e = {0.5 * (z.x + zr.x), 0.5 * (z.y - zr.y)};
+    const cd o = {0.5 * (z.y + zr.y), -0.5 * (z.x - zr.x)};
+    const cd X = cadd(e, cmul(wk[i], o));
+    S[k] = double2{X.x, X.y};
+    A[k] = hypot(X.x, X.y);                   // numpy's complex abs
+  }
+}
+
+// The recurrence is the definition (two roundings per step: ns_step keeps the compiler from
+// contracting the product and the sum into an FMA), so it stays sequential; what is hidden is the load latency: the next NS_BLK frames are
+// in registers before the current ones are worked through.  Frames outside [t_lo, t_lo + t_n) are
+// all-zero windows: A = 0 without reading the scratch.
+constexpr int NS_BLK = 16;
+MMLA_DEV double ns_step(double b, double x, double z) {   // b x + z, the product rounded first
+#pragma clang fp contract(off)
+  const double bx = b * x;
+  return bx + z;
+}
+__global__ void __launch_bounds__(NT) nr_ns_smooth_kernel(NrArgs a, NrNsParams p) {
+  const int k = blockIdx.x * NT + threadIdx.x;
+  if (k >= NB) return;
+  const int64_t item = blockIdx.y;
+  double* __restrict__ A = a.rows + item * a.T * NB + k;        // A[t] at A[t * NB]
+  double* __restrict__ F = a.frames + item * a.T * NFFT + k;    // f[t] at F[t * NB]
+  const int T = a.T, lo = a.t_lo, hi = a.t_lo + a.t_n;          // hi <= T
+  const double b = p.b, omb = p.one_minus_b;
+  auto load_a = [&](int t) { return t >= lo && t < hi ? A[(int64_t)t * NB] : 0.0; };
+  // forward: z = (1 - b) A[0]; f[t] = b A[t] + z; z = (1 - b) f[t]
+  double cur[NS_BLK], nxt[NS_BLK];
+#pragma unroll
+  for (int j = 0; j < NS_BLK; ++j) cur[j] = load_a(j);
+  double z = omb * cur[0], f = 0.0;
+  for (int t0 = 0; t0 < T; t0 += NS_BLK) {
+#pragma unroll
+    for (int j = 0; j < NS_BLK; ++j) nxt[j] = load_a(t0 + NS_BLK + j);
+#pragma unroll
+    for (int j = 0; j < NS_BLK; ++j) {
+      if (t0 + j >= T) break;
+      f = ns_step(b, cur[j], z);
+      z = omb * f;
+      F[(int64_t)(t0 + j) * NB] = f;
+    }
+#pragma unroll
+    for (int j = 0; j < NS_BLK; ++j) cur[j] = nxt[j];
+  }
+  wave_stores_done();   // f is re-read below by the thread that stored it
+  // backward: z = (1 - b) f[T-1]; g[t] = b f[t] + z; z = (1 - b) g[t]; mask from A and g
+  const int nblk = (T + NS_BLK - 1) / NS_BLK;
+  double fc[NS_BLK], ac[NS_BLK], fn[NS_BLK], an[NS_BLK];
+#pragma unroll
+  for (int j = 0; j < NS_BLK; ++j) {
+    const int t = (nblk - 1) * NS_BLK + j;
+    fc[j] = t < T ? F[(int64_t)t * NB] : 0.0;
+    ac[j] = load_a(t);
+  }
+  z = omb * f;
+  for (int bi = nblk - 1; bi >= 0; --bi) {
+    const int t0 = bi * NS_BLK;
+    if (bi > 0) {
+#pragma unroll
+      for (int j = 0; j < NS_BLK; ++j) {
+        const int t = t0 - NS_BLK + j;
+        fn[j] = F[(int64_t)t * NB];
+        an[j] = load_a(t);
+      }
+    }
+#pragma unroll
+    for (int j = NS_BLK - 1; j >= 0; --j) {
+      const int t = t0 + j;
+      if (t >= T) continue;
+      const double g = ns_step(b, fc[j], z);
+      z = omb * g;
+      if (t >= lo && t < hi) {     // the rows nr_ns_rows_kernel and nr_gate_kernel read are launched ones
+        const double x = (ac[j] - g) / g;
+        const double m = 1.0 / (1.0 + exp(-(x - p.shift) * p.slope));
+        A[(int64_t)t * NB] = g == 0.0 ? 0.0 : m;   // an all-zero buffer: zeros, not the library's NaN
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NS_BLK; ++j) {
+      fc[j] = fn[j];
+      ac[j] = an[j];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(NT) nr_ns_rows_kernel(NrArgs a) {
+  constexpr int HF = NG_F / 2;
+  __shared__ __attribute__((aligned(16))) double mrow[NB + 2 * HF];   // 16 zero bins each side
+  const int lane = threadIdx.x;
+  const int64_t fr = frame_of_block(a);
+  if (fr < 0) return;
+  const int64_t item = fr / a.t_n;
+  const int t = a.t_lo + (int)(fr - item * a.t_n);
+  if (!reaches(a, t, NG_T / 2)) return;
+  const NrTables& tb = *a.tables;
+  double* row = a.rows + (item * a.T + t) * NB;
+  constexpr int MPL = (NB + 2 * HF + NT - 1) / NT;   // 9
+  double mv[MPL];
+#pragma unroll
+  for (int i = 0; i < MPL; ++i) {                   // all loads first
+    const int kb = lane + NT * i - HF;
+    mv[i] = kb >= 0 && kb < NB ? row[kb] : 0.0;
+  }
+  double g[NG_F];
+#pragma unroll
+  for (int j = 0; j < NG_F; ++j) g[j] = tb.gf[j];
+#pragma unroll
+  for (int i = 0; i < MPL; ++i) {
+    const int k = lane + NT * i;
+    if (k < NB + 2 * HF) mrow[k] = mv[i];
+  }
+  lds_order();
+  // lane: bins 8 lane .. 8 lane + 7 from mrow[8 lane .. 8 lane + 39]; bin 512 by lane 0.  The whole
+  // row is in LDS before the first store overwrites it.
+  double m[8 + NG_F - 1];
+  const double2* m2 = reinterpret_cast<const double2*>(mrow + 8 * lane);
+#pragma unroll
+  for (int q = 0; q < (8 + NG_F - 1) / 2; ++q) {
+    const double2 u = m2[q];
+    m[2 * q] = u.x;
+    m[2 * q + 1] = u.y;
+  }
+  double last = 0.0;
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < NG_F; ++j) last = fma(g[j], mrow[512 + j], last);
+  }
+  lds_order();
+#pragma unroll
+  for (int bq = 0; bq < 8; ++bq) {
+    double sacc = 0.0;
+#pragma unroll
+    for (int j = 0; j < NG_F; ++j) sacc = fma(g[j], m[bq + j], sacc);
+    row[8 * lane + bq] = sacc;
+  }
+  if (lane == 0) row[512] = last;
+}
+
 // ---- noise profile ----------------------------------------------------------------------------
 // float32 like the reference: librosa.load gives float32, so stft -> complex64, |X| (hypotf),
 // square, 10 log10(max(1e-40, .)) in float32; the global max / top_db clamp and the per-bin
@@ -553,6 +739,24 @@ hipError_t nr_gate_launch(const NrArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(nr_stft_kernel, dim3(frames), dim3(NT), 0, s, a);
   hipLaunchKernelGGL(nr_gmax_kernel, dim3((unsigned)a.n_items), dim3(NT), 0, s, a);
   hipLaunchKernelGGL(nr_rows_kernel, dim3(frames), dim3(NT), 0, s, a);
+  hipLaunchKernelGGL(nr_gate_kernel, dim3(frames), dim3(NT), 0, s, a);
+  const int64_t tot = a.n_items * a.keep_len;
+  hipLaunchKernelGGL(nr_ola_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+double nr_ns_coefficient(double time_constant_s, int sr) {
+  const double t_frames = time_constant_s * sr / HOP;
+  return (std::sqrt(1.0 + 4.0 * t_frames * t_frames) - 1.0) / (2.0 * t_frames * t_frames);
+}
+
+hipError_t nr_ns_gate_launch(const NrArgs& a, const NrNsParams& p, hipStream_t s) {
+  if (a.n_items <= 0) return hipSuccess;
+  const int64_t total = a.n_items * a.t_n;
+  const unsigned frames = (unsigned)((total + NXCD - 1) / NXCD * NXCD);   // frame_of_block
+  hipLaunchKernelGGL(nr_ns_stft_kernel, dim3(frames), dim3(NT), 0, s, a);
+  hipLaunchKernelGGL(nr_ns_smooth_kernel, dim3((NB + NT - 1) / NT, (unsigned)a.n_items), dim3(NT), 0, s, a, p);
+  hipLaunchKernelGGL(nr_ns_rows_kernel, dim3(frames), dim3(NT), 0, s, a);
   hipLaunchKernelGGL(nr_gate_kernel, dim3(frames), dim3(NT), 0, s, a);
   const int64_t tot = a.n_items * a.keep_len;
   hipLaunchKernelGGL(nr_ola_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a);

@@ -308,9 +308,10 @@ int od_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t strid
                        int32_t clip_len, bool gated, int32_t nr_passes, float ssim_threshold,
                        float* probs, int32_t* argmax, uint8_t* silent, float* ssim, uint32_t flags) {
   const char* bad = bad_pcm_args(pcm, n, stride, lens, clip_len) ? "bad pcm args" : nullptr;
+  const bool ns = flags & MMLA_NR_NONSTATIONARY;   // the passes run the non-stationary gate: no bank
   if (c && !bad && gated) {
     if (nr_passes < 0) bad = "nr_passes < 0";
-    else if (nr_passes > 0 && !c->nr_ready) bad = "nr_passes > 0: mmla_nr_set_noise must be called first";
+    else if (nr_passes > 0 && !ns && !c->nr_ready) bad = "nr_passes > 0: mmla_nr_set_noise must be called first";
   }
   return clip_call(c, NET_OD, n, flags, bad, [&](int64_t c0, int64_t cnt, bool dev) -> int {
     Pcm p;
@@ -361,7 +362,7 @@ int od_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t strid
         for (int k = 0; k < nr_passes; ++k) {
           // a pass re-uses the gate's item table and scratch: the one before it has drained
           if (k) HIPCHK(c, hipStreamSynchronize(c->stream));
-          CHK(nr_reduce_dev(c, y0, cnt, D, D, y1));
+          CHK(nr_reduce_dev(c, y0, cnt, D, D, y1, nullptr, ns));
           const bool last = k == nr_passes - 1;
           LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * (last ? 6 : 8),
                  requant_launch(y1, p.lens, D, cnt, last ? nullptr : y0, last ? yq : nullptr, c->stream));
@@ -447,6 +448,7 @@ struct Conditioner {
   int64_t ips;
   int16_t* out_pcm;    // nullable
   int32_t* kept_len;   // nullable
+  bool ns = false;     // MMLA_NR_NONSTATIONARY: the passes need no bank and read no profile
   int64_t snap_c0 = -1, snap_streams = 0;
   const int16_t* q = nullptr;      // device results of the last run()
   const int32_t* kept = nullptr;
@@ -456,12 +458,12 @@ struct Conditioner {
     if (clip_len < 1 || clip_len > 600000) return "clip_len must be in [1, 600000] (one gate chunk)";
     if (n > 1 && stride < clip_len) return "clip_stride < clip_len";
     if (nr_passes < 0) return "nr_passes < 0";
-    if (nr_passes > 0 && !c->nr_ready) return "nr_passes > 0: mmla_nr_set_noise(_bank) must be called first";
+    if (nr_passes > 0 && !ns && !c->nr_ready) return "nr_passes > 0: mmla_nr_set_noise(_bank) must be called first";
     if (ips < 1 || n % ips) return "n_clips is not a multiple of items_per_stream";
     if (silence_remove && (!c->vad_state || c->vad_streams != n / ips))
       return "silence_remove: mmla_vad_reset must have created n_clips / items_per_stream streams";
     // device-pointer profile indices cannot be seen here: the kernels clamp them into the bank
-    if (profile && !dev && nr_passes > 0)
+    if (profile && !dev && nr_passes > 0 && !ns)
       for (int64_t i = 0; i < n; ++i)
         if (profile[i] < 0 || profile[i] >= c->nr_profiles) return "profile index outside the bank";
     return nullptr;
@@ -487,13 +489,13 @@ struct Conditioner {
       CHK(ws_get(c, S_GATE_Y1, (size_t)cnt * D * sizeof(float), &py1));
       float *y0 = static_cast<float*>(py0), *y1 = static_cast<float*>(py1);
       const int32_t* dprof;
-      CHK(in_ptr(c, profile ? profile + c0 : nullptr, (size_t)cnt, dev, S_NR_PROF, &dprof));
+      CHK(in_ptr(c, profile && !ns ? profile + c0 : nullptr, (size_t)cnt, dev, S_NR_PROF, &dprof));
       LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * 6,
              pcm_f32_launch(p.p, p.stride, p.lens, D, cnt, y0, c->stream));
       for (int k = 0; k < nr_passes; ++k) {
         // a pass re-uses the gate's item table and scratch: the one before it has drained
         if (k) HIPCHK(c, hipStreamSynchronize(c->stream));
-        CHK(nr_reduce_dev(c, y0, cnt, D, D, y1, dprof));
+        CHK(nr_reduce_dev(c, y0, cnt, D, D, y1, dprof, ns));
         const bool last = k == nr_passes - 1;
         LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * (last ? 6 : 8),
                requant_launch(y1, p.lens, D, cnt, last ? nullptr : y0, last ? src : nullptr, c->stream));
@@ -731,7 +733,7 @@ int mmla_condition(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride, c
                    int32_t clip_len, const int32_t* profile, int32_t nr_passes, int32_t silence_remove,
                    int64_t items_per_stream, int16_t* out_pcm, int32_t* kept_len, uint32_t flags) {
   Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, items_per_stream,
-                 out_pcm, kept_len};
+                 out_pcm, kept_len, (flags & MMLA_NR_NONSTATIONARY) != 0};
   return condition_call(c, cd, flags);
 }
 
@@ -742,7 +744,7 @@ int mmla_od_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, int
                                  uint8_t* silent, uint32_t flags) {
   if (!c) return MMLA_E_INVALID;
   Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, items_per_stream,
-                 out_pcm, kept_len};
+                 out_pcm, kept_len, (flags & MMLA_NR_NONSTATIONARY) != 0};
   const char* bad = cd.bad(c, flags & MMLA_DEVICE_PTR);
   if (!bad && cd.off()) {   // nothing to condition: mmla_od_pipeline itself, then the copies asked for
     CHK(od_pipeline_common(c, pcm, n, stride, lens, clip_len, false, 0, 0.0f, probs, argmax, silent,
@@ -762,7 +764,7 @@ int mmla_si_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, int
                                  uint8_t* silent, uint32_t flags) {
   if (!c) return MMLA_E_INVALID;
   Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, items_per_stream,
-                 out_pcm, kept_len};
+                 out_pcm, kept_len, (flags & MMLA_NR_NONSTATIONARY) != 0};
   const char* bad = cd.bad(c, flags & MMLA_DEVICE_PTR);
   if (!bad && cd.off()) {   // nothing to condition: mmla_si_pipeline itself, then the copies asked for
     CHK(mmla_si_pipeline(c, pcm, n, stride, lens, clip_len, probs, argmax, silent, flags));
@@ -788,7 +790,7 @@ int mmla_room_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, i
                                    uint8_t* silent, uint32_t flags) {
   if (!c) return MMLA_E_INVALID;
   Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, items_per_stream,
-                 out_pcm, kept_len};
+                 out_pcm, kept_len, (flags & MMLA_NR_NONSTATIONARY) != 0};
   const bool dev = flags & MMLA_DEVICE_PTR;
   if (const char* bad = cd.bad(c, dev)) return fail(c, MMLA_E_INVALID, "%s", bad);
   if (!c->od_loaded) return fail(c, MMLA_E_NOWEIGHTS, "OD weights not loaded");

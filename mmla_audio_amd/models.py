@@ -66,12 +66,17 @@ class _Model:
         ips = int(items_per_stream)
         if ips < 1 or n % ips:
             raise ValueError(f'{n} clips are not whole streams of {ips}')
+        ns = noise is None      # no ambient-noise clips: the non-stationary gate, no bank
         one = isinstance(noise, np.ndarray) and noise.ndim == 1
-        noises = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in ([noise] if one else noise)]
+        noises = [] if ns else [np.ascontiguousarray(x, dtype=np.float32).ravel()
+                                for x in ([noise] if one else noise)]
         if mic is None:     # the clip's stream is its microphone
-            mic = np.zeros(n, np.int32) if len(noises) == 1 else np.arange(n, dtype=np.int32) // ips
+            mic = np.zeros(n, np.int32) if len(noises) <= 1 else np.arange(n, dtype=np.int32) // ips
         mic = np.ascontiguousarray(mic, dtype=np.int32)
-        if passes > 0:
+        if ns:
+            if mic.shape != (n,):
+                raise ValueError(f'mic must hold one entry per clip, got shape {mic.shape}')
+        elif passes > 0:
             if mic.shape != (n,) or (n and (mic.min() < 0 or mic.max() >= len(noises))):
                 raise ValueError(f'mic must hold one index into the {len(noises)} noise clips per clip')
             noisereduce._set_noise_bank(self.ctx, noises, 16000)
@@ -82,7 +87,7 @@ class _Model:
             if reset_vad or getattr(self.ctx, 'vad_owner', None) != tag:
                 self.ctx.vad_reset(n // ips, vad_mode)
                 self.ctx.vad_owner = tag
-        return call(pcm, lens, mic, passes, silence_remove, ips)
+        return call(pcm, lens, mic, passes, silence_remove, ips, nonstationary=ns)
 
 
 class OverlapDetectionModel(_Model):
@@ -106,19 +111,22 @@ class OverlapDetectionModel(_Model):
         self._ensure_loaded()
         return self.ctx.od_pipeline(pcm, lens)
 
-    def predict_wavs_gated(self, pcm, noise, lens=None, passes=4, threshold=0.3):
+    def predict_wavs_gated(self, pcm, noise=None, lens=None, passes=4, threshold=0.3):
         """predict_wavs with the edge loop's silent check (record_on_pi.py:103-124): every clip is
         denoised `passes` times against the float32 noise clip `noise` (16 kHz), a clip whose feature
         image has an SSIM below `threshold` with its denoised image is 'silent', and the network reads
-        the denoised image -> (probs [N,2], argmax [N] (-1 = 'silent'), silent [N], ssim [N])."""
+        the denoised image -> (probs [N,2], argmax [N] (-1 = 'silent'), silent [N], ssim [N]).
+        noise=None: the passes run the non-stationary gate, which needs no noise clip."""
         from . import noisereduce
         self._ensure_loaded()
+        if noise is None:
+            return self.ctx.od_pipeline_gated(pcm, lens, passes, threshold, nonstationary=True)
         if passes > 0:
             yn = np.ascontiguousarray(noise, dtype=np.float32).ravel()
             noisereduce._set_noise(self.ctx, yn, 16000)
         return self.ctx.od_pipeline_gated(pcm, lens, passes, threshold)
 
-    def predict_wavs_conditioned(self, pcm, noise, mic=None, lens=None, passes=1, silence_remove=True,
+    def predict_wavs_conditioned(self, pcm, noise=None, mic=None, lens=None, passes=1, silence_remove=True,
                                  items_per_stream=1, vad_mode=3, reset_vad=False):
         """predict_wavs behind the PC loop's save_wave_file(noise_reduce=True, silence_remove=True)
         (record_on_pc.py:141-154,200-226) for a room of microphones: clip c is denoised `passes` times
@@ -129,7 +137,8 @@ class OverlapDetectionModel(_Model):
         the mode changes, and keep their state across calls otherwise; reset_vad=True starts afresh),
         and a clip with fewer than 4000 samples left is 'silent' -> (probs [N,2], argmax [N] (-1 =
         'silent'), silent [N], kept_len [N]).  The bank of profiles is rebuilt only when a noise clip
-        changes."""
+        changes.  noise=None: the passes run the non-stationary gate (the context's nr_set_nonstationary
+        parameters), no bank is built and `mic` is only checked for its shape."""
         return self._predict_conditioned(self.ctx.od_pipeline_conditioned, pcm, noise, mic, lens, passes,
                                          silence_remove, items_per_stream, vad_mode, reset_vad)
 
@@ -154,7 +163,7 @@ class SpeakerIdModel(_Model):
         self._ensure_loaded()
         return self.ctx.si_pipeline(pcm, lens)
 
-    def predict_wavs_conditioned(self, pcm, noise, mic=None, lens=None, passes=1, silence_remove=True,
+    def predict_wavs_conditioned(self, pcm, noise=None, mic=None, lens=None, passes=1, silence_remove=True,
                                  items_per_stream=1, vad_mode=3, reset_vad=False):
         """predict_wavs behind save_wave_file(noise_reduce=True, silence_remove=True) (SI
         record_on_pc.py:117-134,178-205, record_on_pi.py:101-127,228-240); arguments and the returned

@@ -24,9 +24,10 @@ class Room:
     detectors' aggressiveness.  The noise bank and the detectors are the context's, owned the way
     ``predict_wavs_conditioned`` owns them: the bank is rebuilt only when a noise clip changes, the
     detectors are created on the first tick or when the stream count or the mode changes and keep their
-    state from tick to tick otherwise."""
+    state from tick to tick otherwise.  ``noises=None``: a room without ambient-noise recordings, gated by
+    the non-stationary gate (no bank; the context's nr_set_nonstationary parameters)."""
 
-    def __init__(self, od_model, si_model, noises, vad_mode=3):
+    def __init__(self, od_model, si_model, noises=None, vad_mode=3):
         if od_model.ctx is not si_model.ctx:
             raise ValueError('the OD and the SI model of a Room must share one context '
                              '(create them with the same device=Context)')
@@ -45,8 +46,9 @@ class Room:
         clips, zeros behind kept_len."""
         self.si._ensure_loaded()
 
-        def call(x, ln, m, p, sr, ips):
-            return self.ctx.room_pipeline_conditioned(x, ln, m, p, sr, ips, return_pcm=return_pcm)
+        def call(x, ln, m, p, sr, ips, nonstationary=False):
+            return self.ctx.room_pipeline_conditioned(x, ln, m, p, sr, ips, return_pcm=return_pcm,
+                                                      nonstationary=nonstationary)
 
         return RoomResult(*self.od._predict_conditioned(call, pcm, self.noises, mic, lens, passes,
                                                         silence_remove, items_per_stream, self.vad_mode,
