@@ -17,7 +17,8 @@
  *   - PCM is 16 kHz mono int16; clip c starts at pcm + c * clip_stride (in samples) and has
  *     lens[c] valid samples (lens == NULL: every clip has clip_len samples).  Without lens the
  *     stride may be smaller than clip_len: overlapping windows of one signal (the offline
- *     segmentation of overlap_detection_post_processing.py:23-85 with step < window).
+ *     segmentation of overlap_detection_post_processing.py:23-85 with step < window).  Only the
+ *     mmla_capture_* and mmla_*_pipeline_capture calls take another rate or interleaved channels.
  */
 #ifndef MMLA_H_
 #define MMLA_H_
@@ -475,6 +476,77 @@ int mmla_ratecv(mmla_ctx* ctx, const int16_t* pcm, int64_t n_frames, int32_t nch
 int mmla_resample_sinc(mmla_ctx* ctx, const float* x, int64_t n, int32_t sr_orig, int32_t sr_new,
                        const double* half_window, int64_t window_len, int32_t num_table, float* y,
                        int64_t n_out, uint32_t flags);
+
+/*
+ * A room that ticks at its microphones' capture rate: streaming conversion of interleaved 16-bit capture
+ * (USB microphones and conference arrays: 44.1 / 48 kHz, usually stereo) to the 16 kHz mono every other
+ * call takes, with audioop's ratecv state carried per stream from clip to clip.  Replaces, per clip and
+ * microphone on the host: np.fromstring(data, np.int16)[0::2] (SpeakerIdentification/scripts/
+ * record_on_pi.py:223), pydub's set_channels(1) = audioop.tomono(data, 2, 0.5, 0.5) and set_frame_rate(16000)
+ * = audioop.ratecv (overlap_detection_post_processing.py:120-121).  Bit-identical to CPython's audioop.
+ *
+ * The format: rate 1..384000 Hz, channels 1..8, channel = k >= 0 picks channel k of every frame,
+ * MMLA_CAPTURE_MEAN (two channels only) is floor(0.5 l + 0.5 r).  The mono signal is formed first and
+ * goes through audioop.ratecv(fragment, 2, 1, rate, 16000, state).  With ir = rate / g, or = 16000 / g,
+ * g = gcd(rate, 16000), a stream's state is (d, prev): audioop's phase counter, -max(ir, or) <= d < 0
+ * (fresh: -or), and the last mono input sample (fresh: 0).  A fragment of n frames x entered with
+ * (d0, prev) gives m = floor((n or + d0) / ir) + 1 samples (0 when n or + d0 < 0); sample j comes from
+ * frame k = ceil((j ir - d0) / or) - 1 at phase d = d0 + (k + 1) or - j ir:
+ *   out[j] = ((int)(((double)p * d + (double)c * (or - d)) / (double)or)) >> 16,
+ *   p = (k > 0 ? x[k - 1] : prev) * 65536, c = x[k] * 65536 (no fp contraction; the cast truncates, the
+ *   shift floors), and leaves (d0 + n or - m ir, n > 0 ? x[n - 1] : prev).  n = 0 changes nothing.
+ *
+ * mmla_capture_reset: sets the context's format and gives each of n_streams streams a fresh state (waits
+ *   for the context stream).  MMLA_E_INVALID: a rate, channel count or channel out of range,
+ *   MMLA_CAPTURE_MEAN with channels != 2.
+ * mmla_capture_convert: the conversion alone.  Clip c = pcm + c * clip_stride (int16 samples) holds
+ *   frames[c] frames (nullable: clip_frames) of `channels` samples; stream s owns clips
+ *   [s * items_per_stream, (s + 1) * items_per_stream), in order.  out [n_clips][out_stride] int16 gets
+ *   out_lens[c] samples per clip, then zeros up to out_clip_len = (clip_frames * or - 1) / ir + 1, the
+ *   longest a clip can become (out_stride >= out_clip_len).  Every stream's state advances once.
+ *   With MMLA_CAPTURE_FRESH the conversion starts from fresh states instead and leaves the context's
+ *   alone, for any stream count: a whole recording (ambient noise, registration) cut into the clips of
+ *   one stream.  Host-pointer calls stage the raw capture on the device in pieces of whole streams
+ *   (64 MiB, or one stream), not all at once.
+ * mmla_capture_state: d [n_streams] and prev [n_streams] (host, each nullable) of the current states
+ *   (waits for the context stream): for tests and for checkpointing a room.
+ * mmla_{od,si,room}_pipeline_capture: the arguments of the _conditioned calls with frames / clip_frames
+ *   in capture frames in place of lens / clip_len: the conversion of all clips, once, then the
+ *   conditioned pipeline on the converted clips with lens = out_lens and clip_len = out_clip_len (so
+ *   out_pcm is [n_clips, out_clip_len] and kept_len counts 16 kHz samples).  The converted audio stays
+ *   on the device.  The conversion runs in front of the micro-batching: every converter state advances
+ *   exactly once per clip whatever the micro-batch size, and a range-guard, split-BiLSTM or
+ *   allocation-failure re-run re-reads the clips already converted.  MMLA_NR_NONSTATIONARY and
+ *   MMLA_DEVICE_PTR mean what they mean for the _conditioned calls (frames is then a device pointer).
+ * MMLA_E_INVALID (conversion and pipelines; every check, the weights' and the bank's included, comes
+ *   before any state moves, and a call that fails a check leaves every state as it was): no
+ *   mmla_capture_reset for n_clips / items_per_stream streams, n_clips not a multiple of
+ *   items_per_stream, clip_frames < 1, clip_stride < clip_frames * channels, a host frames[c] outside
+ *   [0, clip_frames] (device pointers: clamped by the kernels, the convention of the VAD's lens),
+ *   out_clip_len > 600000, and for the pipelines everything mmla_condition rejects.
+ */
+#define MMLA_CAPTURE_MEAN (-1)
+#define MMLA_CAPTURE_FRESH 0x4u /* mmla_capture_convert: from fresh states, the context's untouched */
+int mmla_capture_reset(mmla_ctx* ctx, int64_t n_streams, int32_t rate, int32_t channels, int32_t channel);
+int mmla_capture_convert(mmla_ctx* ctx, const int16_t* pcm, int64_t n_clips, int64_t clip_stride,
+                         const int32_t* frames, int32_t clip_frames, int64_t items_per_stream, int16_t* out,
+                         int64_t out_stride, int32_t* out_lens, uint32_t flags);
+int mmla_capture_state(mmla_ctx* ctx, int32_t* d, int32_t* prev);
+int mmla_od_pipeline_capture(mmla_ctx* ctx, const int16_t* pcm, int64_t n_clips, int64_t clip_stride,
+                             const int32_t* frames, int32_t clip_frames, const int32_t* profile,
+                             int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
+                             int16_t* out_pcm, int32_t* kept_len, float* probs, int32_t* argmax,
+                             uint8_t* silent, uint32_t flags);
+int mmla_si_pipeline_capture(mmla_ctx* ctx, const int16_t* pcm, int64_t n_clips, int64_t clip_stride,
+                             const int32_t* frames, int32_t clip_frames, const int32_t* profile,
+                             int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
+                             int16_t* out_pcm, int32_t* kept_len, float* probs, int32_t* argmax,
+                             uint8_t* silent, uint32_t flags);
+int mmla_room_pipeline_capture(mmla_ctx* ctx, const int16_t* pcm, int64_t n_clips, int64_t clip_stride,
+                               const int32_t* frames, int32_t clip_frames, const int32_t* profile,
+                               int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
+                               int16_t* out_pcm, int32_t* kept_len, float* od_probs, int32_t* od_argmax,
+                               float* si_probs, int32_t* si_argmax, uint8_t* silent, uint32_t flags);
 
 /*
  * Kernel tracing (replaces the reference's time.time() prints, overlap_detector_run.py:49-104).

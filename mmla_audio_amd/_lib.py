@@ -16,6 +16,8 @@ LIB_PATH = os.path.join(_HERE, 'libmmla.so')
 MMLA_OK = 0
 MMLA_DEVICE_PTR = 0x1
 MMLA_NR_NONSTATIONARY = 0x2
+MMLA_CAPTURE_FRESH = 0x4
+MMLA_CAPTURE_MEAN = -1
 MODEL_OD, MODEL_SI = 0, 1
 HEAD_SOFTMAX, HEAD_SIGMOID = 0, 1
 PREC_F32, PREC_F16X3 = 0, 1
@@ -48,6 +50,15 @@ SIGNATURES = {
                                      _P, _P, _P, _U32],
     'mmla_room_pipeline_conditioned': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P,
                                        _P, _P, _P, _P, _P, _U32],
+    'mmla_capture_reset': [_P, _I64, _I32, _I32, _I32],
+    'mmla_capture_convert': [_P, _P, _I64, _I64, _P, _I32, _I64, _P, _I64, _P, _U32],
+    'mmla_capture_state': [_P, _P, _P],
+    'mmla_od_pipeline_capture': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P,
+                                 _P, _P, _P, _U32],
+    'mmla_si_pipeline_capture': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P,
+                                 _P, _P, _P, _U32],
+    'mmla_room_pipeline_capture': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P,
+                                   _P, _P, _P, _P, _P, _U32],
     'mmla_debug_vad_path': [_P, _I64, ctypes.POINTER(_I32)],
     'mmla_abi_version': [],
     'mmla_crc32c': [_P, _I64, ctypes.POINTER(_U32)],
@@ -695,6 +706,155 @@ class Context:
             'mmla_room_pipeline_conditioned')
         res = (od_probs, od_am, si_probs, si_am, silent.astype(bool), kept)
         return res + (out,) if return_pcm else res
+
+    # -- a room's capture format: streaming conversion to 16 kHz mono in front of the pipelines ----
+    def capture_reset(self, n_streams, rate, channels=1, channel=0):
+        """The capture format of every later capture call (rate in Hz, interleaved channels, channel k
+        or MMLA_CAPTURE_MEAN for stereo) and n_streams fresh audioop.ratecv states."""
+        self._check(self.lib.mmla_capture_reset(self.h, int(n_streams), int(rate), int(channels),
+                                                int(channel)), 'mmla_capture_reset')
+        self.capture_format = (int(rate), int(channels), int(channel))
+        self.capture_streams = int(n_streams)
+
+    @staticmethod
+    def capture_out_len(clip_frames, rate):
+        """the longest a clip of clip_frames capture frames can become at 16 kHz (the row width of the
+        converted clips)"""
+        from math import gcd
+        g = gcd(int(rate), 16000)
+        return (int(clip_frames) * (16000 // g) - 1) // (int(rate) // g) + 1
+
+    def _capture_pcm(self, pcm, frames):
+        """-> (contiguous int16 [n, clip_frames * channels], frames int32 [n] or None, clip_frames)"""
+        fmt = getattr(self, 'capture_format', None)
+        if fmt is None:
+            raise MmlaError('capture_reset must be called first', -1)
+        ch = fmt[1]
+        if isinstance(pcm, (list, tuple)):
+            for p in pcm:
+                if len(p) % ch:
+                    raise MmlaError(f'{len(p)} samples are not whole frames of {ch} channels', -1)
+        a, ln, width = self._pcm(pcm, None)
+        if isinstance(pcm, (list, tuple)):
+            if width % ch:      # (only the placeholder width of a list of empty clips)
+                a = np.zeros((a.shape[0], ch), np.int16)
+            fr = ln // ch
+        else:
+            if a.shape[1] % ch:
+                raise MmlaError(f'rows of {a.shape[1]} samples are not whole frames of {ch} channels', -1)
+            fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32)
+            if fr is not None and fr.shape != (a.shape[0],):
+                raise ValueError(f'frames {fr.shape}: expected one count per clip ({a.shape[0]})')
+        return a, fr, a.shape[1] // ch
+
+    def capture_convert(self, pcm, frames=None, items_per_stream=1, fresh=False):
+        """Interleaved capture int16 [n, clip_frames * channels] (or a list of clips) with frames[c]
+        valid frames -> (int16 [n, out_clip_len] at 16 kHz mono, zeros behind out_lens; out_lens [n]).
+        Stream s owns clips [s * items_per_stream, (s + 1) * items_per_stream) and its audioop state
+        carries from clip to clip and from call to call.  fresh=True: from fresh states instead, the
+        context's left alone."""
+        a, fr, cf = self._capture_pcm(pcm, frames)
+        n = a.shape[0]
+        ocl = self.capture_out_len(max(cf, 1), self.capture_format[0])
+        out = np.empty((n, ocl), np.int16)
+        olen = np.empty(n, np.int32)
+        self._check(self.lib.mmla_capture_convert(
+            self.h, _ptr(a), n, a.shape[1], _ptr(fr), cf, int(items_per_stream), _ptr(out), ocl,
+            _ptr(olen), MMLA_CAPTURE_FRESH if fresh else 0), 'mmla_capture_convert')
+        return out, olen
+
+    def capture_convert_dev(self, pcm, n, stride, clip_frames, out, out_stride, out_lens,
+                            items_per_stream=1, frames=0, fresh=False):
+        self._check(self.lib.mmla_capture_convert(
+            self.h, pcm, n, stride, frames or None, clip_frames, int(items_per_stream), out, out_stride,
+            out_lens, MMLA_DEVICE_PTR | (MMLA_CAPTURE_FRESH if fresh else 0)), 'mmla_capture_convert(dev)')
+
+    def capture_state(self):
+        """-> (d int32 [n_streams], prev int32 [n_streams]): audioop's phase counter and the last mono
+        input sample of every stream"""
+        n = getattr(self, 'capture_streams', 0)
+        d = np.zeros(n, np.int32)
+        prev = np.zeros(n, np.int32)
+        self._check(self.lib.mmla_capture_state(self.h, _ptr(d) if n else None, _ptr(prev) if n else None),
+                    'mmla_capture_state')
+        return d, prev
+
+    def _capture_pipeline(self, fn, what, n_classes, pcm, frames, profile, passes, silence_remove,
+                          items_per_stream, return_pcm, nonstationary):
+        """the shared body of {od,si,room}_pipeline_capture; n_classes: one width per network"""
+        a, fr, cf = self._capture_pcm(pcm, frames)
+        n = a.shape[0]
+        pr = self._profile(profile, n)
+        ocl = self.capture_out_len(max(cf, 1), self.capture_format[0])
+        out = np.empty((n, ocl), np.int16) if return_pcm else None
+        kept = np.empty(n, np.int32)
+        nets = []
+        for k in n_classes:
+            nets += [np.empty((n, k), np.float32), np.empty(n, np.int32)]
+        silent = np.empty(n, np.uint8)
+        self._check(fn(self.h, _ptr(a), n, a.shape[1], _ptr(fr), cf, _ptr(pr), int(passes),
+                       int(bool(silence_remove)), int(items_per_stream), _ptr(out), _ptr(kept),
+                       *[_ptr(x) for x in nets], _ptr(silent), _ns(nonstationary)), what)
+        res = tuple(nets) + (silent.astype(bool), kept)
+        return res + (out,) if return_pcm else res
+
+    def od_pipeline_capture(self, pcm, frames=None, profile=None, passes=1, silence_remove=True,
+                            items_per_stream=1, return_pcm=False, nonstationary=False):
+        """od_pipeline_conditioned on interleaved capture in the capture_reset format: capture_convert
+        of all clips, then the conditioned pipeline on the converted clips, which stay on the device ->
+        (probs [n,2], argmax [n], silent [n] bool, kept_len [n] at 16 kHz); return_pcm adds the
+        conditioned clips [n, out_clip_len]."""
+        return self._capture_pipeline(self.lib.mmla_od_pipeline_capture, 'mmla_od_pipeline_capture', (2,),
+                                      pcm, frames, profile, passes, silence_remove, items_per_stream,
+                                      return_pcm, nonstationary)
+
+    def si_pipeline_capture(self, pcm, frames=None, profile=None, passes=1, silence_remove=True,
+                            items_per_stream=1, return_pcm=False, nonstationary=False):
+        """si_pipeline_conditioned on interleaved capture -> (probs [n,K], argmax, silent, kept_len)"""
+        return self._capture_pipeline(self.lib.mmla_si_pipeline_capture, 'mmla_si_pipeline_capture',
+                                      (self.si_classes or 0,), pcm, frames, profile, passes,
+                                      silence_remove, items_per_stream, return_pcm, nonstationary)
+
+    def room_pipeline_capture(self, pcm, frames=None, profile=None, passes=1, silence_remove=True,
+                              items_per_stream=1, return_pcm=False, nonstationary=False):
+        """room_pipeline_conditioned on interleaved capture -> (od_probs [n,2], od_argmax [n], si_probs
+        [n,K], si_argmax [n], silent [n] bool, kept_len [n]); return_pcm adds the conditioned clips."""
+        return self._capture_pipeline(self.lib.mmla_room_pipeline_capture, 'mmla_room_pipeline_capture',
+                                      (2, self.si_classes or 0), pcm, frames, profile, passes,
+                                      silence_remove, items_per_stream, return_pcm, nonstationary)
+
+    def _capture_pipeline_dev(self, fn, what, pcm, n, stride, clip_frames, passes, silence_remove,
+                              items_per_stream, nets, silent, out_pcm, kept_len, frames, profile,
+                              nonstationary):
+        self._check(fn(self.h, pcm, n, stride, frames or None, clip_frames, profile or None, int(passes),
+                       int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
+                       *[x or None for x in nets], silent or None,
+                       MMLA_DEVICE_PTR | _ns(nonstationary)), what)
+
+    def od_pipeline_capture_dev(self, pcm, n, stride, clip_frames, passes=1, silence_remove=True,
+                                items_per_stream=1, probs=0, argmax=0, silent=0, out_pcm=0, kept_len=0,
+                                frames=0, profile=0, nonstationary=False):
+        """synchronises the context stream internally when passes > 0 (see mmla.h)"""
+        self._capture_pipeline_dev(self.lib.mmla_od_pipeline_capture, 'mmla_od_pipeline_capture(dev)', pcm,
+                                   n, stride, clip_frames, passes, silence_remove, items_per_stream,
+                                   (probs, argmax), silent, out_pcm, kept_len, frames, profile, nonstationary)
+
+    def si_pipeline_capture_dev(self, pcm, n, stride, clip_frames, passes=1, silence_remove=True,
+                                items_per_stream=1, probs=0, argmax=0, silent=0, out_pcm=0, kept_len=0,
+                                frames=0, profile=0, nonstationary=False):
+        """synchronises the context stream internally when passes > 0 (see mmla.h)"""
+        self._capture_pipeline_dev(self.lib.mmla_si_pipeline_capture, 'mmla_si_pipeline_capture(dev)', pcm,
+                                   n, stride, clip_frames, passes, silence_remove, items_per_stream,
+                                   (probs, argmax), silent, out_pcm, kept_len, frames, profile, nonstationary)
+
+    def room_pipeline_capture_dev(self, pcm, n, stride, clip_frames, passes=1, silence_remove=True,
+                                  items_per_stream=1, od_probs=0, od_argmax=0, si_probs=0, si_argmax=0,
+                                  silent=0, out_pcm=0, kept_len=0, frames=0, profile=0, nonstationary=False):
+        """synchronises the context stream internally when passes > 0 (see mmla.h)"""
+        self._capture_pipeline_dev(self.lib.mmla_room_pipeline_capture, 'mmla_room_pipeline_capture(dev)',
+                                   pcm, n, stride, clip_frames, passes, silence_remove, items_per_stream,
+                                   (od_probs, od_argmax, si_probs, si_argmax), silent, out_pcm, kept_len,
+                                   frames, profile, nonstationary)
 
     def debug_vad_path(self, n_streams):
         """True when a detector call over n_streams streams runs the one-stream-per-wave kernel"""

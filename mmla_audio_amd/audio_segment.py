@@ -149,6 +149,18 @@ class AudioSegment:
         out = self.ctx.ratecv(self.data, self.channels, self.frame_rate, frame_rate)
         return self._spawn(out, frame_rate)
 
+    def set_channels(self, channels):
+        """pydub's set_channels(1) of stereo data: audioop.tomono(data, 2, 0.5, 0.5), i.e.
+        floor(0.5 l + 0.5 r) per frame (on the host: one pass over the samples)"""
+        if channels == self.channels:
+            return self
+        if channels != 1 or self.channels != 2:
+            raise ValueError(f'set_channels({channels}) of {self.channels}-channel data: only the '
+                             'stereo-to-mono downmix is built')
+        x = self.data.reshape(-1, 2).astype(np.float64)
+        mono = np.floor(0.5 * x[:, 0] + 0.5 * x[:, 1]).astype(np.int16)
+        return AudioSegment(mono, self.frame_rate, 1, self._ctx)
+
     @property
     def rms(self):
         """audioop.rms(data, 2): (unsigned int) sqrt(sum(x^2) / n) with a float64 running sum,

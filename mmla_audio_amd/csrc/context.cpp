@@ -285,6 +285,9 @@ int mmla_destroy(mmla_ctx* c) {
   if (c->nr_thresh) (void)hipFree(c->nr_thresh);
   if (c->range_dev) (void)hipFree(c->range_dev);
   if (c->vad_state) (void)hipFree(c->vad_state);
+  if (c->cap_state) (void)hipFree(c->cap_state);
+  for (void* p : c->cap_buf)
+    if (p) (void)hipFree(p);
   if (c->range_host) (void)hipHostFree(c->range_host);
   if (c->range_map) (void)hipHostFree(c->range_map);
   if (c->pin_out) (void)hipHostFree(c->pin_out);
@@ -359,7 +362,14 @@ int mmla_get_microbatch(mmla_ctx* c, int64_t* od_clips, int64_t* si_clips) {
 int mmla_release_workspace(mmla_ctx* c) {
   if (!c) return MMLA_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
-  return ws_release(c);
+  CHK(ws_release(c));   // (the stream has drained)
+  for (int i = 0; i < 5; ++i)   // the capture conversion's buffers; its states stay
+    if (c->cap_buf[i]) {
+      HIPCHK(c, hipFree(c->cap_buf[i]));
+      c->cap_buf[i] = nullptr;
+      c->cap_bytes[i] = 0;
+    }
+  return MMLA_OK;
 }
 
 int mmla_set_precision(mmla_ctx* c, int mode) {

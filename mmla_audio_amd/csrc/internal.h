@@ -187,6 +187,19 @@ struct mmla_ctx {
   // holds the states a conditioned micro-batch started from, for its re-runs (pipeline.cpp)
   VadState* vad_state = nullptr;
   int64_t vad_streams = 0;
+  // mmla_capture_reset: the capture format (cap_ir / cap_or: the rate and 16000 over their gcd) and
+  // audioop's ratecv state (d, prev) per stream (device, [2][cap_streams][2] int32).  A call reads half
+  // cap_cur and writes the other one, which becomes current once every launch of the call is enqueued:
+  // a call that fails on the way leaves the states it found
+  int32_t* cap_state = nullptr;
+  int cap_cur = 0;
+  int64_t cap_streams = 0;
+  int32_t cap_rate = 0, cap_channels = 0, cap_channel = 0, cap_ir = 0, cap_or = 0;
+  // the conversion's buffers (mmla::CapBuf).  Not workspace slots: an allocation failure in the
+  // conditioned micro-batches behind the conversion frees every slot (ws_release), and the re-run must
+  // find the converted clips
+  void* cap_buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  size_t cap_bytes[5] = {0, 0, 0, 0, 0};
   // noise gate (nr.hip): tables + the bank of noise profiles' thresholds [nr_profiles][513]
   NrTables* nr_tables = nullptr;
   float* nr_thresh = nullptr;
@@ -240,6 +253,10 @@ enum Slot {
   S_NR_PROF, S_COND_Q, S_COND_KEPT,       // profile indices of the gate; mmla_condition's outputs
   S_ROOM_P, S_ROOM_A                      // mmla_room_pipeline_conditioned: the SI outputs' staging
 };
+
+// mmla_ctx::cap_buf: staged raw capture, host frames, per-clip entry (d0, prev), converted clips and
+// their lengths
+enum CapBuf { CB_RAW = 0, CB_FRAMES, CB_ITEM, CB_OUT, CB_LENS };
 
 int ws_get(mmla_ctx* c, int slot, size_t bytes, void** out);
 int ws_release(mmla_ctx* c);   // free every workspace slot (after the stream drains)

@@ -2,9 +2,11 @@
 // range guard around the front-end kernels and the network runners (net_runners.cpp).
 #include <algorithm>
 #include <cmath>
+#include <numeric>
 #include <type_traits>
 
 #include "internal.h"
+#include "resample.h"
 
 using namespace mmla;
 
@@ -306,7 +308,8 @@ int od_forward_common(mmla_ctx* c, const float* x_f32, const uint8_t* x_u8, int6
 // (nr_passes gate + PCM_16 round trips, the second image, their SSIM) in front of the network
 int od_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride, const int32_t* lens,
                        int32_t clip_len, bool gated, int32_t nr_passes, float ssim_threshold,
-                       float* probs, int32_t* argmax, uint8_t* silent, float* ssim, uint32_t flags) {
+                       float* probs, int32_t* argmax, uint8_t* silent, float* ssim, uint32_t flags,
+                       bool pcm_dev = false) {
   const char* bad = bad_pcm_args(pcm, n, stride, lens, clip_len) ? "bad pcm args" : nullptr;
   const bool ns = flags & MMLA_NR_NONSTATIONARY;   // the passes run the non-stationary gate: no bank
   if (c && !bad && gated) {
@@ -315,7 +318,7 @@ int od_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t strid
   }
   return clip_call(c, NET_OD, n, flags, bad, [&](int64_t c0, int64_t cnt, bool dev) -> int {
     Pcm p;
-    CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, MMLA_OD_CLIP, dev, &p));
+    CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, MMLA_OD_CLIP, dev || pcm_dev, &p));
     void* pimg = nullptr;
     CHK(ws_get(c, S_IMG, cnt * OD_IMG, &pimg));
     OdFeArgs a{};
@@ -449,6 +452,9 @@ struct Conditioner {
   int16_t* out_pcm;    // nullable
   int32_t* kept_len;   // nullable
   bool ns = false;     // MMLA_NR_NONSTATIONARY: the passes need no bank and read no profile
+  // pcm and lens are device pointers whatever the call's flags say (the capture calls: the converted
+  // clips never leave the device); profile and the outputs follow the flags
+  bool pcm_dev = false;
   int64_t snap_c0 = -1, snap_streams = 0;
   const int16_t* q = nullptr;      // device results of the last run()
   const int32_t* kept = nullptr;
@@ -473,7 +479,7 @@ struct Conditioner {
   int run(mmla_ctx* c, int64_t c0, int64_t cnt, bool dev) {
     const int D = clip_len;
     Pcm p;
-    CHK(stage_pcm(c, pcm, c0, cnt, n > 1 ? stride : (int64_t)D, lens, D, D, dev, &p));
+    CHK(stage_pcm(c, pcm, c0, cnt, n > 1 ? stride : (int64_t)D, lens, D, D, dev || pcm_dev, &p));
     void *py0 = nullptr, *py1 = nullptr, *pq = nullptr, *pk = nullptr;
     CHK(ws_get(c, S_COND_Q, (size_t)cnt * D * sizeof(int16_t), &pq));
     CHK(ws_get(c, S_COND_KEPT, (size_t)cnt * sizeof(int32_t), &pk));
@@ -585,6 +591,232 @@ int od_fe_net(mmla_ctx* c, const Conditioner& cd, int64_t c0, int64_t cnt, bool 
   CHK(copy_back(c, probs, c0 * 2, dp, cnt * 2, dev));
   CHK(copy_back(c, argmax, c0, da, cnt, dev));
   return copy_back(c, silent, c0, ds, cnt, dev);
+}
+
+int si_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride, const int32_t* lens,
+                       int32_t clip_len, float* probs, int32_t* argmax, uint8_t* silent, uint32_t flags,
+                       bool pcm_dev = false) {
+  return clip_call(c, NET_SI, n, flags, bad_pcm_args(pcm, n, stride, lens, clip_len) ? "bad pcm args" : nullptr,
+                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+    Pcm p;
+    CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, SI_NEED_SAMPLES, dev || pcm_dev, &p));
+    p.clip_len = lens ? 0 : clip_len;   // the true length decides T even if fewer samples are staged
+    return si_fe_net(c, p, c0, cnt, dev, probs, argmax, silent);
+  });
+}
+
+// ---- the conditioned pipelines on a Conditioner (mmla_*_pipeline_conditioned, _capture) ------------
+
+enum Which { W_OD, W_SI, W_ROOM };
+
+// the networks' outputs of the three calls: W_OD / W_SI use (probs, argmax), W_ROOM all four
+struct NetOut {
+  float* od_probs;
+  int32_t* od_argmax;
+  float* si_probs;
+  int32_t* si_argmax;
+  uint8_t* silent;
+};
+
+const char* missing_weights(const mmla_ctx* c, Which w) {
+  if (w != W_SI && !c->od_loaded) return "OD";
+  if (w != W_OD && !c->si_loaded) return "SI";
+  return nullptr;
+}
+
+// cd.bad() has passed and the weights are loaded
+int conditioned_body(mmla_ctx* c, Which w, Conditioner& cd, const NetOut& o, uint32_t flags) {
+  const bool dev = flags & MMLA_DEVICE_PTR;
+  if (cd.off()) {   // nothing to condition: the plain pipelines, then the copies asked for
+    if (w != W_SI)
+      CHK(od_pipeline_common(c, cd.pcm, cd.n, cd.stride, cd.lens, cd.clip_len, false, 0, 0.0f, o.od_probs,
+                             o.od_argmax, o.silent, nullptr, flags, cd.pcm_dev));
+    if (w != W_OD)
+      CHK(si_pipeline_common(c, cd.pcm, cd.n, cd.stride, cd.lens, cd.clip_len, o.si_probs, o.si_argmax,
+                             w == W_SI ? o.silent : nullptr, flags, cd.pcm_dev));
+    return cd.out_pcm || cd.kept_len ? condition_call(c, cd, flags) : MMLA_OK;
+  }
+  const int64_t granule = std::max<int64_t>(cd.ips, 1);
+  if (w == W_OD)
+    return clip_call(c, NET_OD, cd.n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev) -> int {
+      CHK(cd.run(c, c0, cnt, dev));
+      return od_fe_net(c, cd, c0, cnt, dev, o.od_probs, o.od_argmax, o.silent);
+    }, granule);
+  if (w == W_SI)
+    return clip_call(c, NET_SI, cd.n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev) -> int {
+      CHK(cd.run(c, c0, cnt, dev));
+      // the conditioned clips with lens = kept_len (a row holds clip_len samples, zeros behind kept_len)
+      const Pcm p{cd.q, cd.clip_len, cd.kept, 0};
+      return si_fe_net(c, p, c0, cnt, dev, o.si_probs, o.si_argmax, o.silent);
+    }, granule);
+  // Both networks on one conditioning: per micro-batch (whole streams, OD's cap) Conditioner::run once,
+  // then each network's front-end + net under its own range guard, reading the conditioned clips that
+  // stay in S_COND_Q / S_COND_KEPT.  A guard re-run repeats that network alone; an allocation failure
+  // repeats the micro-batch with fewer clips, the detectors restored by Conditioner::run's snapshot.
+  HIPCHK(c, hipSetDevice(c->device));
+  CHK(for_microbatches(c, true, cd.n, [&](int64_t c0, int64_t cnt) -> int {
+    CHK(cd.run(c, c0, cnt, dev));
+    CHK(guarded(c, dev, c->od_f32_only, [&]() -> int {
+      return od_fe_net(c, cd, c0, cnt, dev, o.od_probs, o.od_argmax, o.silent);
+    }));
+    CHK(guarded(c, dev, c->si_f32_only, [&]() -> int {
+      // the conditioned clips with lens = kept_len, as mmla_si_pipeline_conditioned reads them; its
+      // 'silent' (kept_len < 4000, the rule of OD's gate) stays in the workspace
+      const Pcm p{cd.q, cd.clip_len, cd.kept, 0};
+      return si_fe_net(c, p, c0, cnt, dev, o.si_probs, o.si_argmax, nullptr, S_ROOM_P, S_ROOM_A);
+    }));
+    if (!dev) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MMLA_OK;
+  }, granule));
+  return finish(c, dev);
+}
+
+int conditioned_call(mmla_ctx* c, Which w, Conditioner& cd, const NetOut& o, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  if (const char* bad = cd.bad(c, flags & MMLA_DEVICE_PTR)) return fail(c, MMLA_E_INVALID, "%s", bad);
+  if (const char* m = missing_weights(c, w)) return fail(c, MMLA_E_NOWEIGHTS, "%s weights not loaded", m);
+  return conditioned_body(c, w, cd, o, flags);
+}
+
+// ---- a room's capture format in front of the conditioned pipelines ----------------------------------
+
+// raw capture staged per piece of a host-pointer conversion (whole streams; one stream where a stream
+// is larger)
+constexpr size_t kCapStageBytes = 64u << 20;
+
+int cap_get(mmla_ctx* c, int which, size_t bytes, void** out) {
+  if (bytes < 256) bytes = 256;
+  if (c->cap_bytes[which] < bytes) {
+    if (c->cap_buf[which]) {
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      HIPCHK(c, hipFree(c->cap_buf[which]));
+      c->cap_buf[which] = nullptr;
+      c->cap_bytes[which] = 0;
+    }
+    if (hipMalloc(&c->cap_buf[which], bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      c->cap_buf[which] = nullptr;
+      return fail(c, MMLA_E_OOM, "hipMalloc(%zu) failed for capture buffer %d", bytes, which);
+    }
+    c->cap_bytes[which] = bytes;
+  }
+  *out = c->cap_buf[which];
+  return MMLA_OK;
+}
+
+// One conversion: interleaved capture clips -> 16 kHz mono.  fresh: from fresh states, the context's
+// left alone (a whole recording); else on the states mmla_capture_reset created, advanced once.
+struct Capture {
+  const int16_t* pcm;
+  int64_t n, stride;
+  const int32_t* frames;
+  int32_t clip_frames;
+  int64_t ips;
+  bool fresh;
+  int32_t out_clip_len = 0;
+
+  const char* bad(const mmla_ctx* c, bool dev) {
+    if (!c->cap_rate) return "mmla_capture_reset must be called first";
+    if (n < 0 || (n > 0 && !pcm)) return "bad capture pcm args";
+    if (clip_frames < 1) return "clip_frames < 1";
+    if (stride < (int64_t)clip_frames * c->cap_channels) return "clip_stride < clip_frames * channels";
+    if (ips < 1 || n % ips) return "n_clips is not a multiple of items_per_stream";
+    if (!fresh && (!c->cap_state || n / ips != c->cap_streams))
+      return "mmla_capture_reset must have created n_clips / items_per_stream streams";
+    const int64_t ocl = ((int64_t)clip_frames * c->cap_or - 1) / c->cap_ir + 1;
+    if (ocl > 600000) return "out_clip_len > 600000 (one gate chunk)";
+    out_clip_len = (int32_t)ocl;
+    if (frames && !dev)   // device-pointer frames cannot be seen here: the kernels clamp them
+      for (int64_t i = 0; i < n; ++i)
+        if (frames[i] < 0 || frames[i] > clip_frames) return "frames[c] outside [0, clip_frames]";
+    return nullptr;
+  }
+
+  // out [n][out_stride], out_lens [n]: device pointers.  The states flip only after the last launch is
+  // enqueued, so an error on the way leaves them as they were
+  int run(mmla_ctx* c, bool dev, int16_t* out, int64_t out_stride, int32_t* out_lens) const {
+    if (n == 0) return MMLA_OK;
+    const int nch = c->cap_channels;
+    void *pitem = nullptr, *pfr = nullptr, *praw = nullptr;
+    CHK(cap_get(c, CB_ITEM, (size_t)n * 2 * sizeof(int32_t), &pitem));
+    const int32_t* dframes = frames;
+    const int64_t row = (int64_t)clip_frames * nch;
+    int64_t piece = n;
+    if (!dev) {
+      if (frames) {
+        CHK(cap_get(c, CB_FRAMES, (size_t)n * sizeof(int32_t), &pfr));
+        HIPCHK(c, hipMemcpyAsync(pfr, frames, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        dframes = static_cast<const int32_t*>(pfr);
+      }
+      piece = std::max<int64_t>(ips, (int64_t)(kCapStageBytes / ((size_t)row * sizeof(int16_t))) / ips * ips);
+      piece = std::min(piece, n);
+      CHK(cap_get(c, CB_RAW, (size_t)piece * row * sizeof(int16_t), &praw));
+    }
+    const int64_t ns = c->cap_streams;
+    for (int64_t c0 = 0; c0 < n; c0 += piece) {
+      const int64_t cnt = std::min(piece, n - c0), s0 = c0 / ips;
+      CaptureArgs a{};
+      if (dev) {
+        a.pcm = pcm + c0 * stride;
+        a.clip_stride = stride;
+      } else {   // the next piece's copy waits on the stream for the kernels that read this one
+        HIPCHK(c, hipMemcpy2DAsync(praw, row * sizeof(int16_t), pcm + c0 * stride, stride * sizeof(int16_t),
+                                   row * sizeof(int16_t), cnt, hipMemcpyHostToDevice, c->stream));
+        a.pcm = static_cast<const int16_t*>(praw);
+        a.clip_stride = row;
+      }
+      a.frames = dframes ? dframes + c0 : nullptr;
+      a.clip_frames = clip_frames;
+      a.channels = nch;
+      a.channel = c->cap_channel;
+      a.ir = c->cap_ir;
+      a.orr = c->cap_or;
+      a.n_clips = cnt;
+      a.items_per_stream = ips;
+      if (!fresh) {
+        a.state_in = c->cap_state + ((int64_t)c->cap_cur * ns + s0) * 2;
+        a.state_out = c->cap_state + ((int64_t)(c->cap_cur ^ 1) * ns + s0) * 2;
+      }
+      a.item = static_cast<int32_t*>(pitem) + c0 * 2;
+      a.out = out + c0 * out_stride;
+      a.out_stride = out_stride;
+      a.out_clip_len = out_clip_len;
+      a.out_lens = out_lens + c0;
+      LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * 16, capture_phase_launch(a, c->stream));
+      LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * 2.0 * ((double)row + out_clip_len),
+             capture_sample_launch(a, c->stream));
+    }
+    if (!fresh) c->cap_cur ^= 1;
+    return MMLA_OK;
+  }
+};
+
+// mmla_{od,si,room}_pipeline_capture: every check first (the capture's, mmla_condition's, the weights),
+// then the conversion of all clips once, then the conditioned pipeline on the converted clips, which
+// stay in the context's capture buffers
+int capture_pipeline(mmla_ctx* c, Which w, const int16_t* pcm, int64_t n, int64_t stride,
+                     const int32_t* frames, int32_t clip_frames, const int32_t* profile, int32_t nr_passes,
+                     int32_t silence_remove, int64_t ips, int16_t* out_pcm, int32_t* kept_len,
+                     const NetOut& o, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  const bool dev = flags & MMLA_DEVICE_PTR;
+  Capture cap{pcm, n, stride, frames, clip_frames, ips, false};
+  if (const char* bad = cap.bad(c, dev)) return fail(c, MMLA_E_INVALID, "%s", bad);
+  const int32_t L = cap.out_clip_len;
+  // the checks of mmla_condition on the converted clips' geometry (the pointers only as non-null marks)
+  Conditioner cd{pcm, n, L, nullptr, L, profile, nr_passes, silence_remove, ips, out_pcm, kept_len,
+                 (flags & MMLA_NR_NONSTATIONARY) != 0};
+  if (const char* bad = cd.bad(c, dev)) return fail(c, MMLA_E_INVALID, "%s", bad);
+  if (const char* m = missing_weights(c, w)) return fail(c, MMLA_E_NOWEIGHTS, "%s weights not loaded", m);
+  HIPCHK(c, hipSetDevice(c->device));
+  void *pout = nullptr, *plens = nullptr;
+  CHK(cap_get(c, CB_OUT, (size_t)n * L * sizeof(int16_t), &pout));
+  CHK(cap_get(c, CB_LENS, (size_t)n * sizeof(int32_t), &plens));
+  CHK(cap.run(c, dev, static_cast<int16_t*>(pout), L, static_cast<int32_t*>(plens)));
+  cd.pcm = static_cast<const int16_t*>(pout);
+  cd.lens = static_cast<const int32_t*>(plens);
+  cd.pcm_dev = true;
+  return conditioned_body(c, w, cd, o, flags);
 }
 
 }  // namespace
@@ -720,13 +952,7 @@ int mmla_ssim_u8(mmla_ctx* c, const uint8_t* a, const uint8_t* b, int64_t n, int
 int mmla_si_pipeline(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
                      const int32_t* lens, int32_t clip_len, float* probs, int32_t* argmax,
                      uint8_t* silent, uint32_t flags) {
-  return clip_call(c, NET_SI, n, flags, bad_pcm_args(pcm, n, stride, lens, clip_len) ? "bad pcm args" : nullptr,
-                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
-    Pcm p;
-    CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, SI_NEED_SAMPLES, dev, &p));
-    p.clip_len = lens ? 0 : clip_len;   // the true length decides T even if fewer samples are staged
-    return si_fe_net(c, p, c0, cnt, dev, probs, argmax, silent);
-  });
+  return si_pipeline_common(c, pcm, n, stride, lens, clip_len, probs, argmax, silent, flags);
 }
 
 int mmla_condition(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride, const int32_t* lens,
@@ -742,19 +968,9 @@ int mmla_od_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, int
                                  int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
                                  int16_t* out_pcm, int32_t* kept_len, float* probs, int32_t* argmax,
                                  uint8_t* silent, uint32_t flags) {
-  if (!c) return MMLA_E_INVALID;
   Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, items_per_stream,
                  out_pcm, kept_len, (flags & MMLA_NR_NONSTATIONARY) != 0};
-  const char* bad = cd.bad(c, flags & MMLA_DEVICE_PTR);
-  if (!bad && cd.off()) {   // nothing to condition: mmla_od_pipeline itself, then the copies asked for
-    CHK(od_pipeline_common(c, pcm, n, stride, lens, clip_len, false, 0, 0.0f, probs, argmax, silent,
-                           nullptr, flags));
-    return out_pcm || kept_len ? condition_call(c, cd, flags) : MMLA_OK;
-  }
-  return clip_call(c, NET_OD, n, flags, bad, [&](int64_t c0, int64_t cnt, bool dev) -> int {
-    CHK(cd.run(c, c0, cnt, dev));
-    return od_fe_net(c, cd, c0, cnt, dev, probs, argmax, silent);
-  }, std::max<int64_t>(items_per_stream, 1));
+  return conditioned_call(c, W_OD, cd, NetOut{probs, argmax, nullptr, nullptr, silent}, flags);
 }
 
 int mmla_si_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
@@ -762,61 +978,133 @@ int mmla_si_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, int
                                  int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
                                  int16_t* out_pcm, int32_t* kept_len, float* probs, int32_t* argmax,
                                  uint8_t* silent, uint32_t flags) {
-  if (!c) return MMLA_E_INVALID;
   Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, items_per_stream,
                  out_pcm, kept_len, (flags & MMLA_NR_NONSTATIONARY) != 0};
-  const char* bad = cd.bad(c, flags & MMLA_DEVICE_PTR);
-  if (!bad && cd.off()) {   // nothing to condition: mmla_si_pipeline itself, then the copies asked for
-    CHK(mmla_si_pipeline(c, pcm, n, stride, lens, clip_len, probs, argmax, silent, flags));
-    return out_pcm || kept_len ? condition_call(c, cd, flags) : MMLA_OK;
-  }
-  return clip_call(c, NET_SI, n, flags, bad, [&](int64_t c0, int64_t cnt, bool dev) -> int {
-    CHK(cd.run(c, c0, cnt, dev));
-    // the conditioned clips with lens = kept_len (a row holds clip_len samples, zeros behind kept_len)
-    const Pcm p{cd.q, cd.clip_len, cd.kept, 0};
-    return si_fe_net(c, p, c0, cnt, dev, probs, argmax, silent);
-  }, std::max<int64_t>(items_per_stream, 1));
+  return conditioned_call(c, W_SI, cd, NetOut{nullptr, nullptr, probs, argmax, silent}, flags);
 }
 
-// Both networks on one conditioning: per micro-batch (whole streams, OD's cap) Conditioner::run once,
-// then each network's front-end + net under its own range guard, reading the conditioned clips that
-// stay in S_COND_Q / S_COND_KEPT.  A guard re-run repeats that network alone; an allocation failure
-// repeats the micro-batch with fewer clips, the detectors restored by Conditioner::run's snapshot.
+// Both detectors on one conditioning (conditioned_body)
 int mmla_room_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
                                    const int32_t* lens, int32_t clip_len, const int32_t* profile,
                                    int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
                                    int16_t* out_pcm, int32_t* kept_len, float* od_probs,
                                    int32_t* od_argmax, float* si_probs, int32_t* si_argmax,
                                    uint8_t* silent, uint32_t flags) {
-  if (!c) return MMLA_E_INVALID;
   Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, items_per_stream,
                  out_pcm, kept_len, (flags & MMLA_NR_NONSTATIONARY) != 0};
-  const bool dev = flags & MMLA_DEVICE_PTR;
-  if (const char* bad = cd.bad(c, dev)) return fail(c, MMLA_E_INVALID, "%s", bad);
-  if (!c->od_loaded) return fail(c, MMLA_E_NOWEIGHTS, "OD weights not loaded");
-  if (!c->si_loaded) return fail(c, MMLA_E_NOWEIGHTS, "SI weights not loaded");
-  if (cd.off()) {   // nothing to condition: the two plain pipelines, then the copies asked for
-    CHK(od_pipeline_common(c, pcm, n, stride, lens, clip_len, false, 0, 0.0f, od_probs, od_argmax, silent,
-                           nullptr, flags));
-    CHK(mmla_si_pipeline(c, pcm, n, stride, lens, clip_len, si_probs, si_argmax, nullptr, flags));
-    return out_pcm || kept_len ? condition_call(c, cd, flags) : MMLA_OK;
-  }
+  return conditioned_call(c, W_ROOM, cd, NetOut{od_probs, od_argmax, si_probs, si_argmax, silent}, flags);
+}
+
+// ---- a room's capture format (resample.hip capture_*_kernel) ----------------------------------------
+
+int mmla_capture_reset(mmla_ctx* c, int64_t n_streams, int32_t rate, int32_t channels, int32_t channel) {
+  if (!c) return MMLA_E_INVALID;
+  if (n_streams < 1) return fail(c, MMLA_E_INVALID, "n_streams must be >= 1");
+  if (rate < 1 || rate > 384000) return fail(c, MMLA_E_INVALID, "capture rate %d outside 1..384000", rate);
+  if (channels < 1 || channels > 8) return fail(c, MMLA_E_INVALID, "%d capture channels outside 1..8", channels);
+  if (channel >= channels || channel < MMLA_CAPTURE_MEAN)
+    return fail(c, MMLA_E_INVALID, "channel %d of %d", channel, channels);
+  if (channel == MMLA_CAPTURE_MEAN && channels != 2)
+    return fail(c, MMLA_E_INVALID, "MMLA_CAPTURE_MEAN needs 2 channels, got %d", channels);
   HIPCHK(c, hipSetDevice(c->device));
-  CHK(for_microbatches(c, true, n, [&](int64_t c0, int64_t cnt) -> int {
-    CHK(cd.run(c, c0, cnt, dev));
-    CHK(guarded(c, dev, c->od_f32_only, [&]() -> int {
-      return od_fe_net(c, cd, c0, cnt, dev, od_probs, od_argmax, silent);
-    }));
-    CHK(guarded(c, dev, c->si_f32_only, [&]() -> int {
-      // the conditioned clips with lens = kept_len, as mmla_si_pipeline_conditioned reads them; its
-      // 'silent' (kept_len < 4000, the rule of OD's gate) stays in the workspace
-      const Pcm p{cd.q, cd.clip_len, cd.kept, 0};
-      return si_fe_net(c, p, c0, cnt, dev, si_probs, si_argmax, nullptr, S_ROOM_P, S_ROOM_A);
-    }));
-    if (!dev) HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MMLA_OK;
-  }, std::max<int64_t>(items_per_stream, 1)));
-  return finish(c, dev);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const int g = std::gcd(rate, 16000);
+  std::vector<int32_t> h((size_t)n_streams * 2);
+  for (int64_t s = 0; s < n_streams; ++s) {   // a fresh audioop state: d = -outrate, prev = 0
+    h[2 * s] = -(16000 / g);
+    h[2 * s + 1] = 0;
+  }
+  if (c->cap_streams != n_streams) {
+    if (c->cap_state) HIPCHK(c, hipFree(c->cap_state));
+    c->cap_state = nullptr;
+    c->cap_streams = 0;
+    c->cap_rate = 0;
+    if (hipMalloc(&c->cap_state, 4 * n_streams * sizeof(int32_t)) != hipSuccess) {
+      (void)hipGetLastError();
+      c->cap_state = nullptr;
+      return fail(c, MMLA_E_OOM, "capture state for %lld streams", (long long)n_streams);
+    }
+  }
+  HIPCHK(c, hipMemcpy(c->cap_state, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  c->cap_cur = 0;
+  c->cap_streams = n_streams;
+  c->cap_rate = rate;
+  c->cap_channels = channels;
+  c->cap_channel = channel;
+  c->cap_ir = rate / g;
+  c->cap_or = 16000 / g;
+  return MMLA_OK;
+}
+
+int mmla_capture_state(mmla_ctx* c, int32_t* d, int32_t* prev) {
+  if (!c) return MMLA_E_INVALID;
+  if (!c->cap_state || !c->cap_rate) return fail(c, MMLA_E_INVALID, "mmla_capture_reset must be called first");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<int32_t> h((size_t)c->cap_streams * 2);
+  HIPCHK(c, hipMemcpy(h.data(), c->cap_state + (int64_t)c->cap_cur * c->cap_streams * 2,
+                      h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (int64_t s = 0; s < c->cap_streams; ++s) {
+    if (d) d[s] = h[2 * s];
+    if (prev) prev[s] = h[2 * s + 1];
+  }
+  return MMLA_OK;
+}
+
+int mmla_capture_convert(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride, const int32_t* frames,
+                         int32_t clip_frames, int64_t items_per_stream, int16_t* out, int64_t out_stride,
+                         int32_t* out_lens, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  const bool dev = flags & MMLA_DEVICE_PTR;
+  Capture cap{pcm, n, stride, frames, clip_frames, items_per_stream, (flags & MMLA_CAPTURE_FRESH) != 0};
+  if (const char* bad = cap.bad(c, dev)) return fail(c, MMLA_E_INVALID, "%s", bad);
+  const int32_t L = cap.out_clip_len;
+  if (n > 0 && (!out || !out_lens || out_stride < L))
+    return fail(c, MMLA_E_INVALID, "capture_convert needs out, out_lens and out_stride >= out_clip_len = %d", L);
+  if (n == 0) return MMLA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (dev) {
+    CHK(cap.run(c, true, out, out_stride, out_lens));
+    return finish(c, true);
+  }
+  void *pout = nullptr, *plens = nullptr;
+  CHK(cap_get(c, CB_OUT, (size_t)n * L * sizeof(int16_t), &pout));
+  CHK(cap_get(c, CB_LENS, (size_t)n * sizeof(int32_t), &plens));
+  CHK(cap.run(c, false, static_cast<int16_t*>(pout), L, static_cast<int32_t*>(plens)));
+  HIPCHK(c, hipMemcpy2DAsync(out, out_stride * sizeof(int16_t), pout, L * sizeof(int16_t), L * sizeof(int16_t),
+                             n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out_lens, plens, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  return finish(c, false);
+}
+
+int mmla_od_pipeline_capture(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
+                             const int32_t* frames, int32_t clip_frames, const int32_t* profile,
+                             int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
+                             int16_t* out_pcm, int32_t* kept_len, float* probs, int32_t* argmax,
+                             uint8_t* silent, uint32_t flags) {
+  return capture_pipeline(c, W_OD, pcm, n, stride, frames, clip_frames, profile, nr_passes, silence_remove,
+                          items_per_stream, out_pcm, kept_len, NetOut{probs, argmax, nullptr, nullptr, silent},
+                          flags);
+}
+
+int mmla_si_pipeline_capture(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
+                             const int32_t* frames, int32_t clip_frames, const int32_t* profile,
+                             int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
+                             int16_t* out_pcm, int32_t* kept_len, float* probs, int32_t* argmax,
+                             uint8_t* silent, uint32_t flags) {
+  return capture_pipeline(c, W_SI, pcm, n, stride, frames, clip_frames, profile, nr_passes, silence_remove,
+                          items_per_stream, out_pcm, kept_len, NetOut{nullptr, nullptr, probs, argmax, silent},
+                          flags);
+}
+
+int mmla_room_pipeline_capture(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
+                               const int32_t* frames, int32_t clip_frames, const int32_t* profile,
+                               int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
+                               int16_t* out_pcm, int32_t* kept_len, float* od_probs, int32_t* od_argmax,
+                               float* si_probs, int32_t* si_argmax, uint8_t* silent, uint32_t flags) {
+  return capture_pipeline(c, W_ROOM, pcm, n, stride, frames, clip_frames, profile, nr_passes, silence_remove,
+                          items_per_stream, out_pcm, kept_len,
+                          NetOut{od_probs, od_argmax, si_probs, si_argmax, silent}, flags);
 }
 
 int mmla_debug_od_trace(mmla_ctx* c, const float* x, int64_t n, int stage, float* out,

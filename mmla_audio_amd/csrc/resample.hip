@@ -1,4 +1,6 @@
-// Rate conversion of the offline pre-conditioning chains.
+// Rate conversion of the offline pre-conditioning chains, and of a live room's
+// capture (capture_phase_kernel / capture_sample_kernel below: 44.1 / 48 kHz interleaved -> 16 kHz mono
+// with audioop's state carried per stream).
 //
 // Replaces:
 //   pydub AudioSegment.set_frame_rate(16000) = audioop.ratecv(data, 2, channels, rate, 16000, None)
@@ -75,7 +77,114 @@ __global__ void sinc_resample_kernel(SincResampleArgs a) {
   a.y[t] = y;
 }
 
+// ---- streaming conversion of a room's capture to 16 kHz mono (mmla_capture_convert) ---------------
+//
+// audioop.ratecv(fragment, 2, 1, rate, 16000, state) per stream, the state (d, prev) carried from
+// fragment to fragment, on the mono signal picked or averaged out of the interleaved capture.  The
+// sequential loop adds `or` to d per input frame and subtracts `ir` per output frame, so for a fragment
+// of n frames entered with (d0, prev):
+//   m = floor((n or + d0) / ir) + 1 outputs (0 when n or + d0 < 0);
+//   output j is written right after input frame k = ceil((j ir - d0) / or) - 1, at phase
+//   d = d0 + (k + 1) or - j ir in [0, or), from frames k - 1 (or prev, for k = 0) and k;
+//   the state left is (d0 + n or - m ir, x[n - 1]).
+// capture_phase_kernel walks each stream's fragments with that recurrence (one thread per stream: a
+// handful of integer operations per fragment); capture_sample_kernel then computes every output of
+// every fragment independently, ratecv_kernel's expression bit for bit.
+
+// mono frame k of an interleaved clip: channel `sel`, or audioop.tomono(data, 2, 0.5, 0.5) (sel < 0,
+// two channels): floor(0.5 l + 0.5 r) in double, the sum exact
+__device__ __forceinline__ int capture_mono(const int16_t* __restrict__ clip, int64_t k, int nch,
+                                            int sel) {
+  if (sel >= 0) return (int)clip[k * nch + sel];
+  const double v = 0.5 * (double)clip[2 * k] + 0.5 * (double)clip[2 * k + 1];
+  return (int)floor(v);
+}
+
+__device__ __forceinline__ int capture_frames(const CaptureArgs& a, int64_t c) {
+  if (!a.frames) return a.clip_frames;
+  const int n = a.frames[c];
+  return n < 0 ? 0 : (n > a.clip_frames ? a.clip_frames : n);
+}
+
+__global__ void capture_phase_kernel(CaptureArgs a, int64_t n_streams) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_streams) return;
+  int64_t d = -(int64_t)a.orr;   // a fresh audioop state
+  int prev = 0;
+  if (a.state_in) {
+    d = a.state_in[2 * s];
+    prev = a.state_in[2 * s + 1];
+  }
+  for (int64_t i = 0; i < a.items_per_stream; ++i) {
+    const int64_t c = s * a.items_per_stream + i;
+    const int n = capture_frames(a, c);
+    a.item[2 * c] = (int32_t)d;
+    a.item[2 * c + 1] = prev;
+    const int64_t t = (int64_t)n * a.orr + d;
+    const int64_t m = t >= 0 ? t / a.ir + 1 : 0;
+    a.out_lens[c] = (int32_t)m;
+    d = t - m * a.ir;   // [-max(ir, or), 0)
+    if (n > 0) prev = capture_mono(a.pcm + c * a.clip_stride, n - 1, a.channels, a.channel);
+  }
+  if (a.state_out) {
+    a.state_out[2 * s] = (int32_t)d;
+    a.state_out[2 * s + 1] = prev;
+  }
+}
+
+// grid: blocks_per_clip blocks of 256 outputs per clip, clip-major.  Neighbouring threads store
+// neighbouring int16 and read frames ir / or apart (48 kHz stereo: 12 bytes), a few cache lines per wave
+__global__ void capture_sample_kernel(CaptureArgs a, int blocks_per_clip) {
+#pragma clang fp contract(off)
+  const int64_t c = blockIdx.x / blocks_per_clip;
+  const int64_t j = (int64_t)(blockIdx.x % blocks_per_clip) * blockDim.x + threadIdx.x;
+  if (c >= a.n_clips || j >= a.out_clip_len) return;
+  int16_t* __restrict__ out = a.out + c * a.out_stride;
+  if (j >= a.out_lens[c]) {   // the zero tail up to the longest a fragment can become
+    out[j] = 0;
+    return;
+  }
+  const int64_t d0 = a.item[2 * c];
+  const int64_t k = (j * a.ir - d0 + a.orr - 1) / a.orr - 1;   // 0 <= k <= n - 1 (j ir - d0 >= 1)
+  const int64_t d = d0 + (k + 1) * a.orr - j * a.ir;           // [0, or)
+  if (k < 0 || k >= capture_frames(a, c)) return;              // (out_lens makes this impossible)
+  const int16_t* __restrict__ clip = a.pcm + c * a.clip_stride;
+  const int pm = k > 0 ? capture_mono(clip, k - 1, a.channels, a.channel) : a.item[2 * c + 1];
+  const int prev = pm * 65536;                                  // GETSAMPLE32: x << 16
+  const int cur = capture_mono(clip, k, a.channels, a.channel) * 65536;
+  const double v = ((double)prev * (double)d + (double)cur * (double)(a.orr - d)) / (double)a.orr;
+  const int o = (int)v;                                         // C cast: truncation
+  out[j] = (int16_t)(o >> 16);                                  // SETSAMPLE32
+}
+
 }  // namespace
+
+// the geometry both kernels index by: every read stays inside a clip's clip_frames * channels
+// samples, every store inside out_clip_len <= out_stride
+static bool capture_args_ok(const CaptureArgs& a) {
+  return a.items_per_stream >= 1 && a.n_clips % a.items_per_stream == 0 && a.ir >= 1 && a.orr >= 1 &&
+         a.channels >= 1 && a.channel < a.channels && (a.channel >= 0 || a.channels == 2) &&
+         a.clip_frames >= 1 && a.out_clip_len >= 1 && a.out_stride >= a.out_clip_len &&
+         a.clip_stride >= (int64_t)a.clip_frames * a.channels && a.pcm && a.item && a.out && a.out_lens &&
+         a.n_clips * (int64_t)((a.out_clip_len + 255) / 256) <= 0x7fffffffLL;
+}
+
+hipError_t capture_phase_launch(const CaptureArgs& a, hipStream_t s) {
+  if (a.n_clips <= 0) return hipSuccess;
+  if (!capture_args_ok(a)) return hipErrorInvalidValue;
+  const int64_t n_streams = a.n_clips / a.items_per_stream;
+  hipLaunchKernelGGL(capture_phase_kernel, dim3((unsigned)((n_streams + 63) / 64)), dim3(64), 0, s, a,
+                     n_streams);
+  return hipGetLastError();
+}
+
+hipError_t capture_sample_launch(const CaptureArgs& a, hipStream_t s) {
+  if (a.n_clips <= 0) return hipSuccess;
+  if (!capture_args_ok(a)) return hipErrorInvalidValue;
+  const int bpc = (a.out_clip_len + 255) / 256;
+  hipLaunchKernelGGL(capture_sample_kernel, dim3((unsigned)(a.n_clips * bpc)), dim3(256), 0, s, a, bpc);
+  return hipGetLastError();
+}
 
 hipError_t ratecv_launch(const int16_t* in, int64_t n_frames, int nch, int inrate, int outrate,
                          int16_t* out, int64_t n_out, hipStream_t s) {

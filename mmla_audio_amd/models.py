@@ -58,8 +58,9 @@ class _Model:
             setattr(self.ctx, f'_owner_{self.kind}', self)
 
     def _predict_conditioned(self, call, pcm, noise, mic, lens, passes, silence_remove,
-                             items_per_stream, vad_mode, reset_vad):
-        """the shared body of predict_wavs_conditioned: the bank, the detectors, the fused call"""
+                             items_per_stream, vad_mode, reset_vad, capture=None, reset_capture=False):
+        """the shared body of predict_wavs_conditioned: the bank, the detectors, the converters (capture:
+        a room.CaptureFormat; `call` is then the context's *_pipeline_capture), the fused call"""
         from . import noisereduce
         self._ensure_loaded()
         n = len(pcm) if isinstance(pcm, (list, tuple)) else (1 if np.ndim(pcm) == 1 else len(pcm))
@@ -87,6 +88,13 @@ class _Model:
             if reset_vad or getattr(self.ctx, 'vad_owner', None) != tag:
                 self.ctx.vad_reset(n // ips, vad_mode)
                 self.ctx.vad_owner = tag
+        if capture is not None:
+            # one audioop.ratecv state per stream, owned as the detectors are: created on the first call
+            # or when the stream count or the format changes, carried from call to call otherwise
+            fmt = (int(capture.rate), int(capture.channels), int(capture.channel))
+            if (reset_capture or getattr(self.ctx, 'capture_format', None) != fmt or
+                    getattr(self.ctx, 'capture_streams', None) != n // ips):
+                self.ctx.capture_reset(n // ips, *fmt)
         return call(pcm, lens, mic, passes, silence_remove, ips, nonstationary=ns)
 
 
@@ -127,7 +135,8 @@ class OverlapDetectionModel(_Model):
         return self.ctx.od_pipeline_gated(pcm, lens, passes, threshold)
 
     def predict_wavs_conditioned(self, pcm, noise=None, mic=None, lens=None, passes=1, silence_remove=True,
-                                 items_per_stream=1, vad_mode=3, reset_vad=False):
+                                 items_per_stream=1, vad_mode=3, reset_vad=False, capture=None,
+                                 reset_capture=False):
         """predict_wavs behind the PC loop's save_wave_file(noise_reduce=True, silence_remove=True)
         (record_on_pc.py:141-154,200-226) for a room of microphones: clip c is denoised `passes` times
         against the ambient-noise clip of its microphone (`noise`: one float32 clip, or a list with one
@@ -138,9 +147,15 @@ class OverlapDetectionModel(_Model):
         and a clip with fewer than 4000 samples left is 'silent' -> (probs [N,2], argmax [N] (-1 =
         'silent'), silent [N], kept_len [N]).  The bank of profiles is rebuilt only when a noise clip
         changes.  noise=None: the passes run the non-stationary gate (the context's nr_set_nonstationary
-        parameters), no bank is built and `mic` is only checked for its shape."""
-        return self._predict_conditioned(self.ctx.od_pipeline_conditioned, pcm, noise, mic, lens, passes,
-                                         silence_remove, items_per_stream, vad_mode, reset_vad)
+        parameters), no bank is built and `mic` is only checked for its shape.
+        capture (a room.CaptureFormat): pcm is the microphones' interleaved capture, int16 [N, clip_frames *
+        channels] or a list of such clips, `lens` counts capture frames, and every clip is converted to
+        16 kHz mono on the device first, by its stream's audioop.ratecv state (created and reset under the
+        detectors' rule; reset_capture=True starts afresh); kept_len is at 16 kHz.  capture=None: 16 kHz
+        mono in, as before."""
+        call = self.ctx.od_pipeline_conditioned if capture is None else self.ctx.od_pipeline_capture
+        return self._predict_conditioned(call, pcm, noise, mic, lens, passes, silence_remove,
+                                         items_per_stream, vad_mode, reset_vad, capture, reset_capture)
 
 
 class SpeakerIdModel(_Model):
@@ -164,12 +179,14 @@ class SpeakerIdModel(_Model):
         return self.ctx.si_pipeline(pcm, lens)
 
     def predict_wavs_conditioned(self, pcm, noise=None, mic=None, lens=None, passes=1, silence_remove=True,
-                                 items_per_stream=1, vad_mode=3, reset_vad=False):
+                                 items_per_stream=1, vad_mode=3, reset_vad=False, capture=None,
+                                 reset_capture=False):
         """predict_wavs behind save_wave_file(noise_reduce=True, silence_remove=True) (SI
         record_on_pc.py:117-134,178-205, record_on_pi.py:101-127,228-240); arguments and the returned
         (probs [N,K], argmax, silent, kept_len) as OverlapDetectionModel.predict_wavs_conditioned."""
-        return self._predict_conditioned(self.ctx.si_pipeline_conditioned, pcm, noise, mic, lens, passes,
-                                         silence_remove, items_per_stream, vad_mode, reset_vad)
+        call = self.ctx.si_pipeline_conditioned if capture is None else self.ctx.si_pipeline_capture
+        return self._predict_conditioned(call, pcm, noise, mic, lens, passes, silence_remove,
+                                         items_per_stream, vad_mode, reset_vad, capture, reset_capture)
 
 
 def load_model(path, kind=None, n_classes=None, head=None, seed=0, device=None,
