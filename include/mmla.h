@@ -409,7 +409,9 @@ int mmla_nr_reduce_ns(mmla_ctx* ctx, const float* y, int64_t n_signals, int64_t 
  * pointers: clamped by the kernels).
  * Micro-batched in whole streams (multiples of items_per_stream, at least one stream even where
  * mmla_set_microbatch asks for less); the detectors advance exactly once per clip whatever the
- * micro-batch size and whether a micro-batch had to be re-run.  The gate runs at most 512 clips per
+ * micro-batch size and whether a micro-batch had to be re-run (a range-guard or split-BiLSTM re-run
+ * repeats the network alone on the conditioning already made; an allocation failure repeats the
+ * micro-batch with fewer clips from the detectors' saved state).  The gate runs at most 512 clips per
  * launch with a stream synchronisation between launches and between passes, so with MMLA_DEVICE_PTR and
  * nr_passes > 0 these calls synchronise the context stream internally (their last launches are still
  * only enqueued).

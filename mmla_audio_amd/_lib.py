@@ -35,6 +35,11 @@ _I64 = ctypes.c_int64
 _I32 = ctypes.c_int32
 _U32 = ctypes.c_uint32
 
+# ctx, pcm, n_clips, clip_stride, lens (capture: frames), clip_len (clip_frames), profile, nr_passes,
+# silence_remove, items_per_stream, out_pcm, kept_len: what mmla_condition and the conditioned and capture
+# pipelines all begin with; each network adds (probs, argmax), the pipelines `silent`, then the flags
+_COND = [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P]
+
 # name -> argtypes (all return int)
 SIGNATURES = {
     'mmla_nr_set_noise': [_P, _P, _I64, ctypes.c_int32, ctypes.c_uint32],
@@ -43,22 +48,16 @@ SIGNATURES = {
     'mmla_nr_reduce_bank': [_P, _P, _I64, _I64, _I64, _P, _P, _U32],
     'mmla_nr_set_nonstationary': [_P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I32],
     'mmla_nr_reduce_ns': [_P, _P, _I64, _I64, _I64, _P, _U32],
-    'mmla_condition': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P, _U32],
-    'mmla_od_pipeline_conditioned': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P,
-                                     _P, _P, _P, _U32],
-    'mmla_si_pipeline_conditioned': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P,
-                                     _P, _P, _P, _U32],
-    'mmla_room_pipeline_conditioned': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P,
-                                       _P, _P, _P, _P, _P, _U32],
+    'mmla_condition': _COND + [_U32],
+    'mmla_od_pipeline_conditioned': _COND + [_P] * 3 + [_U32],
+    'mmla_si_pipeline_conditioned': _COND + [_P] * 3 + [_U32],
+    'mmla_room_pipeline_conditioned': _COND + [_P] * 5 + [_U32],
     'mmla_capture_reset': [_P, _I64, _I32, _I32, _I32],
     'mmla_capture_convert': [_P, _P, _I64, _I64, _P, _I32, _I64, _P, _I64, _P, _U32],
     'mmla_capture_state': [_P, _P, _P],
-    'mmla_od_pipeline_capture': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P,
-                                 _P, _P, _P, _U32],
-    'mmla_si_pipeline_capture': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P,
-                                 _P, _P, _P, _U32],
-    'mmla_room_pipeline_capture': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I64, _P, _P,
-                                   _P, _P, _P, _P, _P, _U32],
+    'mmla_od_pipeline_capture': _COND + [_P] * 3 + [_U32],
+    'mmla_si_pipeline_capture': _COND + [_P] * 3 + [_U32],
+    'mmla_room_pipeline_capture': _COND + [_P] * 5 + [_U32],
     'mmla_debug_vad_path': [_P, _I64, ctypes.POINTER(_I32)],
     'mmla_abi_version': [],
     'mmla_crc32c': [_P, _I64, ctypes.POINTER(_U32)],
@@ -640,24 +639,31 @@ class Context:
         return probs, am, silent.astype(bool), ssim
 
     # -- the PC loops' pre-conditioning (noise gate + silence removal) in front of the networks ---
-    def _conditioned(self, fn, what, pcm, lens, profile, passes, silence_remove, items_per_stream,
-                     n_classes, return_pcm, nonstationary=False):
-        a, ln, L = self._pcm(pcm, lens)
+    def _fused(self, name, n_classes, clips, profile, passes, silence_remove, items_per_stream, return_pcm,
+               nonstationary):
+        """The shared body of condition and the {od,si,room}_pipeline_{conditioned,capture} calls.
+        clips: (int16 [n, stride], lens or frames, clip_len or clip_frames, row width of the conditioned
+        clips); n_classes: one width per network, () for the conditioning alone."""
+        a, ln, L, width = clips
         n = a.shape[0]
         pr = self._profile(profile, n)
-        out = np.empty_like(a) if return_pcm else None
+        out = np.empty((n, width), np.int16) if return_pcm else None
         kept = np.empty(n, np.int32)
-        head = (self.h, _ptr(a), n, a.shape[1], _ptr(ln), L, _ptr(pr), int(passes),
-                int(bool(silence_remove)), int(items_per_stream), _ptr(out), _ptr(kept))
-        if n_classes is None:
-            self._check(fn(*head, _ns(nonstationary)), what)
-            return out, kept
-        probs = np.empty((n, n_classes), np.float32)
-        am = np.empty(n, np.int32)
+        nets = []
+        for k in n_classes:
+            nets += [np.empty((n, k), np.float32), np.empty(n, np.int32)]
         silent = np.empty(n, np.uint8)
-        self._check(fn(*head, _ptr(probs), _ptr(am), _ptr(silent), _ns(nonstationary)), what)
-        res = (probs, am, silent.astype(bool), kept)
+        tail = nets + [silent] if n_classes else []
+        self._fused_call(name, False, _ptr(a), n, a.shape[1], _ptr(ln), L, passes, silence_remove,
+                         items_per_stream, [_ptr(x) for x in tail], _ptr(out), _ptr(kept), _ptr(pr), nonstationary)
+        if not n_classes:
+            return out, kept
+        res = tuple(nets) + (silent.astype(bool), kept)
         return res + (out,) if return_pcm else res
+
+    def _cond_clips(self, pcm, lens):
+        a, ln, L = self._pcm(pcm, lens)
+        return a, ln, L, a.shape[1]
 
     def condition(self, pcm, lens=None, profile=None, passes=1, silence_remove=True,
                   items_per_stream=1, nonstationary=False):
@@ -666,46 +672,30 @@ class Context:
         [n]).  Clip c is gated `passes` times against noise profile profile[c] (nr_set_noise_bank; None:
         profile 0; nonstationary=True: the gate of nr_reduce_ns, no bank, profile ignored); silence removal runs on the vad_reset detectors, stream s owning clips
         [s * items_per_stream, (s + 1) * items_per_stream), and their state persists across calls."""
-        return self._conditioned(self.lib.mmla_condition, 'mmla_condition', pcm, lens, profile, passes,
-                                 silence_remove, items_per_stream, None, True, nonstationary)
+        return self._fused('mmla_condition', (), self._cond_clips(pcm, lens), profile, passes, silence_remove,
+                           items_per_stream, True, nonstationary)
 
     def od_pipeline_conditioned(self, pcm, lens=None, profile=None, passes=1, silence_remove=True,
                                 items_per_stream=1, return_pcm=False, nonstationary=False):
         """condition() fused in front of od_pipeline -> (probs [n,2], argmax [n] (-1 = 'silent': fewer
         than 4000 samples kept), silent [n] bool, kept_len [n]); return_pcm adds the conditioned clips."""
-        return self._conditioned(self.lib.mmla_od_pipeline_conditioned, 'mmla_od_pipeline_conditioned',
-                                 pcm, lens, profile, passes, silence_remove, items_per_stream, 2,
-                                 return_pcm, nonstationary)
+        return self._fused('mmla_od_pipeline_conditioned', (2,), self._cond_clips(pcm, lens), profile, passes,
+                           silence_remove, items_per_stream, return_pcm, nonstationary)
 
     def si_pipeline_conditioned(self, pcm, lens=None, profile=None, passes=1, silence_remove=True,
                                 items_per_stream=1, return_pcm=False, nonstationary=False):
         """condition() fused in front of si_pipeline -> (probs [n,K], argmax, silent, kept_len)"""
-        return self._conditioned(self.lib.mmla_si_pipeline_conditioned, 'mmla_si_pipeline_conditioned',
-                                 pcm, lens, profile, passes, silence_remove, items_per_stream,
-                                 self.si_classes or 0, return_pcm, nonstationary)
+        return self._fused('mmla_si_pipeline_conditioned', (self.si_classes or 0,), self._cond_clips(pcm, lens),
+                           profile, passes, silence_remove, items_per_stream, return_pcm, nonstationary)
 
     def room_pipeline_conditioned(self, pcm, lens=None, profile=None, passes=1, silence_remove=True,
                                   items_per_stream=1, return_pcm=False, nonstationary=False):
         """condition() once in front of od_pipeline and si_pipeline -> (od_probs [n,2], od_argmax [n],
         si_probs [n,K], si_argmax [n], silent [n] bool, kept_len [n]); return_pcm adds the conditioned
         clips.  Both argmax are -1 where fewer than 4000 samples were kept."""
-        a, ln, L = self._pcm(pcm, lens)
-        n = a.shape[0]
-        pr = self._profile(profile, n)
-        out = np.empty_like(a) if return_pcm else None
-        kept = np.empty(n, np.int32)
-        od_probs = np.empty((n, 2), np.float32)
-        si_probs = np.empty((n, self.si_classes or 0), np.float32)
-        od_am = np.empty(n, np.int32)
-        si_am = np.empty(n, np.int32)
-        silent = np.empty(n, np.uint8)
-        self._check(self.lib.mmla_room_pipeline_conditioned(
-            self.h, _ptr(a), n, a.shape[1], _ptr(ln), L, _ptr(pr), int(passes),
-            int(bool(silence_remove)), int(items_per_stream), _ptr(out), _ptr(kept), _ptr(od_probs),
-            _ptr(od_am), _ptr(si_probs), _ptr(si_am), _ptr(silent), _ns(nonstationary)),
-            'mmla_room_pipeline_conditioned')
-        res = (od_probs, od_am, si_probs, si_am, silent.astype(bool), kept)
-        return res + (out,) if return_pcm else res
+        return self._fused('mmla_room_pipeline_conditioned', (2, self.si_classes or 0),
+                           self._cond_clips(pcm, lens), profile, passes, silence_remove, items_per_stream,
+                           return_pcm, nonstationary)
 
     # -- a room's capture format: streaming conversion to 16 kHz mono in front of the pipelines ----
     def capture_reset(self, n_streams, rate, channels=1, channel=0):
@@ -779,24 +769,9 @@ class Context:
                     'mmla_capture_state')
         return d, prev
 
-    def _capture_pipeline(self, fn, what, n_classes, pcm, frames, profile, passes, silence_remove,
-                          items_per_stream, return_pcm, nonstationary):
-        """the shared body of {od,si,room}_pipeline_capture; n_classes: one width per network"""
+    def _capture_clips(self, pcm, frames):
         a, fr, cf = self._capture_pcm(pcm, frames)
-        n = a.shape[0]
-        pr = self._profile(profile, n)
-        ocl = self.capture_out_len(max(cf, 1), self.capture_format[0])
-        out = np.empty((n, ocl), np.int16) if return_pcm else None
-        kept = np.empty(n, np.int32)
-        nets = []
-        for k in n_classes:
-            nets += [np.empty((n, k), np.float32), np.empty(n, np.int32)]
-        silent = np.empty(n, np.uint8)
-        self._check(fn(self.h, _ptr(a), n, a.shape[1], _ptr(fr), cf, _ptr(pr), int(passes),
-                       int(bool(silence_remove)), int(items_per_stream), _ptr(out), _ptr(kept),
-                       *[_ptr(x) for x in nets], _ptr(silent), _ns(nonstationary)), what)
-        res = tuple(nets) + (silent.astype(bool), kept)
-        return res + (out,) if return_pcm else res
+        return a, fr, cf, self.capture_out_len(max(cf, 1), self.capture_format[0])
 
     def od_pipeline_capture(self, pcm, frames=None, profile=None, passes=1, silence_remove=True,
                             items_per_stream=1, return_pcm=False, nonstationary=False):
@@ -804,57 +779,57 @@ class Context:
         of all clips, then the conditioned pipeline on the converted clips, which stay on the device ->
         (probs [n,2], argmax [n], silent [n] bool, kept_len [n] at 16 kHz); return_pcm adds the
         conditioned clips [n, out_clip_len]."""
-        return self._capture_pipeline(self.lib.mmla_od_pipeline_capture, 'mmla_od_pipeline_capture', (2,),
-                                      pcm, frames, profile, passes, silence_remove, items_per_stream,
-                                      return_pcm, nonstationary)
+        return self._fused('mmla_od_pipeline_capture', (2,), self._capture_clips(pcm, frames), profile, passes,
+                           silence_remove, items_per_stream, return_pcm, nonstationary)
 
     def si_pipeline_capture(self, pcm, frames=None, profile=None, passes=1, silence_remove=True,
                             items_per_stream=1, return_pcm=False, nonstationary=False):
         """si_pipeline_conditioned on interleaved capture -> (probs [n,K], argmax, silent, kept_len)"""
-        return self._capture_pipeline(self.lib.mmla_si_pipeline_capture, 'mmla_si_pipeline_capture',
-                                      (self.si_classes or 0,), pcm, frames, profile, passes,
-                                      silence_remove, items_per_stream, return_pcm, nonstationary)
+        return self._fused('mmla_si_pipeline_capture', (self.si_classes or 0,), self._capture_clips(pcm, frames),
+                           profile, passes, silence_remove, items_per_stream, return_pcm, nonstationary)
 
     def room_pipeline_capture(self, pcm, frames=None, profile=None, passes=1, silence_remove=True,
                               items_per_stream=1, return_pcm=False, nonstationary=False):
         """room_pipeline_conditioned on interleaved capture -> (od_probs [n,2], od_argmax [n], si_probs
         [n,K], si_argmax [n], silent [n] bool, kept_len [n]); return_pcm adds the conditioned clips."""
-        return self._capture_pipeline(self.lib.mmla_room_pipeline_capture, 'mmla_room_pipeline_capture',
-                                      (2, self.si_classes or 0), pcm, frames, profile, passes,
-                                      silence_remove, items_per_stream, return_pcm, nonstationary)
+        return self._fused('mmla_room_pipeline_capture', (2, self.si_classes or 0),
+                           self._capture_clips(pcm, frames), profile, passes, silence_remove, items_per_stream,
+                           return_pcm, nonstationary)
 
-    def _capture_pipeline_dev(self, fn, what, pcm, n, stride, clip_frames, passes, silence_remove,
-                              items_per_stream, nets, silent, out_pcm, kept_len, frames, profile,
-                              nonstationary):
-        self._check(fn(self.h, pcm, n, stride, frames or None, clip_frames, profile or None, int(passes),
-                       int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
-                       *[x or None for x in nets], silent or None,
-                       MMLA_DEVICE_PTR | _ns(nonstationary)), what)
+    def _fused_call(self, name, dev, pcm, n, stride, lens, clip_len, passes, silence_remove, items_per_stream,
+                    outs, out_pcm, kept_len, profile, nonstationary):
+        """The one C call of condition and the {od,si,room}_pipeline_{conditioned,capture} methods, host
+        (dev=False) and *_dev, on addresses (0 or None: a null pointer).  lens, clip_len: frames, clip_frames
+        for capture; outs: each network's (probs, argmax), then silent."""
+        self._check(getattr(self.lib, name)(
+            self.h, pcm, n, stride, lens or None, clip_len, profile or None, int(passes),
+            int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
+            *[x or None for x in outs], (MMLA_DEVICE_PTR if dev else 0) | _ns(nonstationary)),
+            name + ('(dev)' if dev else ''))
 
     def od_pipeline_capture_dev(self, pcm, n, stride, clip_frames, passes=1, silence_remove=True,
                                 items_per_stream=1, probs=0, argmax=0, silent=0, out_pcm=0, kept_len=0,
                                 frames=0, profile=0, nonstationary=False):
         """synchronises the context stream internally when passes > 0 (see mmla.h)"""
-        self._capture_pipeline_dev(self.lib.mmla_od_pipeline_capture, 'mmla_od_pipeline_capture(dev)', pcm,
-                                   n, stride, clip_frames, passes, silence_remove, items_per_stream,
-                                   (probs, argmax), silent, out_pcm, kept_len, frames, profile, nonstationary)
+        self._fused_call('mmla_od_pipeline_capture', True, pcm, n, stride, frames, clip_frames, passes,
+                         silence_remove, items_per_stream, (probs, argmax, silent), out_pcm, kept_len, profile,
+                         nonstationary)
 
     def si_pipeline_capture_dev(self, pcm, n, stride, clip_frames, passes=1, silence_remove=True,
                                 items_per_stream=1, probs=0, argmax=0, silent=0, out_pcm=0, kept_len=0,
                                 frames=0, profile=0, nonstationary=False):
         """synchronises the context stream internally when passes > 0 (see mmla.h)"""
-        self._capture_pipeline_dev(self.lib.mmla_si_pipeline_capture, 'mmla_si_pipeline_capture(dev)', pcm,
-                                   n, stride, clip_frames, passes, silence_remove, items_per_stream,
-                                   (probs, argmax), silent, out_pcm, kept_len, frames, profile, nonstationary)
+        self._fused_call('mmla_si_pipeline_capture', True, pcm, n, stride, frames, clip_frames, passes,
+                         silence_remove, items_per_stream, (probs, argmax, silent), out_pcm, kept_len, profile,
+                         nonstationary)
 
     def room_pipeline_capture_dev(self, pcm, n, stride, clip_frames, passes=1, silence_remove=True,
                                   items_per_stream=1, od_probs=0, od_argmax=0, si_probs=0, si_argmax=0,
                                   silent=0, out_pcm=0, kept_len=0, frames=0, profile=0, nonstationary=False):
         """synchronises the context stream internally when passes > 0 (see mmla.h)"""
-        self._capture_pipeline_dev(self.lib.mmla_room_pipeline_capture, 'mmla_room_pipeline_capture(dev)',
-                                   pcm, n, stride, clip_frames, passes, silence_remove, items_per_stream,
-                                   (od_probs, od_argmax, si_probs, si_argmax), silent, out_pcm, kept_len,
-                                   frames, profile, nonstationary)
+        self._fused_call('mmla_room_pipeline_capture', True, pcm, n, stride, frames, clip_frames, passes,
+                         silence_remove, items_per_stream, (od_probs, od_argmax, si_probs, si_argmax, silent),
+                         out_pcm, kept_len, profile, nonstationary)
 
     def debug_vad_path(self, n_streams):
         """True when a detector call over n_streams streams runs the one-stream-per-wave kernel"""
@@ -951,41 +926,33 @@ class Context:
     def condition_dev(self, pcm, n, stride, clip_len, passes=1, silence_remove=True,
                       items_per_stream=1, out_pcm=0, kept_len=0, lens=0, profile=0, nonstationary=False):
         """synchronises the context stream internally when passes > 0 (see mmla.h)"""
-        self._check(self.lib.mmla_condition(
-            self.h, pcm, n, stride, lens or None, clip_len, profile or None, int(passes),
-            int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
-            MMLA_DEVICE_PTR | _ns(nonstationary)), 'mmla_condition(dev)')
+        self._fused_call('mmla_condition', True, pcm, n, stride, lens, clip_len, passes, silence_remove,
+                         items_per_stream, (), out_pcm, kept_len, profile, nonstationary)
 
     def od_pipeline_conditioned_dev(self, pcm, n, stride, clip_len, passes=1, silence_remove=True,
                                     items_per_stream=1, probs=0, argmax=0, silent=0, out_pcm=0,
                                     kept_len=0, lens=0, profile=0, nonstationary=False):
         """synchronises the context stream internally when passes > 0 (see mmla.h)"""
-        self._check(self.lib.mmla_od_pipeline_conditioned(
-            self.h, pcm, n, stride, lens or None, clip_len, profile or None, int(passes),
-            int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
-            probs or None, argmax or None, silent or None, MMLA_DEVICE_PTR | _ns(nonstationary)),
-            'mmla_od_pipeline_conditioned(dev)')
+        self._fused_call('mmla_od_pipeline_conditioned', True, pcm, n, stride, lens, clip_len, passes,
+                         silence_remove, items_per_stream, (probs, argmax, silent), out_pcm, kept_len, profile,
+                         nonstationary)
 
     def si_pipeline_conditioned_dev(self, pcm, n, stride, clip_len, passes=1, silence_remove=True,
                                     items_per_stream=1, probs=0, argmax=0, silent=0, out_pcm=0,
                                     kept_len=0, lens=0, profile=0, nonstationary=False):
         """synchronises the context stream internally when passes > 0 (see mmla.h)"""
-        self._check(self.lib.mmla_si_pipeline_conditioned(
-            self.h, pcm, n, stride, lens or None, clip_len, profile or None, int(passes),
-            int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
-            probs or None, argmax or None, silent or None, MMLA_DEVICE_PTR | _ns(nonstationary)),
-            'mmla_si_pipeline_conditioned(dev)')
+        self._fused_call('mmla_si_pipeline_conditioned', True, pcm, n, stride, lens, clip_len, passes,
+                         silence_remove, items_per_stream, (probs, argmax, silent), out_pcm, kept_len, profile,
+                         nonstationary)
 
     def room_pipeline_conditioned_dev(self, pcm, n, stride, clip_len, passes=1, silence_remove=True,
                                       items_per_stream=1, od_probs=0, od_argmax=0, si_probs=0,
                                       si_argmax=0, silent=0, out_pcm=0, kept_len=0, lens=0, profile=0,
                                       nonstationary=False):
         """synchronises the context stream internally when passes > 0 (see mmla.h)"""
-        self._check(self.lib.mmla_room_pipeline_conditioned(
-            self.h, pcm, n, stride, lens or None, clip_len, profile or None, int(passes),
-            int(bool(silence_remove)), int(items_per_stream), out_pcm or None, kept_len or None,
-            od_probs or None, od_argmax or None, si_probs or None, si_argmax or None, silent or None,
-            MMLA_DEVICE_PTR | _ns(nonstationary)), 'mmla_room_pipeline_conditioned(dev)')
+        self._fused_call('mmla_room_pipeline_conditioned', True, pcm, n, stride, lens, clip_len, passes,
+                         silence_remove, items_per_stream, (od_probs, od_argmax, si_probs, si_argmax, silent),
+                         out_pcm, kept_len, profile, nonstationary)
 
     def ssim_u8_dev(self, a, b, n, h, w, c, out):
         self._check(self.lib.mmla_ssim_u8(self.h, a, b, n, h, w, c, out, MMLA_DEVICE_PTR),

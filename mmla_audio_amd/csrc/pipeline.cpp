@@ -19,7 +19,9 @@ struct PcmT {
   const T* p;
   int64_t stride;
   const int32_t* lens;
-  int32_t clip_len;
+  int32_t clip_len;   // samples of a row the kernels may read: the staged width at most
+  int32_t true_len;   // without lens the clips' true length (it decides 'silent' and SI's T, not the
+                      // staged width); 0 with lens
 };
 using Pcm = PcmT<int16_t>;
 
@@ -28,8 +30,9 @@ using Pcm = PcmT<int16_t>;
 template <typename T>
 int stage_pcm(mmla_ctx* c, const T* pcm, int64_t c0, int64_t cnt, int64_t stride,
               const int32_t* lens, int32_t clip_len, int need, bool dev, PcmT<T>* out) {
+  const int32_t tl = lens ? 0 : clip_len;
   if (dev) {
-    *out = {pcm + c0 * stride, stride, lens ? lens + c0 : nullptr, clip_len};
+    *out = {pcm + c0 * stride, stride, lens ? lens + c0 : nullptr, clip_len, tl};
     return MMLA_OK;
   }
   int64_t width = lens ? std::min<int64_t>(need, stride) : std::min<int64_t>(need, clip_len);
@@ -52,7 +55,7 @@ int stage_pcm(mmla_ctx* c, const T* pcm, int64_t c0, int64_t cnt, int64_t stride
     CHK(ws_get(c, S_PCM, tot, &dp));
     HIPCHK(c, hipMemcpyAsync(dp, c->pin_in, tot, hipMemcpyHostToDevice, c->stream));
     const int32_t* dl = lens ? reinterpret_cast<const int32_t*>(static_cast<char*>(dp) + loff) : nullptr;
-    *out = {static_cast<T*>(dp), overlap ? stride : width, dl, (int32_t)std::min<int64_t>(clip_len, width)};
+    *out = {static_cast<T*>(dp), overlap ? stride : width, dl, (int32_t)std::min<int64_t>(clip_len, width), tl};
     return MMLA_OK;
   }
   if (overlap) {
@@ -62,7 +65,7 @@ int stage_pcm(mmla_ctx* c, const T* pcm, int64_t c0, int64_t cnt, int64_t stride
     CHK(ws_get(c, S_PCM, (size_t)span * sizeof(T), &dp));
     HIPCHK(c, hipMemcpyAsync(dp, pcm + c0 * stride, span * sizeof(T), hipMemcpyHostToDevice,
                              c->stream));
-    *out = {static_cast<T*>(dp), stride, nullptr, (int32_t)std::min<int64_t>(clip_len, width)};
+    *out = {static_cast<T*>(dp), stride, nullptr, (int32_t)std::min<int64_t>(clip_len, width), tl};
     return MMLA_OK;
   }
   CHK(ws_get(c, S_PCM, (size_t)cnt * width * sizeof(T), &dp));
@@ -75,7 +78,7 @@ int stage_pcm(mmla_ctx* c, const T* pcm, int64_t c0, int64_t cnt, int64_t stride
     HIPCHK(c, hipMemcpyAsync(lp, lens + c0, cnt * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     dl = static_cast<int32_t*>(lp);
   }
-  *out = {static_cast<T*>(dp), width, dl, (int32_t)std::min<int64_t>(clip_len, width)};
+  *out = {static_cast<T*>(dp), width, dl, (int32_t)std::min<int64_t>(clip_len, width), tl};
   return MMLA_OK;
 }
 
@@ -180,16 +183,26 @@ int guarded(mmla_ctx* c, bool dev, bool f32_only, F&& body) {
 // synchronisation behind it, then finish.
 //   FEATURES_*  a front-end call: in device mode one launch over the caller's buffers
 //   NET_*       a network call: needs that model's weights; every micro-batch under the range guard
-enum CallKind { FEATURES_OD, FEATURES_SI, NET_OD, NET_SI };
+//   COND_*      a conditioned call (OD, SI, or both for a room): needs the weights of every network it
+//               runs; micro-batched under both pointer modes (SI's cap for COND_SI, else OD's); the body
+//               puts each network under a guard of its own, behind the conditioning
+enum CallKind { FEATURES_OD, FEATURES_SI, NET_OD, NET_SI, COND_OD, COND_SI, COND_ROOM };
+
+// the model a call of this kind needs and the context has not loaded (OD named first), or null
+const char* missing_weights(const mmla_ctx* c, CallKind kind) {
+  if ((kind == NET_OD || kind == COND_OD || kind == COND_ROOM) && !c->od_loaded) return "OD";
+  if ((kind == NET_SI || kind == COND_SI || kind == COND_ROOM) && !c->si_loaded) return "SI";
+  return nullptr;
+}
 
 template <class F>
 int clip_call(mmla_ctx* c, CallKind kind, int64_t n, uint32_t flags, const char* bad_args, F&& body,
               int64_t granule = 1) {
   if (!c) return MMLA_E_INVALID;
   if (bad_args) return fail(c, MMLA_E_INVALID, "%s", bad_args);
-  const bool od = kind == FEATURES_OD || kind == NET_OD, net = kind == NET_OD || kind == NET_SI;
-  if (net && !(od ? c->od_loaded : c->si_loaded))
-    return fail(c, MMLA_E_NOWEIGHTS, "%s weights not loaded", od ? "OD" : "SI");
+  if (const char* m = missing_weights(c, kind)) return fail(c, MMLA_E_NOWEIGHTS, "%s weights not loaded", m);
+  const bool od = kind != FEATURES_SI && kind != NET_SI && kind != COND_SI;   // whose micro-batch cap
+  const bool net = kind == NET_OD || kind == NET_SI, cond = kind >= COND_OD;
   HIPCHK(c, hipSetDevice(c->device));
   const bool dev = flags & MMLA_DEVICE_PTR;
   auto once = [&](int64_t c0, int64_t cnt) -> int {
@@ -201,12 +214,35 @@ int clip_call(mmla_ctx* c, CallKind kind, int64_t n, uint32_t flags, const char*
     CHK(for_microbatches(c, od, n, [&](int64_t c0, int64_t cnt) -> int {
       return guarded(c, dev, od ? c->od_f32_only : c->si_f32_only, [&]() -> int { return once(c0, cnt); });
     }, granule));
-  } else if (dev) {
+  } else if (dev && !cond) {
     if (n > 0) CHK(once(0, n));
   } else {
     CHK(for_microbatches(c, od, n, once, granule));
   }
   return finish(c, dev);
+}
+
+// The front-ends' arguments on a device view of clips; the outputs are the caller's to set
+template <typename T>
+OdFeArgs od_fe_args(const mmla_ctx* c, const PcmT<T>& p) {
+  OdFeArgs a{};
+  if constexpr (std::is_same<T, float>::value) a.pcm_f32 = p.p;
+  else a.pcm = p.p;
+  a.clip_stride = p.stride;
+  a.lens = p.lens;
+  a.clip_len = p.clip_len;
+  a.tables = c->od_tables;
+  return a;
+}
+
+SiFeArgs si_fe_args(const mmla_ctx* c, const Pcm& p) {
+  SiFeArgs a{};
+  a.pcm = p.p;
+  a.clip_stride = p.stride;
+  a.lens = p.lens;
+  a.clip_len = p.true_len;
+  a.tables = c->si_tables;
+  return a;
 }
 
 // algorithmic HBM bytes of one front-end launch: PCM actually consumed + outputs
@@ -256,18 +292,11 @@ int od_features_common(mmla_ctx* c, const T* pcm, int64_t n, int64_t stride, con
                    [&](int64_t c0, int64_t cnt, bool dev) -> int {
     PcmT<T> p;
     CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, MMLA_OD_CLIP, dev, &p));
-    OdFeArgs a{};
+    OdFeArgs a = od_fe_args(c, p);
     if constexpr (std::is_same<T, float>::value) {
-      a.pcm_f32 = p.p;
       a.range_flag = dev ? c->range_dev : c->range_dev + 1;
       if (!dev) HIPCHK(c, hipMemsetAsync(a.range_flag, 0, sizeof(int), c->stream));
-    } else {
-      a.pcm = p.p;
     }
-    a.clip_stride = p.stride;
-    a.lens = p.lens;
-    a.clip_len = p.clip_len;
-    a.tables = c->od_tables;
     CHK(out_ptr(c, db, c0 * OD_PIX, cnt * OD_PIX, dev, S_OUT0, &a.db));
     CHK(out_ptr(c, norm, c0 * OD_PIX, cnt * OD_PIX, dev, S_OUT1, &a.norm));
     CHK(out_ptr(c, zcr, c0 * OD_W, cnt * OD_W, dev, S_OUT2, &a.zcr));
@@ -304,6 +333,59 @@ int od_forward_common(mmla_ctx* c, const float* x_f32, const uint8_t* x_u8, int6
   });
 }
 
+// The noise gate's passes over clips p (their first D samples): y = pcm / 32768 into y0, then nr_passes x
+// (the gate y0 -> y1, the PCM_16 round trip back into y0); the last pass leaves its int16 samples in q
+// instead.  y0, y1 [cnt][D] floats and q are the caller's; profile: device indices, nullable.
+int gate_passes(mmla_ctx* c, const Pcm& p, int64_t cnt, int D, int nr_passes, const int32_t* profile, bool ns,
+                float* y0, float* y1, int16_t* q) {
+  LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * 6, pcm_f32_launch(p.p, p.stride, p.lens, D, cnt, y0, c->stream));
+  for (int k = 0; k < nr_passes; ++k) {
+    // a pass re-uses the gate's item table and scratch: the one before it has drained
+    if (k) HIPCHK(c, hipStreamSynchronize(c->stream));
+    CHK(nr_reduce_dev(c, y0, cnt, D, D, y1, profile, ns));
+    const bool last = k == nr_passes - 1;
+    LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * (last ? 6 : 8),
+           requant_launch(y1, p.lens, D, cnt, last ? nullptr : y0, last ? q : nullptr, c->stream));
+  }
+  return MMLA_OK;
+}
+
+// the OD front-end's image of clips p into the workspace slot `slot`
+int od_image(mmla_ctx* c, const Pcm& p, int64_t cnt, int slot, const uint8_t** img) {
+  void* pimg = nullptr;
+  CHK(ws_get(c, slot, cnt * OD_IMG, &pimg));
+  OdFeArgs a = od_fe_args(c, p);
+  a.img = static_cast<uint8_t*>(pimg);
+  LAUNCH(c, MMLA_STAGE_OD_FE, od_fe_bytes(cnt, a), od_fe_launch(a, cnt, c->stream));
+  *img = a.img;
+  return MMLA_OK;
+}
+
+// OD-NET on a micro-batch's images with the 'silent' gate on the lengths of p (and on g's SSIM fields,
+// where the caller set them), results into probs / argmax / silent at clip c0
+int od_net_out(mmla_ctx* c, const uint8_t* img, const Pcm& p, OdGate g, int64_t c0, int64_t cnt, bool dev,
+               float* probs, int32_t* argmax, uint8_t* silent) {
+  float* dp;
+  int32_t* da;
+  CHK(out_ptr(c, probs, c0 * 2, cnt * 2, dev, S_OUT0, &dp));
+  CHK(out_ptr(c, argmax, c0, cnt, dev, S_OUT1, &da));
+  CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT2, &g.silent));
+  g.lens = p.lens;
+  g.clip_len = p.true_len;
+  CHK(run_od_net(c, img, nullptr, cnt, dp, da, g));
+  CHK(copy_back(c, probs, c0 * 2, dp, cnt * 2, dev));
+  CHK(copy_back(c, argmax, c0, da, cnt, dev));
+  return copy_back(c, silent, c0, g.silent, cnt, dev);
+}
+
+// OD front-end + network of one micro-batch on the device view p of its clips
+int od_fe_net(mmla_ctx* c, const Pcm& p, int64_t c0, int64_t cnt, bool dev, float* probs, int32_t* argmax,
+              uint8_t* silent) {
+  const uint8_t* img;
+  CHK(od_image(c, p, cnt, S_IMG, &img));
+  return od_net_out(c, img, p, OdGate(), c0, cnt, dev, probs, argmax, silent);
+}
+
 // the fused OD pipeline; `gated` adds the denoise-and-compare silence gate of record_on_pi.py:103-124
 // (nr_passes gate + PCM_16 round trips, the second image, their SSIM) in front of the network
 int od_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride, const int32_t* lens,
@@ -319,84 +401,44 @@ int od_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t strid
   return clip_call(c, NET_OD, n, flags, bad, [&](int64_t c0, int64_t cnt, bool dev) -> int {
     Pcm p;
     CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, MMLA_OD_CLIP, dev || pcm_dev, &p));
-    void* pimg = nullptr;
-    CHK(ws_get(c, S_IMG, cnt * OD_IMG, &pimg));
-    OdFeArgs a{};
-    a.pcm = p.p;
-    a.clip_stride = p.stride;
-    a.lens = p.lens;
-    a.clip_len = p.clip_len;
-    a.tables = c->od_tables;
-    a.img = static_cast<uint8_t*>(pimg);
-    LAUNCH(c, MMLA_STAGE_OD_FE, od_fe_bytes(cnt, a), od_fe_launch(a, cnt, c->stream));
-    float* dp;
-    int32_t* da;
-    uint8_t* ds;
-    CHK(out_ptr(c, probs, c0 * 2, cnt * 2, dev, S_OUT0, &dp));
-    CHK(out_ptr(c, argmax, c0, cnt, dev, S_OUT1, &da));
-    CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT2, &ds));
-    OdGate g;
-    g.lens = p.lens;
-    g.clip_len = lens ? 0 : clip_len;   // the true length decides, not the staged width
-    g.silent = ds;
-    const uint8_t* net_img = a.img;
-    float* dss = nullptr;
-    if (gated) {
-      CHK(out_ptr(c, ssim, c0, cnt, dev, S_OUT3, &dss));
-      if (!dss) {
-        void* q = nullptr;
-        CHK(ws_get(c, S_SSIM, cnt * sizeof(float), &q));
-        dss = static_cast<float*>(q);
-      }
-      // the gate sees what the front-end sees: the first 24000 samples at most
-      const int D = (int)std::min<int64_t>(lens ? clip_len : p.clip_len, MMLA_OD_CLIP);
-      if (nr_passes > 0 && D > 0) {
-        // two float clip buffers; the last pass leaves its int16 samples in the first one.  The slack
-        // keeps the front-end's read of a clip whose lens[i] exceeds clip_len inside the buffer
-        const size_t ybytes = (size_t)cnt * D * sizeof(float) + MMLA_OD_CLIP * sizeof(int16_t);
-        void *py0 = nullptr, *py1 = nullptr, *pimg2 = nullptr;
-        CHK(ws_get(c, S_GATE_Y0, ybytes, &py0));
-        CHK(ws_get(c, S_GATE_Y1, ybytes, &py1));
-        CHK(ws_get(c, S_IMG2, cnt * OD_IMG, &pimg2));
-        float *y0 = static_cast<float*>(py0), *y1 = static_cast<float*>(py1);
-        int16_t* yq = static_cast<int16_t*>(py0);
-        LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * 6,
-               pcm_f32_launch(p.p, p.stride, p.lens, D, cnt, y0, c->stream));
-        for (int k = 0; k < nr_passes; ++k) {
-          // a pass re-uses the gate's item table and scratch: the one before it has drained
-          if (k) HIPCHK(c, hipStreamSynchronize(c->stream));
-          CHK(nr_reduce_dev(c, y0, cnt, D, D, y1, nullptr, ns));
-          const bool last = k == nr_passes - 1;
-          LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * (last ? 6 : 8),
-                 requant_launch(y1, p.lens, D, cnt, last ? nullptr : y0, last ? yq : nullptr, c->stream));
-        }
-        OdFeArgs b = a;
-        b.pcm = yq;
-        b.clip_stride = D;
-        b.clip_len = D;
-        b.img = static_cast<uint8_t*>(pimg2);
-        LAUNCH(c, MMLA_STAGE_OD_FE, od_fe_bytes(cnt, b), od_fe_launch(b, cnt, c->stream));
-        LAUNCH(c, MMLA_STAGE_OD_FE, (double)cnt * (2.0 * OD_IMG + 4),
-               ssim_u8_launch(a.img, b.img, cnt, OD_H, OD_W, 3, dss, c->stream));
-        net_img = b.img;
-      } else {   // not denoised: the second image is the first, their similarity 1
-        LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * 4, fill_f32_launch(dss, cnt, 1.0f, c->stream));
-      }
-      g.ssim = dss;
-      g.ssim_threshold = ssim_threshold;
+    if (!gated) return od_fe_net(c, p, c0, cnt, dev, probs, argmax, silent);
+    const uint8_t *img, *net_img;
+    CHK(od_image(c, p, cnt, S_IMG, &img));
+    net_img = img;
+    float* dss;
+    CHK(out_ptr(c, ssim, c0, cnt, dev, S_OUT3, &dss));
+    if (!dss) {
+      void* q = nullptr;
+      CHK(ws_get(c, S_SSIM, cnt * sizeof(float), &q));
+      dss = static_cast<float*>(q);
     }
-    CHK(run_od_net(c, net_img, nullptr, cnt, dp, da, g));
-    CHK(copy_back(c, probs, c0 * 2, dp, cnt * 2, dev));
-    CHK(copy_back(c, argmax, c0, da, cnt, dev));
-    CHK(copy_back(c, silent, c0, ds, cnt, dev));
-    if (gated) CHK(copy_back(c, ssim, c0, static_cast<const float*>(dss), cnt, dev));
-    return MMLA_OK;
+    // the gate sees what the front-end sees: the first 24000 samples at most
+    const int D = (int)std::min<int64_t>(clip_len, MMLA_OD_CLIP);
+    if (nr_passes > 0 && D > 0) {
+      // two float clip buffers; the last pass leaves its int16 samples in the first one.  The slack
+      // keeps the front-end's read of a clip whose lens[i] exceeds clip_len inside the buffer
+      const size_t ybytes = (size_t)cnt * D * sizeof(float) + MMLA_OD_CLIP * sizeof(int16_t);
+      void *py0 = nullptr, *py1 = nullptr;
+      CHK(ws_get(c, S_GATE_Y0, ybytes, &py0));
+      CHK(ws_get(c, S_GATE_Y1, ybytes, &py1));
+      int16_t* yq = static_cast<int16_t*>(py0);
+      CHK(gate_passes(c, p, cnt, D, nr_passes, nullptr, ns, static_cast<float*>(py0), static_cast<float*>(py1), yq));
+      CHK(od_image(c, Pcm{yq, D, p.lens, D, p.true_len}, cnt, S_IMG2, &net_img));
+      LAUNCH(c, MMLA_STAGE_OD_FE, (double)cnt * (2.0 * OD_IMG + 4),
+             ssim_u8_launch(img, net_img, cnt, OD_H, OD_W, 3, dss, c->stream));
+    } else {   // not denoised: the second image is the first, their similarity 1
+      LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * 4, fill_f32_launch(dss, cnt, 1.0f, c->stream));
+    }
+    OdGate g;
+    g.ssim = dss;
+    g.ssim_threshold = ssim_threshold;
+    CHK(od_net_out(c, net_img, p, g, c0, cnt, dev, probs, argmax, silent));
+    return copy_back(c, ssim, c0, static_cast<const float*>(dss), cnt, dev);
   });
 }
 
-// SI front-end + network of one micro-batch on the device view p of its clips (p.clip_len: the clips'
-// true length without lens), results into probs / argmax / silent at clip c0 (host mode: staged in
-// the output slots slot_p / slot_a)
+// SI front-end + network of one micro-batch on the device view p of its clips, results into probs /
+// argmax / silent at clip c0 (host mode: staged in the output slots slot_p / slot_a)
 int si_fe_net(mmla_ctx* c, const Pcm& p, int64_t c0, int64_t cnt, bool dev, float* probs,
               int32_t* argmax, uint8_t* silent, int slot_p = S_OUT0, int slot_a = S_OUT1) {
   const int k = c->si.k;
@@ -409,12 +451,7 @@ int si_fe_net(mmla_ctx* c, const Pcm& p, int64_t c0, int64_t cnt, bool dev, floa
   if (!dev && silent) CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT2, &pso));
   void* ps = pso;
   if (!ps) CHK(ws_get(c, S_SILENT, cnt, &ps));
-  SiFeArgs a{};
-  a.pcm = p.p;
-  a.clip_stride = p.stride;
-  a.lens = p.lens;
-  a.clip_len = p.clip_len;
-  a.tables = c->si_tables;
+  SiFeArgs a = si_fe_args(c, p);
   a.feat = static_cast<float*>(pf);
   a.ldf = ldf;
   a.silent = static_cast<uint8_t*>(ps);
@@ -439,8 +476,9 @@ int si_fe_net(mmla_ctx* c, const Pcm& p, int64_t c0, int64_t cnt, bool dev, floa
 // [c0, c0 + cnt) into the context's workspace: q [cnt][clip_len] int16 (the rewritten file, zeros
 // behind it) and kept [cnt].  The noise gate is stateless, the detectors are not: run() copies the
 // micro-batch's streams' VadState aside the first time it sees c0 and puts the copy back when it is
-// called for the same c0 again (a re-run by guarded() or, with fewer clips, by for_microbatches), so
-// the decisions and the state left behind do not depend on whether a re-run happened.
+// called for the same c0 again (for_microbatches repeating the micro-batch with fewer clips after an
+// allocation failure; a guard re-run repeats a network alone and does not come here), so the decisions
+// and the state left behind do not depend on whether a re-run happened.
 struct Conditioner {
   const int16_t* pcm;
   int64_t n, stride;
@@ -493,19 +531,9 @@ struct Conditioner {
     }
     if (nr_passes > 0) {
       CHK(ws_get(c, S_GATE_Y1, (size_t)cnt * D * sizeof(float), &py1));
-      float *y0 = static_cast<float*>(py0), *y1 = static_cast<float*>(py1);
       const int32_t* dprof;
       CHK(in_ptr(c, profile && !ns ? profile + c0 : nullptr, (size_t)cnt, dev, S_NR_PROF, &dprof));
-      LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * 6,
-             pcm_f32_launch(p.p, p.stride, p.lens, D, cnt, y0, c->stream));
-      for (int k = 0; k < nr_passes; ++k) {
-        // a pass re-uses the gate's item table and scratch: the one before it has drained
-        if (k) HIPCHK(c, hipStreamSynchronize(c->stream));
-        CHK(nr_reduce_dev(c, y0, cnt, D, D, y1, dprof, ns));
-        const bool last = k == nr_passes - 1;
-        LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * (last ? 6 : 8),
-               requant_launch(y1, p.lens, D, cnt, last ? nullptr : y0, last ? src : nullptr, c->stream));
-      }
+      CHK(gate_passes(c, p, cnt, D, nr_passes, dprof, ns, static_cast<float*>(py0), static_cast<float*>(py1), src));
     } else {
       LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * D * 4,
              pcm_i16_launch(p.p, p.stride, p.lens, D, cnt, src, c->stream));
@@ -555,42 +583,12 @@ struct Conditioner {
   }
 };
 
-// mmla_condition: FEATURES_* micro-batching (host mode), one pass over the whole batch (device mode)
+// mmla_condition once cd.bad() has passed: FEATURES_* micro-batching (host mode), one pass over the whole
+// batch (device mode)
 int condition_call(mmla_ctx* c, Conditioner& cd, uint32_t flags) {
-  if (!c) return MMLA_E_INVALID;
-  return clip_call(c, FEATURES_OD, cd.n, flags, cd.bad(c, flags & MMLA_DEVICE_PTR),
-                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+  return clip_call(c, FEATURES_OD, cd.n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev) -> int {
     return cd.run(c, c0, cnt, dev);
   }, std::max<int64_t>(cd.ips, 1));
-}
-
-// OD front-end + network on a micro-batch's conditioned clips
-int od_fe_net(mmla_ctx* c, const Conditioner& cd, int64_t c0, int64_t cnt, bool dev, float* probs,
-              int32_t* argmax, uint8_t* silent) {
-  void* pimg = nullptr;
-  CHK(ws_get(c, S_IMG, cnt * OD_IMG, &pimg));
-  OdFeArgs a{};
-  a.pcm = cd.q;
-  a.clip_stride = cd.clip_len;
-  a.lens = cd.kept;
-  a.clip_len = cd.clip_len;
-  a.tables = c->od_tables;
-  a.img = static_cast<uint8_t*>(pimg);
-  LAUNCH(c, MMLA_STAGE_OD_FE, od_fe_bytes(cnt, a), od_fe_launch(a, cnt, c->stream));
-  float* dp;
-  int32_t* da;
-  uint8_t* ds;
-  CHK(out_ptr(c, probs, c0 * 2, cnt * 2, dev, S_OUT0, &dp));
-  CHK(out_ptr(c, argmax, c0, cnt, dev, S_OUT1, &da));
-  CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT2, &ds));
-  OdGate g;
-  g.lens = cd.kept;   // silent = kept_len < 4000
-  g.clip_len = 0;
-  g.silent = ds;
-  CHK(run_od_net(c, a.img, nullptr, cnt, dp, da, g));
-  CHK(copy_back(c, probs, c0 * 2, dp, cnt * 2, dev));
-  CHK(copy_back(c, argmax, c0, da, cnt, dev));
-  return copy_back(c, silent, c0, ds, cnt, dev);
 }
 
 int si_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride, const int32_t* lens,
@@ -600,16 +598,14 @@ int si_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t strid
                    [&](int64_t c0, int64_t cnt, bool dev) -> int {
     Pcm p;
     CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, SI_NEED_SAMPLES, dev || pcm_dev, &p));
-    p.clip_len = lens ? 0 : clip_len;   // the true length decides T even if fewer samples are staged
     return si_fe_net(c, p, c0, cnt, dev, probs, argmax, silent);
   });
 }
 
 // ---- the conditioned pipelines on a Conditioner (mmla_*_pipeline_conditioned, _capture) ------------
 
-enum Which { W_OD, W_SI, W_ROOM };
-
-// the networks' outputs of the three calls: W_OD / W_SI use (probs, argmax), W_ROOM all four
+// the networks' outputs of the three calls: COND_OD / COND_SI use their own (probs, argmax), COND_ROOM
+// all four
 struct NetOut {
   float* od_probs;
   int32_t* od_argmax;
@@ -618,64 +614,39 @@ struct NetOut {
   uint8_t* silent;
 };
 
-const char* missing_weights(const mmla_ctx* c, Which w) {
-  if (w != W_SI && !c->od_loaded) return "OD";
-  if (w != W_OD && !c->si_loaded) return "SI";
-  return nullptr;
-}
-
 // cd.bad() has passed and the weights are loaded
-int conditioned_body(mmla_ctx* c, Which w, Conditioner& cd, const NetOut& o, uint32_t flags) {
-  const bool dev = flags & MMLA_DEVICE_PTR;
+int conditioned_body(mmla_ctx* c, CallKind kind, Conditioner& cd, const NetOut& o, uint32_t flags) {
+  if (kind == FEATURES_OD) return condition_call(c, cd, flags);   // mmla_condition: no network
+  const bool od = kind != COND_SI, si = kind != COND_OD;
   if (cd.off()) {   // nothing to condition: the plain pipelines, then the copies asked for
-    if (w != W_SI)
+    if (od)
       CHK(od_pipeline_common(c, cd.pcm, cd.n, cd.stride, cd.lens, cd.clip_len, false, 0, 0.0f, o.od_probs,
                              o.od_argmax, o.silent, nullptr, flags, cd.pcm_dev));
-    if (w != W_OD)
+    if (si)
       CHK(si_pipeline_common(c, cd.pcm, cd.n, cd.stride, cd.lens, cd.clip_len, o.si_probs, o.si_argmax,
-                             w == W_SI ? o.silent : nullptr, flags, cd.pcm_dev));
+                             od ? nullptr : o.silent, flags, cd.pcm_dev));
     return cd.out_pcm || cd.kept_len ? condition_call(c, cd, flags) : MMLA_OK;
   }
-  const int64_t granule = std::max<int64_t>(cd.ips, 1);
-  if (w == W_OD)
-    return clip_call(c, NET_OD, cd.n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev) -> int {
-      CHK(cd.run(c, c0, cnt, dev));
-      return od_fe_net(c, cd, c0, cnt, dev, o.od_probs, o.od_argmax, o.silent);
-    }, granule);
-  if (w == W_SI)
-    return clip_call(c, NET_SI, cd.n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev) -> int {
-      CHK(cd.run(c, c0, cnt, dev));
-      // the conditioned clips with lens = kept_len (a row holds clip_len samples, zeros behind kept_len)
-      const Pcm p{cd.q, cd.clip_len, cd.kept, 0};
-      return si_fe_net(c, p, c0, cnt, dev, o.si_probs, o.si_argmax, o.silent);
-    }, granule);
-  // Both networks on one conditioning: per micro-batch (whole streams, OD's cap) Conditioner::run once,
-  // then each network's front-end + net under its own range guard, reading the conditioned clips that
-  // stay in S_COND_Q / S_COND_KEPT.  A guard re-run repeats that network alone; an allocation failure
-  // repeats the micro-batch with fewer clips, the detectors restored by Conditioner::run's snapshot.
-  HIPCHK(c, hipSetDevice(c->device));
-  CHK(for_microbatches(c, true, cd.n, [&](int64_t c0, int64_t cnt) -> int {
+  // Per micro-batch (whole streams) Conditioner::run once, then each network's front-end + net under
+  // its own range guard, reading the conditioned clips that stay in S_COND_Q / S_COND_KEPT with lens =
+  // kept_len (a row holds clip_len samples, zeros behind kept_len).  A guard re-run repeats that network
+  // alone; an allocation failure repeats the micro-batch with fewer clips, the detectors restored by
+  // Conditioner::run's snapshot.  With OD in the call, 'silent' (kept_len < 4000) is its gate's: SI's own
+  // flag, the same rule, stays in the workspace, and SI's outputs are staged in slots of their own.
+  return clip_call(c, kind, cd.n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev) -> int {
     CHK(cd.run(c, c0, cnt, dev));
-    CHK(guarded(c, dev, c->od_f32_only, [&]() -> int {
-      return od_fe_net(c, cd, c0, cnt, dev, o.od_probs, o.od_argmax, o.silent);
-    }));
-    CHK(guarded(c, dev, c->si_f32_only, [&]() -> int {
-      // the conditioned clips with lens = kept_len, as mmla_si_pipeline_conditioned reads them; its
-      // 'silent' (kept_len < 4000, the rule of OD's gate) stays in the workspace
-      const Pcm p{cd.q, cd.clip_len, cd.kept, 0};
-      return si_fe_net(c, p, c0, cnt, dev, o.si_probs, o.si_argmax, nullptr, S_ROOM_P, S_ROOM_A);
-    }));
-    if (!dev) HIPCHK(c, hipStreamSynchronize(c->stream));
+    const Pcm p{cd.q, cd.clip_len, cd.kept, cd.clip_len, 0};
+    if (od)
+      CHK(guarded(c, dev, c->od_f32_only, [&]() -> int {
+        return od_fe_net(c, p, c0, cnt, dev, o.od_probs, o.od_argmax, o.silent);
+      }));
+    if (si)
+      CHK(guarded(c, dev, c->si_f32_only, [&]() -> int {
+        return si_fe_net(c, p, c0, cnt, dev, o.si_probs, o.si_argmax, od ? nullptr : o.silent,
+                         od ? S_ROOM_P : S_OUT0, od ? S_ROOM_A : S_OUT1);
+      }));
     return MMLA_OK;
-  }, granule));
-  return finish(c, dev);
-}
-
-int conditioned_call(mmla_ctx* c, Which w, Conditioner& cd, const NetOut& o, uint32_t flags) {
-  if (!c) return MMLA_E_INVALID;
-  if (const char* bad = cd.bad(c, flags & MMLA_DEVICE_PTR)) return fail(c, MMLA_E_INVALID, "%s", bad);
-  if (const char* m = missing_weights(c, w)) return fail(c, MMLA_E_NOWEIGHTS, "%s weights not loaded", m);
-  return conditioned_body(c, w, cd, o, flags);
+  }, std::max<int64_t>(cd.ips, 1));
 }
 
 // ---- a room's capture format in front of the conditioned pipelines ----------------------------------
@@ -791,32 +762,43 @@ struct Capture {
   }
 };
 
-// mmla_{od,si,room}_pipeline_capture: every check first (the capture's, mmla_condition's, the weights),
-// then the conversion of all clips once, then the conditioned pipeline on the converted clips, which
-// stay in the context's capture buffers
-int capture_pipeline(mmla_ctx* c, Which w, const int16_t* pcm, int64_t n, int64_t stride,
+// mmla_condition (kind FEATURES_OD) and mmla_{od,si,room}_pipeline_conditioned.  cap: the _capture calls,
+// whose arguments describe the converted clips (the pointers only as non-null marks) -- every check first,
+// then the conversion of all clips once, then the conditioned pipeline on the converted clips, which stay
+// in the context's capture buffers
+int conditioned_call(mmla_ctx* c, CallKind kind, const Capture* cap, const int16_t* pcm, int64_t n,
+                     int64_t stride, const int32_t* lens, int32_t clip_len, const int32_t* profile,
+                     int32_t nr_passes, int32_t silence_remove, int64_t ips, int16_t* out_pcm,
+                     int32_t* kept_len, const NetOut& o, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  const bool dev = flags & MMLA_DEVICE_PTR;
+  Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, ips, out_pcm, kept_len,
+                 (flags & MMLA_NR_NONSTATIONARY) != 0};
+  if (const char* bad = cd.bad(c, dev)) return fail(c, MMLA_E_INVALID, "%s", bad);
+  if (const char* m = missing_weights(c, kind)) return fail(c, MMLA_E_NOWEIGHTS, "%s weights not loaded", m);
+  if (cap) {
+    HIPCHK(c, hipSetDevice(c->device));
+    void *pout = nullptr, *plens = nullptr;
+    CHK(cap_get(c, CB_OUT, (size_t)n * clip_len * sizeof(int16_t), &pout));
+    CHK(cap_get(c, CB_LENS, (size_t)n * sizeof(int32_t), &plens));
+    CHK(cap->run(c, dev, static_cast<int16_t*>(pout), clip_len, static_cast<int32_t*>(plens)));
+    cd.pcm = static_cast<const int16_t*>(pout);
+    cd.lens = static_cast<const int32_t*>(plens);
+    cd.pcm_dev = true;
+  }
+  return conditioned_body(c, kind, cd, o, flags);
+}
+
+int capture_pipeline(mmla_ctx* c, CallKind kind, const int16_t* pcm, int64_t n, int64_t stride,
                      const int32_t* frames, int32_t clip_frames, const int32_t* profile, int32_t nr_passes,
                      int32_t silence_remove, int64_t ips, int16_t* out_pcm, int32_t* kept_len,
                      const NetOut& o, uint32_t flags) {
   if (!c) return MMLA_E_INVALID;
-  const bool dev = flags & MMLA_DEVICE_PTR;
   Capture cap{pcm, n, stride, frames, clip_frames, ips, false};
-  if (const char* bad = cap.bad(c, dev)) return fail(c, MMLA_E_INVALID, "%s", bad);
+  if (const char* bad = cap.bad(c, flags & MMLA_DEVICE_PTR)) return fail(c, MMLA_E_INVALID, "%s", bad);
   const int32_t L = cap.out_clip_len;
-  // the checks of mmla_condition on the converted clips' geometry (the pointers only as non-null marks)
-  Conditioner cd{pcm, n, L, nullptr, L, profile, nr_passes, silence_remove, ips, out_pcm, kept_len,
-                 (flags & MMLA_NR_NONSTATIONARY) != 0};
-  if (const char* bad = cd.bad(c, dev)) return fail(c, MMLA_E_INVALID, "%s", bad);
-  if (const char* m = missing_weights(c, w)) return fail(c, MMLA_E_NOWEIGHTS, "%s weights not loaded", m);
-  HIPCHK(c, hipSetDevice(c->device));
-  void *pout = nullptr, *plens = nullptr;
-  CHK(cap_get(c, CB_OUT, (size_t)n * L * sizeof(int16_t), &pout));
-  CHK(cap_get(c, CB_LENS, (size_t)n * sizeof(int32_t), &plens));
-  CHK(cap.run(c, dev, static_cast<int16_t*>(pout), L, static_cast<int32_t*>(plens)));
-  cd.pcm = static_cast<const int16_t*>(pout);
-  cd.lens = static_cast<const int32_t*>(plens);
-  cd.pcm_dev = true;
-  return conditioned_body(c, w, cd, o, flags);
+  return conditioned_call(c, kind, &cap, pcm, n, L, nullptr, L, profile, nr_passes, silence_remove, ips,
+                          out_pcm, kept_len, o, flags);
 }
 
 }  // namespace
@@ -843,12 +825,7 @@ int mmla_si_features(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
                    [&](int64_t c0, int64_t cnt, bool dev) -> int {
     Pcm p;
     CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, SI_NEED_SAMPLES, dev, &p));
-    SiFeArgs a{};
-    a.pcm = p.p;
-    a.clip_stride = p.stride;
-    a.lens = p.lens;
-    a.clip_len = lens ? 0 : clip_len;   // true length decides T even if fewer samples are staged
-    a.tables = c->si_tables;
+    SiFeArgs a = si_fe_args(c, p);
     CHK(out_ptr(c, feat, c0 * SI_T * SI_D, cnt * SI_T * SI_D, dev, S_OUT0, &a.feat));
     CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT1, &a.silent));
     LAUNCH(c, MMLA_STAGE_SI_FE, si_fe_bytes(cnt, a), si_fe_launch(a, cnt, c->stream));
@@ -958,9 +935,8 @@ int mmla_si_pipeline(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
 int mmla_condition(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride, const int32_t* lens,
                    int32_t clip_len, const int32_t* profile, int32_t nr_passes, int32_t silence_remove,
                    int64_t items_per_stream, int16_t* out_pcm, int32_t* kept_len, uint32_t flags) {
-  Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, items_per_stream,
-                 out_pcm, kept_len, (flags & MMLA_NR_NONSTATIONARY) != 0};
-  return condition_call(c, cd, flags);
+  return conditioned_call(c, FEATURES_OD, nullptr, pcm, n, stride, lens, clip_len, profile, nr_passes,
+                          silence_remove, items_per_stream, out_pcm, kept_len, NetOut{}, flags);
 }
 
 int mmla_od_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
@@ -968,9 +944,9 @@ int mmla_od_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, int
                                  int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
                                  int16_t* out_pcm, int32_t* kept_len, float* probs, int32_t* argmax,
                                  uint8_t* silent, uint32_t flags) {
-  Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, items_per_stream,
-                 out_pcm, kept_len, (flags & MMLA_NR_NONSTATIONARY) != 0};
-  return conditioned_call(c, W_OD, cd, NetOut{probs, argmax, nullptr, nullptr, silent}, flags);
+  return conditioned_call(c, COND_OD, nullptr, pcm, n, stride, lens, clip_len, profile, nr_passes,
+                          silence_remove, items_per_stream, out_pcm, kept_len,
+                          NetOut{probs, argmax, nullptr, nullptr, silent}, flags);
 }
 
 int mmla_si_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
@@ -978,9 +954,9 @@ int mmla_si_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, int
                                  int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
                                  int16_t* out_pcm, int32_t* kept_len, float* probs, int32_t* argmax,
                                  uint8_t* silent, uint32_t flags) {
-  Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, items_per_stream,
-                 out_pcm, kept_len, (flags & MMLA_NR_NONSTATIONARY) != 0};
-  return conditioned_call(c, W_SI, cd, NetOut{nullptr, nullptr, probs, argmax, silent}, flags);
+  return conditioned_call(c, COND_SI, nullptr, pcm, n, stride, lens, clip_len, profile, nr_passes,
+                          silence_remove, items_per_stream, out_pcm, kept_len,
+                          NetOut{nullptr, nullptr, probs, argmax, silent}, flags);
 }
 
 // Both detectors on one conditioning (conditioned_body)
@@ -990,9 +966,9 @@ int mmla_room_pipeline_conditioned(mmla_ctx* c, const int16_t* pcm, int64_t n, i
                                    int16_t* out_pcm, int32_t* kept_len, float* od_probs,
                                    int32_t* od_argmax, float* si_probs, int32_t* si_argmax,
                                    uint8_t* silent, uint32_t flags) {
-  Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, items_per_stream,
-                 out_pcm, kept_len, (flags & MMLA_NR_NONSTATIONARY) != 0};
-  return conditioned_call(c, W_ROOM, cd, NetOut{od_probs, od_argmax, si_probs, si_argmax, silent}, flags);
+  return conditioned_call(c, COND_ROOM, nullptr, pcm, n, stride, lens, clip_len, profile, nr_passes,
+                          silence_remove, items_per_stream, out_pcm, kept_len,
+                          NetOut{od_probs, od_argmax, si_probs, si_argmax, silent}, flags);
 }
 
 // ---- a room's capture format (resample.hip capture_*_kernel) ----------------------------------------
@@ -1082,7 +1058,7 @@ int mmla_od_pipeline_capture(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t
                              int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
                              int16_t* out_pcm, int32_t* kept_len, float* probs, int32_t* argmax,
                              uint8_t* silent, uint32_t flags) {
-  return capture_pipeline(c, W_OD, pcm, n, stride, frames, clip_frames, profile, nr_passes, silence_remove,
+  return capture_pipeline(c, COND_OD, pcm, n, stride, frames, clip_frames, profile, nr_passes, silence_remove,
                           items_per_stream, out_pcm, kept_len, NetOut{probs, argmax, nullptr, nullptr, silent},
                           flags);
 }
@@ -1092,7 +1068,7 @@ int mmla_si_pipeline_capture(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t
                              int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
                              int16_t* out_pcm, int32_t* kept_len, float* probs, int32_t* argmax,
                              uint8_t* silent, uint32_t flags) {
-  return capture_pipeline(c, W_SI, pcm, n, stride, frames, clip_frames, profile, nr_passes, silence_remove,
+  return capture_pipeline(c, COND_SI, pcm, n, stride, frames, clip_frames, profile, nr_passes, silence_remove,
                           items_per_stream, out_pcm, kept_len, NetOut{nullptr, nullptr, probs, argmax, silent},
                           flags);
 }
@@ -1102,7 +1078,7 @@ int mmla_room_pipeline_capture(mmla_ctx* c, const int16_t* pcm, int64_t n, int64
                                int32_t nr_passes, int32_t silence_remove, int64_t items_per_stream,
                                int16_t* out_pcm, int32_t* kept_len, float* od_probs, int32_t* od_argmax,
                                float* si_probs, int32_t* si_argmax, uint8_t* silent, uint32_t flags) {
-  return capture_pipeline(c, W_ROOM, pcm, n, stride, frames, clip_frames, profile, nr_passes, silence_remove,
+  return capture_pipeline(c, COND_ROOM, pcm, n, stride, frames, clip_frames, profile, nr_passes, silence_remove,
                           items_per_stream, out_pcm, kept_len,
                           NetOut{od_probs, od_argmax, si_probs, si_argmax, silent}, flags);
 }

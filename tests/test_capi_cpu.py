@@ -40,6 +40,31 @@ def test_shim_signatures_cover_header():
     from mmla_audio_amd import _lib
     declared = set(declared_symbols()) - {'mmla_last_error'}
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
+    # ... and with the header's parameter list: the same count, and per parameter the same class
+    # (pointer, int64_t, int32_t / int, uint32_t, float, double)
+    src = re.sub(r'/\*.*?\*/|//[^\n]*', '', open(HEADER).read(), flags=re.S)
+    protos = dict(re.findall(r'^\s*int\s+(mmla_\w+)\s*\(([^)]*)\)\s*;', src, re.M))
+    assert declared <= set(protos)
+    scalars = {'int64_t': 'i64', 'int32_t': 'i32', 'int': 'i32', 'uint32_t': 'u32', 'float': 'f32',
+               'double': 'f64'}
+
+    def header_class(param):
+        if '*' in param:
+            return 'ptr'
+        words = [w for w in param.split() if w != 'const']
+        assert len(words) == 2 and words[0] in scalars, param      # type, name
+        return scalars[words[0]]
+
+    def shim_class(t):
+        if t is ctypes.c_void_p or issubclass(t, ctypes._Pointer):
+            return 'ptr'
+        return {ctypes.c_int64: 'i64', ctypes.c_int32: 'i32', ctypes.c_int: 'i32', ctypes.c_uint32: 'u32',
+                ctypes.c_float: 'f32', ctypes.c_double: 'f64'}[t]
+
+    for name in sorted(declared):
+        params = [p.strip() for p in protos[name].split(',')]
+        params = [] if params in ([''], ['void']) else params
+        assert [header_class(p) for p in params] == [shim_class(t) for t in _lib.SIGNATURES[name]], name
 
 
 def test_abi_version(lib):

@@ -195,3 +195,35 @@ def test_zeroed_tail_matters(ctx, clips):
     print('gated', s, 'exactly 12000 samples', s_s, 'diff', abs(float(s[0]) - float(s_s[0])))
     assert silent[0] == silent_s[0] and am[0] == am_s[0]
     assert abs(float(s[0]) - float(s_s[0])) <= ORACLE_BOUND
+
+
+def test_launch_plan_over_the_plain_pipeline(ctx, clips):
+    """what the gate adds to od_pipeline's launches and algorithmic work on the same clips (no lens, D =
+    min(clip_len, 24000) samples per clip): per pass one gate launch (8 n D) and one PCM_16 round trip (8 n
+    D, the last one to int16: 6 n D) behind the float conversion (6 n D), then the second image (reads 2 D
+    bytes, writes an image per clip) and the SSIM (reads two images, writes a float per clip); without a
+    pass only the fill of the SSIM output with 1"""
+    n, D, img = len(clips), min(CLIP, _lib.OD_CLIP), _lib.OD_MELS * _lib.OD_FRAMES * 3
+
+    def profile(fn):
+        ctx.profile_enable(True)
+        try:
+            ctx.profile_read(reset=True)
+            fn()
+            return {k: v[1:] for k, v in ctx.profile_read(reset=True).items()}
+        finally:
+            ctx.profile_enable(False)
+
+    plain = profile(lambda: ctx.od_pipeline(clips))
+    for p in (2, 0):
+        gated = profile(lambda: ctx.od_pipeline_gated(clips, passes=p, threshold=THRESHOLD))
+        delta = {k: (gated[k][0] - plain[k][0], gated[k][1] - plain[k][1]) for k in plain}
+        print('passes', p, 'plain', plain, 'gated', gated)
+        want = dict.fromkeys(plain, (0, 0))
+        if p:
+            want['nr'] = (p, 8 * n * D * p)
+            want['glue'] = (1 + p, n * D * (8 * p + 4))
+            want['od_fe'] = (2, n * (2 * D + img) + n * (2 * img + 4))
+        else:
+            want['glue'] = (1, 4 * n)
+        assert delta == want, (p, delta)

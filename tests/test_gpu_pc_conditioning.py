@@ -175,9 +175,9 @@ def _debug_ctx(monkeypatch, name, value):
 
 
 def test_split_lstm_rerun_keeps_vad_state(monkeypatch, ctx, clips, noises):
-    """MMLA_DEBUG_LSTM_SPIN=-1: every micro-batch of a host call runs twice (the split BiLSTM gives up,
-    the unsplit one repeats it), the conditioning with it: the detectors must start the re-run from
-    where the micro-batch found them.  Two consecutive calls: the second shows the state left behind."""
+    """MMLA_DEBUG_LSTM_SPIN=-1: the network of every micro-batch of a host call runs twice (the split
+    BiLSTM gives up, the unsplit one repeats it) on the conditioning already made, which is not repeated:
+    the detectors must have advanced once.  Two consecutive calls: the second shows the state left behind."""
     dbg = _debug_ctx(monkeypatch, 'MMLA_DEBUG_LSTM_SPIN', '-1')
     for c in (ctx, dbg):
         c.nr_set_noise_bank(noises)
@@ -192,6 +192,31 @@ def test_split_lstm_rerun_keeps_vad_state(monkeypatch, ctx, clips, noises):
             _same(res[1], res[0], (kind, call))
     f32_reruns, split_reruns = dbg.debug_counters()
     assert f32_reruns == 0 and split_reruns >= 8, (f32_reruns, split_reruns)
+
+
+def test_f32_rerun_of_a_conditioned_call(clips, noises):
+    """OD weights whose block-4 BatchNorm drives its conv input past the fp16 range (the recipe of
+    test_gpu_range_guard._hot_od): every micro-batch of a host call trips the range guard and is re-run
+    in exact f32.  Every output of two consecutive calls (the second shows the state left behind) equals,
+    byte for byte, a context with the same weights that runs exact f32 throughout."""
+    W = weights.synthetic(weights.OD, seed=5)
+    W['layer_with_weights-14/gamma'] = W['layer_with_weights-14/gamma'] * 2.0e5
+    W['layer_with_weights-14/beta'] = np.abs(W['layer_with_weights-14/beta']) * 2.0e5
+    hot, exact = _new_ctx(load=False), _new_ctx(load=False)
+    for c in (hot, exact):
+        c.load_weights(weights.OD, weights.pack(weights.OD, W), 2)
+        c.nr_set_noise_bank(noises)
+        c.vad_reset(3, 3)
+        c.set_microbatch(od=4)           # 4 + 2 clips
+    exact.set_precision(_lib.PREC_F32)
+    for call in (0, 1):
+        want = exact.od_pipeline_conditioned(clips, LENS, PROFILE, 1, True, 2, return_pcm=True)
+        got = hot.od_pipeline_conditioned(clips, LENS, PROFILE, 1, True, 2, return_pcm=True)
+        assert np.isfinite(got[0]).all()
+        _same(got, want, call)
+    print('debug counters: guarded', hot.debug_counters(), 'exact', exact.debug_counters())
+    assert hot.debug_counters() == (4, 0)            # 2 calls x 2 micro-batches, no split re-run
+    assert exact.debug_counters() == (0, 0)
 
 
 def test_oom_retry_keeps_vad_state(monkeypatch, ctx, clips):

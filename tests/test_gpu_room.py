@@ -236,6 +236,24 @@ def test_the_conditioning_runs_once(ctxs, ticks, noises):
     assert cond[0] > 0 and od[0] == cond[0] and si[0] == cond[0]
     assert room[0] == od[0]
     assert room[1] == od[1] + si[1] - cond[1]
+    # the conditioning's own plan, in absolute numbers: one micro-batch of N <= 512 clips of L samples, p
+    # passes and silence removal -- one gate launch per pass (8 N L each); glue: the float conversion (6 N L),
+    # a PCM_16 round trip per pass (8 N L, the last one to int16: 6 N L), the detector and the collector
+    # (N L each), the tail fill (2 N L)
+    for p in (1, 3):
+        od_ctx.nr_set_noise_bank(noises)
+        od_ctx.vad_reset(STREAMS, 3)
+        od_ctx.profile_enable(True)
+        try:
+            od_ctx.profile_read(reset=True)
+            od_ctx.condition(x, LENS, MIC, p, True, IPS)
+            prof = od_ctx.profile_read(reset=True)
+        finally:
+            od_ctx.profile_enable(False)
+        print('condition alone, passes', p, {k: v[1:] for k, v in prof.items()})
+        assert prof['nr'][1:] == (p, 8 * N * L * p)
+        assert prof['glue'][1:] == (p + 4, N * L * (8 * p + 8))
+        assert all(prof[s][1] == 0 for s in _lib.STAGES if s not in ('nr', 'glue'))
 
 
 def test_misuse(ticks, noises):
