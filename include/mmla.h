@@ -197,6 +197,25 @@ int mmla_si_features(mmla_ctx* ctx, const int16_t* pcm, int64_t n_clips, int64_t
 int mmla_si_features_seq(mmla_ctx* ctx, const int16_t* pcm, int64_t n_samples, int64_t n_windows,
                          float* feat, uint32_t flags);
 
+/*
+ * mmla_si_features_seq on a ragged batch of signals in one launch: the front-end of registration, where
+ * every speaker's recording is cut into 256-frame windows (make_feature_experiment,
+ * speaker_identification.py:317-369).  Signal i = pcm + i * stride has lens[i] samples (nullable:
+ * clip_len; stride >= clip_len for more than one signal).  With T(n) = 1 for 1 <= n <= 400, else
+ * 1 + ceil((n - 400) / 160), w_max = ceil(T(clip_len) / 256):
+ *   feat [n_signals, w_max, 256, 39] f32: window w < n_windows[i] = ceil(T(lens[i]) / 256) holds exactly
+ *     what mmla_si_features_seq gives for that signal alone (global frames [256 w, 256 w + 256), deltas
+ *     edge-padded at the signal's own ends, zero rows past its last frame); every other window, and
+ *     every window of a signal with lens[i] == 0, is all zeros;
+ *   n_windows [n_signals] i32 (nullable), 0 for an empty signal.
+ * Host or device pointers (MMLA_DEVICE_PTR).  MMLA_E_INVALID: clip_len < 1, a host lens[i] outside
+ * [0, clip_len] or above the stride (device pointers: clamped into [0, clip_len] by the kernel, the
+ * convention of the VAD's lens).
+ */
+int mmla_si_features_seq_batch(mmla_ctx* ctx, const int16_t* pcm, int64_t n_signals, int64_t stride,
+                               const int32_t* lens, int32_t clip_len, float* feat, int32_t* n_windows,
+                               uint32_t flags);
+
 /* OD-NET predict on float NHWC [n,128,151,3] (values 0..255) -> probs [n,2]
  * (model.predict, record_on_pc.py:159). */
 int mmla_od_forward(mmla_ctx* ctx, const float* x_nhwc, int64_t n, float* probs, uint32_t flags);
@@ -457,6 +476,46 @@ int mmla_room_pipeline_conditioned(mmla_ctx* ctx, const int16_t* pcm, int64_t n_
                                    int16_t* out_pcm, int32_t* kept_len, float* od_probs,
                                    int32_t* od_argmax, float* si_probs, int32_t* si_argmax,
                                    uint8_t* silent, uint32_t flags);
+
+/*
+ * Speaker registration in a room, step 2 of the reference's manual: every speaker's recording (a
+ * one-minute paragraph: SpeakerIdentification/scripts/record_on_pc.py:44-71,300-346) conditioned, cut
+ * into 256-frame windows and embedded (make_feature_experiment and the frozen base of transfer_learning,
+ * speaker_identification.py:317-369,401-432) on the context the room ticks on, in one call.
+ *
+ * mmla_si_enrol_embed: the conditioning is mmla_condition's with items_per_stream = 1 -- the gate passes
+ *   against profile[c] of the context's bank (or MMLA_NR_NONSTATIONARY), the PCM_16 round trip per pass,
+ *   lens, zeros behind kept_len -- with two differences.  clip_len may reach MMLA_ENROL_MAX_SAMPLES (the
+ *   gate works chunk by chunk, as mmla_nr_reduce does for a long signal).  Silence removal runs on fresh,
+ *   temporary detectors of mode vad_mode, one per recording: the context's mmla_vad_reset detectors, the
+ *   capture converters and the noise bank are not touched.  (A stated deviation: the reference has one
+ *   module-level Vad(3) for everything; a detector per recording is the room's detector per microphone.)
+ *   Then mmla_si_features_seq_batch on the conditioned int16 with lens = kept_len, on the device, and
+ *   SI-NET up to the BiLSTM output (mmla_si_embed's path, range guard and re-run policy) on all
+ *   n_rec * w_max windows, w_max = ceil(T(clip_len) / 256).
+ *   emb [n_rec, w_max, 512] f32: rows at or past n_windows[i] are the network's output on zero features
+ *   and carry no meaning.  out_pcm [n_rec, clip_len] i16, kept_len [n_rec], n_windows [n_rec]: nullable.
+ *   The result does not depend on mmla_set_microbatch (SI's size counts recordings per conditioning and
+ *   windows per network pass; recordings are independent and the detectors fresh, so a repeated
+ *   micro-batch starts again).  MMLA_E_INVALID: what mmla_condition rejects except its 600000 limit,
+ *   clip_len > MMLA_ENROL_MAX_SAMPLES, vad_mode outside 0..3, a null emb; MMLA_E_NOWEIGHTS without SI
+ *   weights; every check comes before any state moves.  With MMLA_DEVICE_PTR the call synchronises the
+ *   context stream internally (its last launches are still only enqueued).
+ * mmla_si_set_head: replaces the Dense head of the loaded SI model in place (the customized_dense of
+ *   speaker_identification.py:407-432, or any Dense(K)): w [512, K], b [K], host pointers as for
+ *   mmla_load_weights; head = MMLA_HEAD_SOFTMAX or MMLA_HEAD_SIGMOID.  Waits for the context stream,
+ *   prepares the head exactly as mmla_load_weights does (the 3xFP16 split at the tensor's own scale; a
+ *   non-finite tensor makes the whole model run exact f32, a finite one afterwards lifts that again
+ *   unless the base itself is non-finite) and frees the old one: every later call gives the bits
+ *   mmla_load_weights of the full blob with that head would give, without re-uploading the base.
+ *   MMLA_E_NOWEIGHTS without an SI model; MMLA_E_INVALID: n_classes < 1, an unknown head, null pointers.
+ */
+#define MMLA_ENROL_MAX_SAMPLES 1966080 /* 4096 detector frames of 480 samples: the VAD's item limit */
+int mmla_si_enrol_embed(mmla_ctx* ctx, const int16_t* pcm, int64_t n_rec, int64_t stride,
+                        const int32_t* lens, int32_t clip_len, const int32_t* profile, int32_t nr_passes,
+                        int32_t silence_remove, int32_t vad_mode, int16_t* out_pcm, int32_t* kept_len,
+                        int32_t* n_windows, float* emb, uint32_t flags);
+int mmla_si_set_head(mmla_ctx* ctx, const float* w, const float* b, int32_t n_classes, int32_t head);
 
 /*
  * Rate conversion of the offline pre-conditioning (resample.hip).

@@ -25,6 +25,18 @@ PREC_F32, PREC_F16X3 = 0, 1
 OD_MELS, OD_FRAMES, OD_CLIP = 128, 151, 24000
 SI_FRAMES, SI_DIMS, SI_SILENT_LEN = 256, 39, 4000
 SI_EMBED, SI_TRAIN_MAX_CLASSES = 512, 32
+ENROL_MAX_SAMPLES = 1966080
+
+
+def si_seq_frames(n):
+    """psf's frame count T(n) of a signal of n >= 1 samples (400-sample frames, step 160)"""
+    n = int(n)
+    return 1 if n <= 400 else 1 + -(-(n - 400) // 160)
+
+
+def si_seq_windows(n):
+    """256-frame windows of a signal of n samples: ceil(T(n) / 256), 0 for an empty signal"""
+    return -(-si_seq_frames(n) // SI_FRAMES) if int(n) > 0 else 0
 
 MMLA_E_RANGE = -6
 _ERRORS = {-1: 'MMLA_E_INVALID', -2: 'MMLA_E_HIP', -3: 'MMLA_E_NOWEIGHTS', -4: 'MMLA_E_OOM',
@@ -76,6 +88,9 @@ SIGNATURES = {
     'mmla_od_features_f32': [_P, _P, _I64, _I64, _P, _I32, _P, _P, _P, _P, _U32],
     'mmla_si_features': [_P, _P, _I64, _I64, _P, _I32, _P, _P, _U32],
     'mmla_si_features_seq': [_P, _P, _I64, _I64, _P, _U32],
+    'mmla_si_features_seq_batch': [_P, _P, _I64, _I64, _P, _I32, _P, _P, _U32],
+    'mmla_si_enrol_embed': [_P, _P, _I64, _I64, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _U32],
+    'mmla_si_set_head': [_P, _P, _P, _I32, _I32],
     'mmla_od_forward': [_P, _P, _I64, _P, _U32],
     'mmla_od_forward_u8': [_P, _P, _I64, _P, _U32],
     'mmla_si_forward': [_P, _P, _I64, _P, _U32],
@@ -549,6 +564,50 @@ class Context:
                     'mmla_si_features_seq')
         return feat
 
+    def si_features_seq_batch(self, pcm, lens=None):
+        """si_features_seq of a ragged batch in one launch: int16 [n, L] with lens (or a list of
+        signals) -> (float32 [n, w_max, 256, 39], n_windows int32 [n]); w_max = si_seq_windows(L).
+        Window w < n_windows[i] is what si_features_seq gives for signal i alone, every other zeros."""
+        a, ln, L = self._pcm(pcm, lens)
+        n = a.shape[0]
+        feat = np.empty((n, si_seq_windows(L), SI_FRAMES, SI_DIMS), np.float32)
+        nw = np.empty(n, np.int32)
+        self._check(self.lib.mmla_si_features_seq_batch(self.h, _ptr(a), n, a.shape[1], _ptr(ln), L,
+                                                        _ptr(feat), _ptr(nw), 0),
+                    'mmla_si_features_seq_batch')
+        return feat, nw
+
+    def si_enrol_embed(self, pcm, lens=None, profile=None, passes=1, silence_remove=True, vad_mode=3,
+                       nonstationary=False, return_pcm=False):
+        """Registration recordings int16 [n, L] (or a list; L up to ENROL_MAX_SAMPLES) -> (emb float32
+        [n, w_max, 512], n_windows [n], kept_len [n][, conditioned int16 [n, L]]): condition() with one
+        fresh temporary detector of mode vad_mode per recording (the vad_reset detectors are left
+        alone), si_features_seq_batch of the conditioned recordings, si_embed of every window.  Rows of
+        emb at or past n_windows[i] carry no meaning."""
+        a, ln, L = self._pcm(pcm, lens)
+        n = a.shape[0]
+        pr = self._profile(profile, n)
+        emb = np.empty((n, si_seq_windows(L), SI_EMBED), np.float32)
+        nw = np.empty(n, np.int32)
+        kept = np.empty(n, np.int32)
+        out = np.empty((n, L), np.int16) if return_pcm else None
+        self._check(self.lib.mmla_si_enrol_embed(
+            self.h, _ptr(a), n, a.shape[1], _ptr(ln), L, _ptr(pr), int(passes), int(bool(silence_remove)),
+            int(vad_mode), _ptr(out), _ptr(kept), _ptr(nw), _ptr(emb), _ns(nonstationary)),
+            'mmla_si_enrol_embed')
+        return (emb, nw, kept, out) if return_pcm else (emb, nw, kept)
+
+    def si_set_head(self, w, b, head=HEAD_SIGMOID):
+        """Replace the Dense head of the loaded SI model in place: w [512, K], b [K] (host arrays)."""
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        if w.ndim != 2 or w.shape[0] != SI_EMBED or b.shape != (w.shape[1],):
+            raise ValueError(f'w {w.shape} / b {b.shape}: expected [512,K] and [K]')
+        k = w.shape[1]
+        self._check(self.lib.mmla_si_set_head(self.h, _ptr(w) if k else None, _ptr(b) if k else None, k,
+                                              int(head)), 'mmla_si_set_head')
+        self.si_classes = int(k)
+
     def od_forward(self, x):
         x = np.ascontiguousarray(x)
         n = x.shape[0]
@@ -908,6 +967,20 @@ class Context:
         self._check(self.lib.mmla_si_features(self.h, pcm, n, stride, lens or None, clip_len, feat,
                                               silent or None, MMLA_DEVICE_PTR),
                     'mmla_si_features(dev)')
+
+    def si_features_seq_batch_dev(self, pcm, n, stride, clip_len, feat, n_windows=0, lens=0):
+        """lens: device int32 [n] (0: clip_len each); entries outside [0, clip_len] are clamped"""
+        self._check(self.lib.mmla_si_features_seq_batch(self.h, pcm, n, stride, lens or None, clip_len, feat,
+                                                        n_windows or None, MMLA_DEVICE_PTR),
+                    'mmla_si_features_seq_batch(dev)')
+
+    def si_enrol_embed_dev(self, pcm, n, stride, clip_len, emb, passes=1, silence_remove=True, vad_mode=3,
+                           out_pcm=0, kept_len=0, n_windows=0, lens=0, profile=0, nonstationary=False):
+        """synchronises the context stream internally (see mmla.h)"""
+        self._check(self.lib.mmla_si_enrol_embed(
+            self.h, pcm, n, stride, lens or None, clip_len, profile or None, int(passes),
+            int(bool(silence_remove)), int(vad_mode), out_pcm or None, kept_len or None, n_windows or None,
+            emb, MMLA_DEVICE_PTR | _ns(nonstationary)), 'mmla_si_enrol_embed(dev)')
 
     def od_pipeline_dev(self, pcm, n, stride, clip_len, probs=0, argmax=0, lens=0, silent=0):
         self._check(self.lib.mmla_od_pipeline(self.h, pcm, n, stride, lens or None, clip_len,

@@ -277,6 +277,7 @@ int mmla_destroy(mmla_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   free_allocs(c->od_allocs);
   free_allocs(c->si_allocs);
+  free_allocs(c->si_head_allocs);
   for (size_t i = 0; i < c->ws.size(); ++i)
     if (c->ws[i]) (void)hipFree(static_cast<char*>(c->ws[i]) - c->ws_guard[i]);
   if (c->od_tables) (void)hipFree(c->od_tables);

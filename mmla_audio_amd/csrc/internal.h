@@ -113,6 +113,9 @@ struct mmla_ctx {
   mmla::OdNet od;
   mmla::SiNet si;
   std::vector<void*> od_allocs, si_allocs;
+  // the SI Dense head's tensors, apart from the frozen base's in si_allocs: mmla_si_set_head frees and
+  // replaces them alone
+  std::vector<void*> si_head_allocs;
   std::vector<void*> ws;
   std::vector<size_t> ws_size;
   std::vector<size_t> ws_guard;   // MMLA_WS_GUARD: guard bytes before and after each slot (0 = none)
@@ -182,7 +185,8 @@ struct mmla_ctx {
   int64_t lstm_split_reruns = 0;
   int64_t range_reruns = 0;
   bool od_f32_only = false, si_f32_only = false;   // weights outside the fp16 range
-  bool loading_f16_bad = false;                     // mmla_load_weights scratch
+  bool loading_f16_bad = false;                     // mmla_load_weights / mmla_si_set_head scratch
+  bool si_base_f16_bad = false;   // a non-finite tensor below the SI head (si_f32_only = this or the head's)
   // mmla_vad_reset: webrtcvad.Vad(mode) per stream (device), [2 * vad_streams]: the second half
   // holds the states a conditioned micro-batch started from, for its re-runs (pipeline.cpp)
   VadState* vad_state = nullptr;
@@ -251,7 +255,8 @@ enum Slot {
   S_TRAIN,  // mmla_si_head_fit: every host-pointer operand, carved from one slot
   S_IMG2, S_GATE_Y0, S_GATE_Y1, S_SSIM,   // mmla_od_pipeline_gated / mmla_ssim_u8
   S_NR_PROF, S_COND_Q, S_COND_KEPT,       // profile indices of the gate; mmla_condition's outputs
-  S_ROOM_P, S_ROOM_A                      // mmla_room_pipeline_conditioned: the SI outputs' staging
+  S_ROOM_P, S_ROOM_A,                     // mmla_room_pipeline_conditioned: the SI outputs' staging
+  S_ENROL_VAD, S_ENROL_NW                 // mmla_si_enrol_embed: the temporary detectors, the window counts
 };
 
 // mmla_ctx::cap_buf: staged raw capture, host frames, per-clip entry (d0, prev), converted clips and

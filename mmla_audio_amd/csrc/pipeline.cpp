@@ -258,6 +258,12 @@ double si_fe_bytes(int64_t n, const SiFeArgs& a) {
   return (double)n * (in + SI_T * SI_D * 4.0 + (a.silent ? 1.0 : 0.0));
 }
 
+// 256-frame windows of a signal of n >= 1 samples: ceil(T / 256), T = psf's frame count
+int64_t si_seq_windows(int64_t n) {
+  const int64_t T = n <= 400 ? 1 : 1 + (n - 400 + 159) / 160;
+  return (T + SI_T - 1) / SI_T;
+}
+
 bool bad_pcm_args(const void* pcm, int64_t n, int64_t stride, const int32_t* lens, int32_t clip_len) {
   if (n < 0 || (n > 0 && !pcm)) return true;
   if (!lens && clip_len < 0) return true;
@@ -493,18 +499,31 @@ struct Conditioner {
   // pcm and lens are device pointers whatever the call's flags say (the capture calls: the converted
   // clips never leave the device); profile and the outputs follow the flags
   bool pcm_dev = false;
+  // mmla_si_enrol_embed: whole recordings (clip_len up to MMLA_ENROL_MAX_SAMPLES, gated chunk by chunk
+  // inside nr_reduce_dev), one per stream, each on a fresh temporary detector of mode vad_mode that
+  // run() creates anew every time: the context's vad_state is neither needed nor touched, and a
+  // repeated micro-batch simply starts again
+  bool enrol = false;
+  int32_t vad_mode = 3;
   int64_t snap_c0 = -1, snap_streams = 0;
   const int16_t* q = nullptr;      // device results of the last run()
   const int32_t* kept = nullptr;
+  std::vector<VadState> fresh;     // enrol: the host image of the temporary detectors
 
   const char* bad(const mmla_ctx* c, bool dev) const {
     if (bad_pcm_args(pcm, n, stride, lens, clip_len)) return "bad pcm args";
-    if (clip_len < 1 || clip_len > 600000) return "clip_len must be in [1, 600000] (one gate chunk)";
+    if (enrol) {
+      if (clip_len < 1 || clip_len > MMLA_ENROL_MAX_SAMPLES)
+        return "clip_len must be in [1, MMLA_ENROL_MAX_SAMPLES] (4096 detector frames)";
+      if (vad_mode < 0 || vad_mode > 3) return "VAD mode must be 0..3";
+    } else if (clip_len < 1 || clip_len > 600000) {
+      return "clip_len must be in [1, 600000] (one gate chunk)";
+    }
     if (n > 1 && stride < clip_len) return "clip_stride < clip_len";
     if (nr_passes < 0) return "nr_passes < 0";
     if (nr_passes > 0 && !ns && !c->nr_ready) return "nr_passes > 0: mmla_nr_set_noise(_bank) must be called first";
     if (ips < 1 || n % ips) return "n_clips is not a multiple of items_per_stream";
-    if (silence_remove && (!c->vad_state || c->vad_streams != n / ips))
+    if (silence_remove && !enrol && (!c->vad_state || c->vad_streams != n / ips))
       return "silence_remove: mmla_vad_reset must have created n_clips / items_per_stream streams";
     // device-pointer profile indices cannot be seen here: the kernels clamp them into the bank
     if (profile && !dev && nr_passes > 0 && !ns)
@@ -541,8 +560,20 @@ struct Conditioner {
     const int32_t* vad_lens = nullptr;
     if (silence_remove) {
       const int64_t s0 = c0 / ips, ns = cnt / ips;
+      VadState* state = c->vad_state + s0;
       VadState* snap = c->vad_state + c->vad_streams;
-      if (c0 == snap_c0) {
+      if (enrol) {
+        VadState init;
+        if (!vad_init_state(&init, vad_mode)) return fail(c, MMLA_E_INVALID, "VAD mode must be 0..3");
+        void* pst = nullptr;
+        CHK(ws_get(c, S_ENROL_VAD, (size_t)cnt * sizeof(VadState), &pst));
+        fresh.assign((size_t)cnt, init);
+        HIPCHK(c, hipMemcpyAsync(pst, fresh.data(), (size_t)cnt * sizeof(VadState), hipMemcpyHostToDevice,
+                                 c->stream));
+        // a device-pointer call returns with its launches only enqueued: the host image must have left
+        if (dev) HIPCHK(c, hipStreamSynchronize(c->stream));
+        state = static_cast<VadState*>(pst);
+      } else if (c0 == snap_c0) {
         HIPCHK(c, hipMemcpyAsync(c->vad_state + s0, snap + s0, snap_streams * sizeof(VadState),
                                  hipMemcpyDeviceToDevice, c->stream));
       } else {
@@ -559,7 +590,7 @@ struct Conditioner {
       v.clip_len = D;
       v.n_items = cnt;
       v.items_per_stream = ips;
-      v.state = c->vad_state + s0;
+      v.state = state;
       v.max_frames = std::max(1, vad_frames(D));
       CHK(ws_get(c, S_VAD_SPEECH, (size_t)cnt * v.max_frames, &psp));
       CHK(ws_get(c, S_VAD_LENS, (size_t)cnt * sizeof(int32_t), &pvl));
@@ -852,6 +883,99 @@ int mmla_si_features_seq(mmla_ctx* c, const int16_t* pcm, int64_t n_samples, int
          si_fe_launch(a, n_windows, c->stream));
   CHK(copy_back(c, feat, 0, a.feat, n_windows * SI_T * SI_D, dev));
   return finish(c, dev);
+}
+
+int mmla_si_features_seq_batch(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride, const int32_t* lens,
+                               int32_t clip_len, float* feat, int32_t* n_windows, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  if (n < 0 || n > 0x7fffffff || clip_len < 1 || (n > 0 && (!pcm || !feat)) || (n > 1 && stride < clip_len))
+    return fail(c, MMLA_E_INVALID, "bad si_features_seq_batch args");
+  const bool dev = flags & MMLA_DEVICE_PTR;
+  if (n == 1) stride = std::max<int64_t>(stride, clip_len);   // one row: its width is clip_len
+  // device-pointer lens cannot be seen here: the kernel clamps them into [0, clip_len]
+  if (lens && !dev)
+    for (int64_t i = 0; i < n; ++i)
+      if (lens[i] < 0 || lens[i] > clip_len || lens[i] > stride)
+        return fail(c, MMLA_E_INVALID, "lens[%lld] = %d outside [0, clip_len = %d]", (long long)i, lens[i], clip_len);
+  if (n == 0) return MMLA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int64_t w_max = si_seq_windows(clip_len);
+  SiFeArgs a{};
+  a.pcm = pcm;
+  a.clip_stride = stride;
+  if (!dev) {   // the rows' first clip_len samples, dense
+    void* dp = nullptr;
+    CHK(ws_get(c, S_PCM, (size_t)n * clip_len * sizeof(int16_t), &dp));
+    HIPCHK(c, hipMemcpy2DAsync(dp, (size_t)clip_len * sizeof(int16_t), pcm, (size_t)stride * sizeof(int16_t),
+                               (size_t)clip_len * sizeof(int16_t), n, hipMemcpyHostToDevice, c->stream));
+    a.pcm = static_cast<const int16_t*>(dp);
+    a.clip_stride = clip_len;
+  }
+  CHK(in_ptr(c, lens, (size_t)n, dev, S_LENS, &a.lens));
+  a.clip_len = clip_len;
+  a.tables = c->si_tables;
+  a.w_max = (int32_t)w_max;
+  const size_t nf = (size_t)(n * w_max) * SI_T * SI_D;
+  CHK(out_ptr(c, feat, 0, nf, dev, S_OUT0, &a.feat));
+  CHK(out_ptr(c, n_windows, 0, (size_t)n, dev, S_OUT1, &a.n_windows));
+  LAUNCH(c, MMLA_STAGE_SI_FE, (double)n * clip_len * 2 + (double)nf * 4, si_fe_launch(a, n, c->stream));
+  CHK(copy_back(c, feat, 0, a.feat, nf, dev));
+  CHK(copy_back(c, n_windows, 0, a.n_windows, (size_t)n, dev));
+  return finish(c, dev);
+}
+
+int mmla_si_enrol_embed(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride, const int32_t* lens,
+                        int32_t clip_len, const int32_t* profile, int32_t nr_passes, int32_t silence_remove,
+                        int32_t vad_mode, int16_t* out_pcm, int32_t* kept_len, int32_t* n_windows, float* emb,
+                        uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  const bool dev0 = flags & MMLA_DEVICE_PTR;
+  Conditioner cd{pcm, n, stride, lens, clip_len, profile, nr_passes, silence_remove, 1, out_pcm, kept_len,
+                 (flags & MMLA_NR_NONSTATIONARY) != 0};
+  cd.enrol = true;
+  cd.vad_mode = vad_mode;
+  if (const char* bad = cd.bad(c, dev0)) return fail(c, MMLA_E_INVALID, "%s", bad);
+  if (n > 0 && !emb) return fail(c, MMLA_E_INVALID, "null emb");
+  if (const char* m = missing_weights(c, COND_SI)) return fail(c, MMLA_E_NOWEIGHTS, "%s weights not loaded", m);
+  const int64_t w_max = si_seq_windows(clip_len);
+  // Per micro-batch of recordings (SI's cap, counted in recordings): the conditioning, the batched
+  // sequence front-end on the conditioned int16 with lens = kept_len, then SI-NET up to the BiLSTM on the
+  // cnt * w_max windows in micro-batches of that many windows, each under mmla_si_embed's range guard.
+  // A window's embedding does not depend on where it sits in a batch, so neither size enters the result
+  return clip_call(c, COND_SI, n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev) -> int {
+    CHK(cd.run(c, c0, cnt, dev));
+    const int64_t nwin = cnt * w_max;
+    void *pf = nullptr, *pw = nullptr;
+    CHK(ws_get(c, S_FEAT, (size_t)nwin * SI_T * SI_D * sizeof(float), &pf));
+    CHK(ws_get(c, S_ENROL_NW, (size_t)cnt * sizeof(int32_t), &pw));
+    SiFeArgs a{};
+    a.pcm = cd.q;
+    a.clip_stride = clip_len;
+    a.lens = cd.kept;
+    a.clip_len = clip_len;
+    a.tables = c->si_tables;
+    a.feat = static_cast<float*>(pf);
+    a.ldf = SI_D;
+    a.w_max = (int32_t)w_max;
+    a.n_windows = static_cast<int32_t*>(pw);
+    LAUNCH(c, MMLA_STAGE_SI_FE, (double)cnt * clip_len * 2 + (double)nwin * SI_T * SI_D * 4,
+           si_fe_launch(a, cnt, c->stream));
+    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (n_windows)
+      HIPCHK(c, hipMemcpyAsync(n_windows + c0, a.n_windows, (size_t)cnt * sizeof(int32_t), kind, c->stream));
+    const int64_t mb = std::max<int64_t>(1, microbatch(c, false));
+    for (int64_t w0 = 0; w0 < nwin; w0 += mb) {
+      const int64_t wc = std::min(mb, nwin - w0);
+      CHK(guarded(c, dev, c->si_f32_only, [&]() -> int {
+        const float* h = nullptr;
+        CHK(run_si_net(c, a.feat + w0 * SI_T * SI_D, wc, nullptr, nullptr, nullptr, SI_D, &h));
+        HIPCHK(c, hipMemcpyAsync(emb + (c0 * w_max + w0) * MMLA_SI_EMBED, h,
+                                 (size_t)wc * MMLA_SI_EMBED * sizeof(float), kind, c->stream));
+        return MMLA_OK;
+      }));
+    }
+    return MMLA_OK;
+  });
 }
 
 int mmla_od_forward(mmla_ctx* c, const float* x, int64_t n, float* probs, uint32_t flags) {

@@ -32,8 +32,15 @@ struct SiFeArgs {
   float* feat;              // [n,256,ldf]
   int ldf;                  // feature row stride: 39 (0 = 39), or 40 with a zero 40th column
   uint8_t* silent;          // [n] nullable (clip mode only)
+  // > 0: batched sequence mode -- block (i, w) = 256-frame window w of signal i (pcm + i * clip_stride,
+  // lens[i] samples clamped to [0, clip_len]; lens null: clip_len) into feat [n, w_max, 256, ldf];
+  // w_max must be ceil(T(clip_len) / 256).  Windows at or past ceil(T(lens[i]) / 256), and every window
+  // of an empty signal, are zeros
+  int32_t w_max;
+  int32_t* n_windows;       // [n] nullable (batched sequence mode): windows of signal i, 0 when empty
 };
 
 void si_fe_build_tables(SiFeTables* t);
 bool si_fe_tables_ok(const SiFeTables& t);
+// n_blocks: clips, windows of the one signal, or (batched sequence mode) signals
 hipError_t si_fe_launch(const SiFeArgs& a, int64_t n_blocks, hipStream_t stream);

@@ -155,11 +155,30 @@ __global__ void __launch_bounds__(NT, 2) si_fe_kernel(SiFeArgs a) {
   // feature rows of ldf floats: 39, or 40 with a zero 40th column (the fused SI pipeline: the stem
   // Conv1D then stages 16-B aligned rows as float4, conv_h3 V4)
   const int ldf = a.ldf > 39 ? 40 : 39;
-  float* out = a.feat + blk * (OUTF * ldf);
+  // batched sequence mode: the grid is [signal][window]; the other modes launch gridDim.y = 1
+  const int64_t oblk = a.w_max > 0 ? blk * a.w_max + blockIdx.y : blk;
+  float* out = a.feat + oblk * (OUTF * ldf);
 
   const int16_t* x;
   int64_t len, frame0;
-  if (a.seq_len > 0) {            // window blk of one long signal (conversation mode)
+  if (a.w_max > 0) {              // window blockIdx.y of signal blk of a ragged batch (enrolment)
+    // the block's triple comes from uniform values only (kernel arguments, block indices and one
+    // scalar load of lens[blk]): no lane-varying state is added in front of the round loop
+    const int w = blockIdx.y;
+    int l = a.lens ? a.lens[blk] : a.clip_len;
+    l = l < 0 ? 0 : (l > a.clip_len ? a.clip_len : l);   // the convention of the VAD's lens
+    const int tl = l <= 400 ? 1 : 1 + (l - 400 + 159) / 160;
+    const int nw = l > 0 ? (tl + OUTF - 1) / OUTF : 0;
+    if (a.n_windows && w == 0 && lane == 0) a.n_windows[blk] = nw;
+    if (w >= nw) {                // past the signal's last window, or an empty signal: zeros
+      float4* o4 = reinterpret_cast<float4*>(out);
+      for (int e = lane; e < OUTF * ldf / 4; e += NT) o4[e] = float4{0.f, 0.f, 0.f, 0.f};
+      return;
+    }
+    x = a.pcm + blk * a.clip_stride;
+    len = l;
+    frame0 = (int64_t)OUTF * w;
+  } else if (a.seq_len > 0) {     // window blk of one long signal (conversation mode)
     x = a.pcm;
     len = a.seq_len;
     frame0 = OUTF * blk;
@@ -483,7 +502,9 @@ __global__ void __launch_bounds__(NT, 2) si_fe_kernel(SiFeArgs a) {
 
 hipError_t si_fe_launch(const SiFeArgs& a, int64_t n_clips, hipStream_t stream) {
   if (n_clips <= 0) return hipSuccess;
-  hipLaunchKernelGGL(v2::si_fe_kernel, dim3((unsigned)n_clips), dim3(v2::NT), 0, stream, a);
+  if (a.w_max > 0 && (a.seq_len > 0 || a.clip_len < 0 || a.w_max > 65535)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(v2::si_fe_kernel, dim3((unsigned)n_clips, a.w_max > 0 ? (unsigned)a.w_max : 1u),
+                     dim3(v2::NT), 0, stream, a);
   return hipGetLastError();
 }
 

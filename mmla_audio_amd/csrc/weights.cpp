@@ -211,6 +211,7 @@ extern "C" int mmla_load_weights(mmla_ctx* c, int kind, const float* packed, int
     if (head != MMLA_HEAD_SOFTMAX && head != MMLA_HEAD_SIGMOID)
       return fail(c, MMLA_E_INVALID, "unknown head %d", head);
     free_allocs(c->si_allocs);
+    free_allocs(c->si_head_allocs);
     c->si_loaded = false;
     SiNet& W = c->si;
     auto& al = c->si_allocs;
@@ -218,7 +219,9 @@ extern "C" int mmla_load_weights(mmla_ctx* c, int kind, const float* packed, int
     CHK(take_units(c, cur, al, W.unit, 32, 3, 1, 3, 1, false));
     CHK(take_bn(c, cur, al, 128, &W.final_bn));
     CHK(take_lstm(c, cur, al, 128, &W.lstm));
-    CHK(take_conv(c, cur, al, 1, 1, 512, n_classes, &W.dense));
+    c->si_base_f16_bad = c->loading_f16_bad;
+    W.dense = ConvW();
+    CHK(take_conv(c, cur, c->si_head_allocs, 1, 1, 512, n_classes, &W.dense));
     if (cur.left != 0)
       return fail(c, MMLA_E_SHAPE, "SI weight blob has %lld extra floats", (long long)cur.left);
     W.k = n_classes;
@@ -228,4 +231,39 @@ extern "C" int mmla_load_weights(mmla_ctx* c, int kind, const float* packed, int
     return MMLA_OK;
   }
   return fail(c, MMLA_E_INVALID, "unknown model kind %d", kind);
+}
+
+// The Dense head of the loaded SI model replaced in place: the tensors go through take_conv as the
+// blob's last two do in mmla_load_weights (the 3xFP16 split at the tensor's own scale, a non-finite
+// tensor sending the whole model to exact f32), so every later call gives the bits of a full load with
+// that head.  The old head is freed only once the new one is on the device.
+extern "C" int mmla_si_set_head(mmla_ctx* c, const float* w, const float* b, int32_t n_classes, int32_t head) {
+  if (!c) return MMLA_E_INVALID;
+  if (!w || !b) return fail(c, MMLA_E_INVALID, "null head tensors");
+  if (n_classes < 1) return fail(c, MMLA_E_INVALID, "SI n_classes must be >= 1");
+  if (head != MMLA_HEAD_SOFTMAX && head != MMLA_HEAD_SIGMOID)
+    return fail(c, MMLA_E_INVALID, "unknown head %d", head);
+  if (!c->si_loaded) return fail(c, MMLA_E_NOWEIGHTS, "SI weights not loaded");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // kernel [512, K] then bias [K], contiguous as in the blob
+  std::vector<float> blob((size_t)512 * n_classes + n_classes);
+  memcpy(blob.data(), w, sizeof(float) * 512 * n_classes);
+  memcpy(blob.data() + (size_t)512 * n_classes, b, sizeof(float) * n_classes);
+  Cursor cur{blob.data(), (int64_t)blob.size()};
+  c->loading_f16_bad = false;
+  std::vector<void*> al;
+  ConvW dense;
+  const int rc = take_conv(c, cur, al, 1, 1, 512, n_classes, &dense);
+  if (rc != MMLA_OK) {   // the model keeps the head it had
+    free_allocs(al);
+    return rc;
+  }
+  free_allocs(c->si_head_allocs);
+  c->si_head_allocs.swap(al);
+  c->si.dense = dense;
+  c->si.k = n_classes;
+  c->si.head = head;
+  c->si_f32_only = c->si_base_f16_bad || c->loading_f16_bad;
+  return MMLA_OK;
 }

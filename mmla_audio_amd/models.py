@@ -173,6 +173,24 @@ class SpeakerIdModel(_Model):
             raise ValueError(f'SI model expects [N,256,39], got {x.shape}')
         return self.ctx.si_forward(x)
 
+    def set_head(self, w, b, head=_lib.HEAD_SIGMOID):
+        """Replace the Dense head in place (``mmla_si_set_head``): w [512, K], b [K] -- the head a
+        registration just fitted, installed without re-uploading the frozen base.  self.W, n_classes and
+        head follow, so a later re-load (another model took the context) gives the same model."""
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        if w.ndim != 2 or w.shape[0] != _lib.SI_EMBED or b.shape != (w.shape[1],) or w.shape[1] < 1:
+            raise ValueError(f'w {w.shape} / b {b.shape}: expected [512,K] and [K], K >= 1')
+        if head not in (_lib.HEAD_SOFTMAX, _lib.HEAD_SIGMOID):
+            raise ValueError(f'unknown head {head}')
+        self._ensure_loaded()
+        self.ctx.si_set_head(w, b, head)
+        name = weights.si_spec(w.shape[1])[-2][0].rsplit('/', 1)[0]
+        W = dict(self.W)
+        W[name + '/kernel'] = w.copy()
+        W[name + '/bias'] = b.copy()
+        self.W, self.n_classes, self.head = W, int(w.shape[1]), int(head)
+
     def predict_wavs(self, pcm, lens=None):
         """Fused WAV -> speaker: -> (probs [N,K], argmax [N] (-1 = 'silent'), silent [N])."""
         self._ensure_loaded()

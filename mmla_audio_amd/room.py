@@ -22,6 +22,8 @@ from .overlap_detection_post_processing import LABELS as _OD_LABELS
 RoomResult = namedtuple('RoomResult', 'od_probs od_argmax si_probs si_argmax silent kept_len pcm',
                         defaults=(None,))
 
+Registration = namedtuple('Registration', 'speaker_id_dict accuracy kept_len n_windows history')
+
 MEAN = -1      # CaptureFormat.channel: pydub's set_channels(1) of a stereo capture
 
 
@@ -109,6 +111,75 @@ class Room:
             self.ctx.capture_reset(live[1] if live[0] is not None and live[1] else 1, rate, ch, sel)
         out, lens = self.ctx.capture_convert(clips, items_per_stream=len(clips), fresh=True)
         return np.concatenate([out[i, :lens[i]] for i in range(len(clips))])
+
+    def register(self, recordings, names, mic=None, passes=1, silence_remove=True, seed=1, epochs=500,
+                 restarts=1, save_to=None):
+        """Enrol the room's speakers (step 2 and 3 of the reference's manual: SpeakerIdentification/scripts/
+        record_on_pc.py:300-346) on the context the room ticks on: ``recordings`` is one int16 array per
+        speaker -- interleaved capture in a room with a capture format (it goes through ``Room.convert``:
+        fresh states, the live converters left alone), 16 kHz mono otherwise -- and ``names`` their unique
+        names; class k is names[k].  All recordings are conditioned in one batch with the room's gate (its
+        noise bank with mic[k], default 0; the non-stationary gate when ``noises is None``) and a fresh
+        detector each (the live streams' detectors are left alone), cut into 256-frame windows, embedded by
+        the frozen base (``mmla_si_enrol_embed``) and fitted (``fit_registration``: the reference's call,
+        test split 0; labels k repeated n_windows[k] times).  The fitted head is installed in place
+        (``SpeakerIdModel.set_head``): the next tick answers with the new speakers.  ``save_to`` also writes
+        the deployed bundle and speaker_id_dict.json there, so ``load_model(save_to)`` gives the same model.
+        -> Registration(speaker_id_dict {str(k): names[k]}, accuracy (validation, of the kept restart),
+        kept_len [K] (the reference asks to re-record when less than 50 s are left), n_windows [K], history
+        [restarts, epochs, 4]).  A speaker with no window left raises ValueError naming the speaker; the
+        room is unchanged when anything raises."""
+        import json
+        import os
+
+        from . import _lib, noisereduce, tfbundle
+        from .speaker_identification import deployed_weights, fit_registration
+        names = [str(x) for x in names]
+        K = len(names)
+        if K < 1 or len(recordings) != K:
+            raise ValueError(f'{len(recordings)} recordings for {K} names: one recording per speaker')
+        if len(set(names)) != K:
+            raise ValueError('speaker names must be unique: '
+                             f'{sorted(x for x in set(names) if names.count(x) > 1)} repeat')
+        if K > _lib.SI_TRAIN_MAX_CLASSES:
+            raise ValueError(f'{K} speakers: the head trainer fits at most {_lib.SI_TRAIN_MAX_CLASSES}')
+        if epochs < 1 or restarts < 1 or passes < 0:
+            raise ValueError('epochs and restarts must be >= 1, passes >= 0')
+        ns = self.noises is None
+        one = isinstance(self.noises, np.ndarray) and self.noises.ndim == 1
+        noises = [] if ns else [np.ascontiguousarray(x, dtype=np.float32).ravel()
+                                for x in ([self.noises] if one else self.noises)]
+        mic = np.zeros(K, np.int32) if mic is None else np.ascontiguousarray(mic, dtype=np.int32)
+        if mic.shape != (K,):
+            raise ValueError(f'mic must hold one entry per speaker, got shape {mic.shape}')
+        if not ns and (mic.min() < 0 or mic.max() >= len(noises)):
+            raise ValueError(f'mic must hold one index into the {len(noises)} noise clips per speaker')
+        recs = [self.convert(r) if self.capture is not None
+                else np.ascontiguousarray(r, dtype=np.int16).reshape(-1) for r in recordings]
+        longest = max(len(r) for r in recs)
+        if longest > _lib.ENROL_MAX_SAMPLES:
+            raise ValueError(f'a recording of {longest} samples at 16 kHz exceeds {_lib.ENROL_MAX_SAMPLES}')
+        self.si._ensure_loaded()
+        if not ns and passes > 0:
+            noisereduce._set_noise_bank(self.ctx, noises, 16000)
+        emb, n_windows, kept_len = self.ctx.si_enrol_embed(
+            recs, profile=mic, passes=passes, silence_remove=silence_remove, vad_mode=self.vad_mode,
+            nonstationary=ns)
+        for k in range(K):
+            if n_windows[k] < 1:
+                raise ValueError(f'speaker {names[k]!r}: no audio left after conditioning '
+                                 f'({len(recs[k])} samples recorded, {int(kept_len[k])} kept)')
+        labels = np.repeat(np.arange(K, dtype=np.int32), n_windows)
+        x = np.concatenate([emb[k, :n_windows[k]] for k in range(K)])
+        fit = fit_registration(x, labels, K, seed, 0, epochs, restarts, self.ctx)
+        speaker_id_dict = {str(k): names[k] for k in range(K)}
+        if save_to is not None:
+            os.makedirs(save_to, exist_ok=True)
+            tfbundle.save_deployed(save_to, deployed_weights(self.si.W, fit.w, fit.b), K)
+            with open(os.path.join(save_to, 'speaker_id_dict.json'), 'w') as f:
+                json.dump(speaker_id_dict, f)
+        self.si.set_head(fit.w, fit.b, _lib.HEAD_SIGMOID)
+        return Registration(speaker_id_dict, fit.accuracy, kept_len, n_windows, fit.history)
 
     @staticmethod
     def labels(result, speaker_id_dict):

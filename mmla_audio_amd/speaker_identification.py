@@ -12,6 +12,7 @@ import math
 import os
 import sys
 import time
+from collections import namedtuple
 
 import numpy as np
 import scipy.io.wavfile as _wavfile
@@ -162,6 +163,39 @@ def fit_head(emb, labels, val_emb, val_labels, w0, b0, perm, epochs, batch=16, l
     return ctx.si_head_fit(emb, labels, val_emb, val_labels, w0, b0, perm, epochs, batch, lr)
 
 
+HeadFit = namedtuple('HeadFit', 'w b accuracy history best test')
+
+
+def fit_registration(emb, labels, K, seed, test_split_ratio, epochs, restarts, device=None):
+    """The part of a registration behind the embeddings, shared by transfer_learning and Room.register:
+    the plan drawn from `seed` (``_fit_plan``), `restarts` heads fitted side by side (``fit_head``) and
+    the choice between them -- the best final validation accuracy, ties by the lower validation loss,
+    then the lower index (without a validation set: the training figures).  emb [n,512], labels [n].
+    -> HeadFit(w [512,K], b [K] of the kept restart, its accuracy, history [R,epochs,4], the kept
+    restart's index, the test split's indices)."""
+    emb = np.asarray(emb)
+    labels = np.asarray(labels, dtype=np.int32)
+    plan = _fit_plan(labels, K, seed, test_split_ratio, epochs, restarts)
+    tr, va = plan['train'], plan['val']
+    w, b, hist = fit_head(emb[tr], labels[tr], emb[va], labels[va], plan['w0'], plan['b0'],
+                          plan['perm'], epochs, batch=16, lr=1e-4, device=device)
+    last = hist[:, -1]
+    score = last[:, 2:] if len(va) else last[:, :2]      # (loss, acc) deciding between restarts
+    best = min(range(restarts), key=lambda r: (-score[r, 1], score[r, 0], r))
+    return HeadFit(w[best], b[best], float(score[best, 1]), hist, best, plan['test'])
+
+
+def deployed_weights(base_W, w, b):
+    """the tensors of the deployed model: the base below its Dense head + the head (w [512,K], b [K])"""
+    from . import weights
+    K = int(np.shape(w)[1])
+    head = weights.si_spec(K)[-2][0].rsplit('/', 1)[0]
+    W = {n: base_W[n] for n, _, _ in weights.si_spec(K)[:-2]}
+    W[head + '/kernel'] = w
+    W[head + '/bias'] = b
+    return W
+
+
 def transfer_learning(_x, _y, seed, _test_split_ratio, base_model_path, final_model_path, *,
                       epochs=500, restarts=1, allow_synthetic=False, device=None):
     """speaker_identification.py:401-477, stage 1: freeze the base model below its Dense head, fit
@@ -192,20 +226,11 @@ def transfer_learning(_x, _y, seed, _test_split_ratio, base_model_path, final_mo
                              allow_synthetic=allow_synthetic)
     base._ensure_loaded()
     emb = base.ctx.si_embed(_x)
-    plan = _fit_plan(labels, K, seed, _test_split_ratio, epochs, restarts)
-    tr, va, te = plan['train'], plan['val'], plan['test']
-    w, b, hist = fit_head(emb[tr], labels[tr], emb[va], labels[va], plan['w0'], plan['b0'],
-                          plan['perm'], epochs, batch=16, lr=1e-4, device=base.ctx)
-    last = hist[:, -1]
-    score = last[:, 2:] if len(va) else last[:, :2]      # (loss, acc) deciding between restarts
-    best = min(range(restarts), key=lambda r: (-score[r, 1], score[r, 0], r))
-    head = weights.si_spec(K)[-2][0].rsplit('/', 1)[0]
-    W = {n: base.W[n] for n, _, _ in weights.si_spec(K)[:-2]}
-    W[head + '/kernel'] = w[best]
-    W[head + '/bias'] = b[best]
+    fit = fit_registration(emb, labels, K, seed, _test_split_ratio, epochs, restarts, base.ctx)
+    te = fit.test
     os.makedirs(final_model_path, exist_ok=True)
-    tfbundle.save_deployed(final_model_path, W, K)
-    accuracy = float(score[best, 1])
+    tfbundle.save_deployed(final_model_path, deployed_weights(base.W, fit.w, fit.b), K)
+    accuracy = fit.accuracy
     if len(te):      # model.evaluate(x_test, y_test) on the model just saved
         deployed = models.load_model(final_model_path, device=base.ctx)
         accuracy = float((deployed.predict(_x[te]).argmax(axis=1) == labels[te]).mean())
