@@ -123,20 +123,19 @@ struct mmla_ctx {
   int64_t od_mb_cap = mmla::kOdMicrobatch, si_mb_cap = mmla::kSiMicrobatch;   // default caps of the automatic size
   int debug_fail_allocs = 0;   // test hook (env MMLA_DEBUG_FAIL_ALLOC at create): fail this many workspace allocations
   int precision = MMLA_PREC_F16X3;
-  // SI res units without pooling as one fused kernel each (siu.hip); env MMLA_NO_SIU=1 at create:
-  // the two conv_h3 launches (A/B)
+  // SI res units as fused launches of siu.hip's one template, siu_chain_kernel<..., POOL, NU, FIN, ...>
+  // (net_runners.cpp si_choose); env MMLA_NO_SIU=1 at create: two conv_h3 launches per unit (A/B)
   bool siu = true;
-  // ... and the pool units too (siu.hip POOL); env MMLA_NO_SIPU=1 at create: the conv_h3 pair
+  // ... and the pool units too (POOL); env MMLA_NO_SIPU=1 at create: the conv_h3 pair
   bool sipu = true;
-  // ... and the last one with the final BN + ReLU + AvgPool4 (siu.hip FIN); env MMLA_NO_SIFIN=1: the
-  // unit writes its output and bn_relu_avgpool4 runs as its own launch
+  // ... and the last one with the final BN + ReLU + AvgPool4 (FIN); env MMLA_NO_SIFIN=1: the unit
+  // writes its output and bn_relu_avgpool4 runs as its own launch
   bool sifin = true;
-  // ... and two consecutive units without pooling (2-3, 5-6, 8-9) as one kernel (siu.hip
-  // siu_chain_kernel without a pool unit: the first unit's output stays on chip); env MMLA_NO_SIPAIR=1:
-  // one launch each
+  // ... and two consecutive units without pooling (2-3, 5-6, 8-9) in one launch (NU = 2: the first
+  // unit's output stays on chip); env MMLA_NO_SIPAIR=1: one launch each (NU = 1)
   bool sipair = true;
-  // ... and a pool unit with the two units after it (1-3, 4-6, 7-9) as one kernel (siu.hip
-  // siu_chain_kernel POOL); env MMLA_NO_SICHAIN=1: the pool unit alone, then the pair
+  // ... and a pool unit with the two units after it (1-3, 4-6, 7-9) in one launch (POOL, NU = 2); env
+  // MMLA_NO_SICHAIN=1: the pool unit alone (POOL, NU = 0), then the pair
   bool sichain = true;
   // fused SI pipeline: si_fe writes 40-float feature rows for the stem (env MMLA_NO_SIPAD=1: 39)
   bool si_pad_feat = true;

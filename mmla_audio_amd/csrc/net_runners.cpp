@@ -1,7 +1,8 @@
 // libmmla network runners: OD-NET and SI-NET on one device micro-batch.  Which kernel runs each OD
-// res block is decided in od_choose(); the SI unit walk prefers pool-chain, pair, single unit, conv
-// pair in that order.  One filler per kernel argument struct, one FLOP formula per block kind, one
-// tail that advances the state.  DESIGN.md ("Where the dispatch lives") says how to add a path.
+// res block is decided in od_choose(), which launch covers each SI res unit in si_choose() (pool-chain,
+// pair, single unit, conv pair in that order).  One filler per kernel argument struct, one FLOP
+// formula per block kind, one tail that advances the state.  DESIGN.md ("Where the dispatch lives")
+// says how to add a path.
 #include <algorithm>
 
 #include "conv.h"
@@ -401,16 +402,37 @@ namespace {
 
 // a res unit without pooling that siu.hip runs (3xFP16 weights of the exact widths)
 bool siu_ok(const ResUnitW& U, int cin) {
-  return U.ca.wh && U.cb.wh && siu_supported(cin) && U.ca.cin == cin && U.ca.cout == cin && U.cb.cin == cin &&
-         U.cb.cout == cin && U.ca.cin_pad == cin && U.ca.cout_pad == cin && U.cb.cout_pad == cin;
+  return U.ca.wh && U.cb.wh && siu_chain_supported(cin, cin, false, 1, false) && U.ca.cin == cin &&
+         U.ca.cout == cin && U.cb.cin == cin && U.cb.cout == cin && U.ca.cin_pad == cin && U.ca.cout_pad == cin &&
+         U.cb.cout_pad == cin;
 }
 
 // ... and a pool unit (siu.hip POOL)
 bool sipu_ok(const ResUnitW& U, int cin) {
-  return U.ca.wh && U.cb.wh && U.sc.wh && sipu_supported(cin, U.ca.cout) && U.ca.cin_pad == cin &&
-         U.ca.cout_pad == U.ca.cout && U.cb.cin == U.ca.cout && U.cb.cout == U.ca.cout &&
+  return U.ca.wh && U.cb.wh && U.sc.wh && siu_chain_supported(cin, U.ca.cout, true, 1, false) &&
+         U.ca.cin_pad == cin && U.ca.cout_pad == U.ca.cout && U.cb.cin == U.ca.cout && U.cb.cout == U.ca.cout &&
          U.cb.cout_pad == U.ca.cout && U.sc.cin == cin && U.sc.cout == U.ca.cout &&
          U.sc.cout_pad == U.ca.cout;
+}
+
+// how many units the siu.hip launch that starts at unit u covers: a pool unit with the two units
+// after it or alone, two units without pooling or one; 0: the unit runs as conv_h3 / exact-f32 launches
+int si_choose(const mmla_ctx* c, const SiNet& W, int u) {
+  if (!c->siu || c->precision != MMLA_PREC_F16X3) return 0;
+  const int cin = W.unit[u].ca.cin, C = W.unit[u].ca.cout;
+  auto plain = [&](int v) { return v < 9 && !POOL[v] && siu_ok(W.unit[v], C); };
+  if (POOL[u]) {
+    if (!c->sipu || !sipu_ok(W.unit[u], cin)) return 0;
+    return c->sichain && siu_chain_supported(cin, C, true, 3, false) && plain(u + 1) && plain(u + 2) ? 3 : 1;
+  }
+  if (!siu_ok(W.unit[u], cin)) return 0;
+  return c->sipair && siu_chain_supported(cin, cin, false, 2, false) && plain(u + 1) ? 2 : 1;
+}
+
+// a whole res unit at t (pooled) rows per clip: both convs, and the pool units' shortcut
+double si_unit_flops(const ResUnitW& U, bool pool, int64_t n, int t) {
+  return 2.0 * n * t *
+         (3.0 * U.ca.cin * U.ca.cout + 3.0 * U.cb.cin * U.cb.cout + (pool ? 1.0 * U.sc.cin * U.sc.cout : 0.0));
 }
 
 // t: the unit's rows.  t_src > 0: a pool unit reading t_src rows through MaxPool1D, with its shortcut
@@ -466,17 +488,6 @@ int run_si_net(mmla_ctx* c, const float* x, int64_t n, float* probs, int32_t* ar
   int t = SI_T;
   const bool h3 = c->precision == MMLA_PREC_F16X3;
   bool fused_final = false;   // the last unit wrote BN + ReLU + AvgPool4 itself (siu FIN)
-  // `last` closes the launch that ends with unit u_last: when that is unit 9, + the final BN + ReLU +
-  // AveragePooling1D(4) in its epilogue: the unit's output never reaches HBM (bit-identical to
-  // bn_relu_avgpool4_launch below)
-  auto fuse_final = [&](SiuArgs& last, int u_last, int ch, int rows) {
-    if (u_last != 8 || !c->sifin || !siu_final_supported(ch) || rows % 4 != 0) return;
-    last.y = nullptr;
-    last.seq = SEQ;
-    last.fs = W.final_bn.scale;
-    last.ft = W.final_bn.shift;
-    fused_final = true;
-  };
   // Conv1D(32, 4, same): [n, 256, 1, 39] -> [n, 256, 1, 32] (speaker_identification.py:195)
   ConvW stem = W.stem;
   if (ldx == SI_D + 1 && h3 && stem.wh && stem.cin_pad > SI_D) stem.cin = ldx;
@@ -485,30 +496,35 @@ int run_si_net(mmla_ctx* c, const float* x, int64_t n, float* probs, int32_t* ar
   for (int u = 0; u < 9; ++u) {   // res_unit, speaker_identification.py:168-190
     const ResUnitW& U = W.unit[u];
     const int cin = U.ca.cin;
-    if (POOL[u] && c->siu && c->sipu && h3 && sipu_ok(U, cin)) {
-      // the whole pool unit in one launch: MaxPool1D in the staging, t1 on chip, the shortcut in the
-      // epilogue (siu.hip POOL), bit-identical to the two conv_h3 launches below
-      const int tp = (t + 1) / 2;
+    const bool pool = POOL[u];
+    const int tp = pool ? (t + 1) / 2 : t;
+    const int units = si_choose(c, W, u);
+    float* out = R;   // where the unit's (or the chain's) output lands
+    if (units > 0) {
+      // the units in one launch (siu.hip): MaxPool1D in the staging, every t1 and the outputs between
+      // units on chip, the shortcut in the epilogue, bit-identical to the conv_h3 launches below
       const int C = U.ca.cout;
-      SiuArgs s = siu_args(U, X, R, n, tp, c->range_ptr, t);
-      const double pool_flops = 2.0 * n * tp * (3.0 * cin * C + 3.0 * C * C + cin * C);
-      // ... with the two units after it (siu.hip chain: both intermediates stay on chip)
-      if (c->sichain && u + 2 < 9 && !POOL[u + 1] && !POOL[u + 2] && siu_triple_supported(cin, C) &&
-          siu_ok(W.unit[u + 1], C) && siu_ok(W.unit[u + 2], C)) {
-        SiuArgs sa = siu_args(W.unit[u + 1], nullptr, nullptr, n, tp, c->range_ptr);
-        SiuArgs sb = siu_args(W.unit[u + 2], nullptr, R, n, tp, c->range_ptr);
-        fuse_final(sb, u + 2, C, tp);
-        s.y = nullptr;
-        LAUNCH(c, MMLA_STAGE_CONV, pool_flops + 2.0 * 2.0 * 2.0 * n * tp * 3 * C * C,
-               siu_triple_launch(s, sa, sb, cin, C, c->stream));
-        u += 2;
-      } else {
-        LAUNCH(c, MMLA_STAGE_CONV, pool_flops, sipu_launch(s, cin, C, c->stream));
+      SiuArgs s[3];
+      double flops = 0.0;
+      for (int k = 0; k < units; ++k) {
+        const bool first = k == 0;
+        s[k] = siu_args(W.unit[u + k], first ? X : nullptr, k == units - 1 ? R : nullptr, n, tp, c->range_ptr,
+                        first && pool ? t : 0);
+        flops += si_unit_flops(W.unit[u + k], first && pool, n, tp);
       }
-      std::swap(X, R);
-      t = tp;
-    } else if (POOL[u]) {
-      const int tp = (t + 1) / 2;
+      // a launch that ends with unit 9: + the final BN + ReLU + AveragePooling1D(4) in its epilogue,
+      // so the unit's output never reaches HBM (bit-identical to bn_relu_avgpool4_launch below)
+      if (u + units == 9 && c->sifin && tp % 4 == 0 && siu_chain_supported(cin, C, pool, units, true)) {
+        SiuArgs& last = s[units - 1];
+        last.y = nullptr;
+        last.seq = SEQ;
+        last.fs = W.final_bn.scale;
+        last.ft = W.final_bn.shift;
+        fused_final = true;
+      }
+      LAUNCH(c, MMLA_STAGE_CONV, flops, siu_chain_launch(s, units, pool, cin, C, c->stream));
+      u += units - 1;
+    } else if (pool) {
       if (h3 && U.ca.wh) {
         // MaxPool1D(2, same) taken inside the conv's staging (conv_h3.hip PIN)
         CHK(conv_spatial(c, U.ca, X, T1, (int)n, tp, 1, &U.bn_in, PRO_BN_RELU, EPI_BIAS, nullptr,
@@ -526,26 +542,14 @@ int run_si_net(mmla_ctx* c, const float* x, int64_t n, float* probs, int32_t* ar
         CHK(conv_run(c, conv_args(U.sc, X, R, (int)n, t, 1, 2, nullptr, PRO_NONE, EPI_BIAS, nullptr)));
         CHK(conv_spatial(c, U.cb, T1, R, (int)n, tp, 1, &U.bn_mid, PRO_BN_RELU, EPI_ADD, R));
       }
-      std::swap(X, R);
-      t = tp;
-    } else if (c->siu && h3 && siu_ok(U, cin)) {
-      // the whole unit in one launch, t1 kept on chip (siu.hip), bit-identical to the pair below
-      SiuArgs s = siu_args(U, X, R, n, t, c->range_ptr);
-      if (c->sipair && u + 1 < 9 && !POOL[u + 1] && siu_pair_supported(cin) && siu_ok(W.unit[u + 1], cin)) {
-        SiuArgs s2 = siu_args(W.unit[u + 1], nullptr, R, n, t, c->range_ptr);
-        fuse_final(s2, u + 1, cin, t);
-        s.y = nullptr;
-        LAUNCH(c, MMLA_STAGE_CONV, 2.0 * 2.0 * 2.0 * n * t * 3 * cin * cin, siu_pair_launch(s, s2, cin, c->stream));
-        ++u;
-      } else {
-        fuse_final(s, u, cin, t);
-        LAUNCH(c, MMLA_STAGE_CONV, 2.0 * 2.0 * n * t * 3 * cin * cin, siu_launch(s, cin, c->stream));
-      }
-      std::swap(X, R);
     } else {
       CHK(conv_spatial(c, U.ca, X, T1, (int)n, t, 1, &U.bn_in, PRO_BN_RELU, EPI_BIAS, nullptr));
       CHK(conv_spatial(c, U.cb, T1, X, (int)n, t, 1, &U.bn_mid, PRO_BN_RELU, EPI_ADD, X));
+      out = X;
     }
+    // the tail every unit runs through: the output becomes X, pooled rows
+    if (out != X) std::swap(X, R);
+    t = tp;
   }
   // t = 32, c = 128 -> BN -> ReLU -> AvgPool1D(4) -> [n, 8, 128] (speaker_identification.py:208-212)
   if (!fused_final)

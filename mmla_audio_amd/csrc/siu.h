@@ -1,4 +1,4 @@
-// One SpeakerIdentification res_unit without pooling as a single fused kernel.  See siu.hip.
+// SpeakerIdentification res units, one to three of them per fused kernel launch.  See siu.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,32 +19,23 @@ struct SiuArgs {
   float ua, ub;            // 1 / (2^4 x the weight tensor's split scale), conv_h3's unscale
   int n, t;                // clips, rows per clip (pool units: pooled rows, (t_src + 1) / 2)
   int* range_flag;         // nullable: an operand split into fp16 left the fp16 range
-  // pool units only (sipu_launch): x is [n * t_src, CIN]; the shortcut Conv1D(C, 1, strides=2)
+  // pool units only: x is [n * t_src, CIN]; the shortcut Conv1D(C, 1, strides=2)
   int t_src;
   const uint16_t* wsh;     // its weight, conv_h3_split_weights layout (cin = CIN, cout = C)
   const uint16_t* wsl;
   const float* bs;         // its bias [C]
   float us;                // its unscale
-  // siu_launch with seq set (the last unit, siu_final_supported): instead of y, seq [n * t / 4, C] =
+  // seq set (the last unit of the net, siu_chain_supported's fin): instead of y, seq [n * t / 4, C] =
   // AveragePooling1D(4)(ReLU(x_out * fs + ft)) (the final BatchNormalization, folded)
   float* seq;
   const float* fs;
   const float* ft;
-  uint32_t tdiv_m, tdiv_s;   // set by the launchers: row / t as a multiply-high (callers leave 0)
+  uint32_t tdiv_m, tdiv_s;   // set by the launcher: row / t as a multiply-high (callers leave 0)
 };
 
-bool siu_supported(int c);
-bool siu_final_supported(int c);
-hipError_t siu_launch(const SiuArgs& a, int c, hipStream_t stream);
-// two consecutive units without pooling (a then b, b.x / a.y unused: the intermediate stays on chip);
-// b.seq set: b is the last unit (siu_final_supported's epilogue)
-bool siu_pair_supported(int c);
-hipError_t siu_pair_launch(const SiuArgs& a, const SiuArgs& b, int c, hipStream_t stream);
-// a pool unit p and the two units after it (p.x the input, b.y / b.seq the output: the
-// intermediates stay on chip)
-bool siu_triple_supported(int cin, int c);
-hipError_t siu_triple_launch(const SiuArgs& p, const SiuArgs& a, const SiuArgs& b, int cin, int c,
-                             hipStream_t stream);
-// the pool unit (speaker_identification.py:170-172 + 173-188) with t1 kept on chip
-bool sipu_supported(int cin, int c);
-hipError_t sipu_launch(const SiuArgs& a, int cin, int c, hipStream_t stream);
+// A chain of consecutive units as one launch: with `pool` a pool unit (cin -> c channels) first, then
+// units without pooling (c channels).  units[0].x is the chain's input and the last unit's y (or seq:
+// fin) its output; the x / y in between are unused, the intermediates stay on chip.  Chains: a pool
+// unit alone or with the two units after it, and one or two units without pooling.
+bool siu_chain_supported(int cin, int c, bool pool, int n_units, bool fin);
+hipError_t siu_chain_launch(const SiuArgs* units, int n_units, bool pool, int cin, int c, hipStream_t stream);

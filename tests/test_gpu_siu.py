@@ -8,6 +8,8 @@ probabilities over a batch with ragged and 'silent' clips, across several tiles 
 * MMLA_NO_SIPAIR: two consecutive units without pooling as one kernel (the first unit's output kept
   on chip), with and without the last unit's fused pooling;
 * MMLA_NO_SICHAIN: a pool unit and the two units after it as one kernel.
+All of these are instantiations of siu.hip's one kernel template (pool unit + two units, two units, one
+unit, the pool unit alone), so each A/B path is also compared with the conv_h3 launches directly.
 Each switch is set explicitly, so the tests hold whatever the library's defaults are."""
 import numpy as np
 import pytest
@@ -78,3 +80,36 @@ def test_unit_chains_bit_identical(monkeypatch, pcm):
 def test_unit_pairs_small_batches(monkeypatch, pcm, n):
     """batches smaller than one pair workgroup's rows (every row clamped at both batch ends)"""
     _same(monkeypatch, pcm[:n], ALL_ON, ALL_OFF)
+
+
+# the chain kernel's other instantiations, each against the conv_h3 launches: two units after a lone
+# pool unit; one unit per launch (the last with the fused pooling); ... and without the fused pooling
+NO_CHAIN = dict(ALL_ON, MMLA_NO_SICHAIN='1')
+AB_PATHS = {'no_chain': NO_CHAIN,
+            'no_pair': dict(NO_CHAIN, MMLA_NO_SIPAIR='1'),
+            'no_fin': dict(NO_CHAIN, MMLA_NO_SIPAIR='1', MMLA_NO_SIFIN='1')}
+_REF = {}   # clips -> the conv_h3 path's outputs (ALL_OFF), computed once and read-only
+
+
+def _same_as_conv_h3(monkeypatch, pcm, env):
+    if len(pcm) not in _REF:
+        _REF[len(pcm)] = _ctx(monkeypatch, ALL_OFF).si_pipeline(pcm)
+        for a in _REF[len(pcm)]:
+            a.setflags(write=False)
+    p, a, s = _ctx(monkeypatch, env).si_pipeline(pcm)
+    p_ref, a_ref, s_ref = _REF[len(pcm)]
+    assert np.array_equal(p, p_ref) and np.array_equal(a, a_ref)
+    assert np.array_equal(s, s_ref)
+
+
+@pytest.mark.parametrize('path', AB_PATHS)
+def test_ab_paths_bit_identical(monkeypatch, pcm, path):
+    _same_as_conv_h3(monkeypatch, pcm, AB_PATHS[path])
+
+
+@pytest.mark.parametrize('path', AB_PATHS)
+@pytest.mark.parametrize('n', [1, 2, 5])
+def test_ab_paths_small_batches(monkeypatch, pcm, n, path):
+    """one clip: 32 rows at C = 128, fewer than any workgroup's (every row clamped at both batch ends);
+    five clips: 640 rows at C = 32, workgroups straddle clip boundaries"""
+    _same_as_conv_h3(monkeypatch, pcm[:n], AB_PATHS[path])
