@@ -153,6 +153,10 @@ struct mmla_ctx {
   // OD blocks 1-3 as rolling column strips (rbs.hip); env MMLA_RB_TILE=1 at create: the 16 x 16 tile
   // kernels of resblk.hip instead
   bool rbs = true;
+  // ... blocks 2-3 with the 3x3 conv's weights copied to LDS once per strip (rbs_w1l.hip); env
+  // MMLA_NO_RBS_W1L=1 at create: rbs.hip's kernel, which streams them from global memory every chunk
+  // (A/B, bit-identical)
+  bool rbs_w1l = true;
   // batches of <= lstm_split_max clips: the 3xFP16 BiLSTM with each direction's hidden units on eight workgroups
   // (nets.hip bilstm_h3_split_kernel); env MMLA_NO_LSTM_SPLIT=1 at create: one workgroup per direction
   bool lstm_split = true;

@@ -162,6 +162,8 @@ struct OdChoice {
   bool stem;
   // OD_ODU only: strips per workgroup, two for the blocks that are faster so (odu_two_strips)
   int strips;
+  // OD_STRIPS only: blocks 2-3 with the 3x3 conv's weights in LDS (rbs_w1l.hip)
+  bool w1_lds;
 };
 
 bool strips_ok(const ResUnitW& B, bool pool, int h, int w) {
@@ -186,11 +188,14 @@ bool odu_ok(const ResUnitW& B, bool pool, int h, int w) {
 
 // stop: the debug trace's last stage (-1: none); a trace of the stem alone (0) needs it in HBM
 OdChoice od_choose(const mmla_ctx* c, const ResUnitW& B, int b, int h, int w, int stop) {
-  OdChoice k{OD_PAIR, false, 1};
+  OdChoice k{OD_PAIR, false, 1, false};
   if (c->precision != MMLA_PREC_F16X3) return k;
-  if (c->rbs && strips_ok(B, POOL[b], h, w)) k.path = OD_STRIPS;
-  else if (tiles_ok(B, POOL[b])) k.path = OD_TILES;
-  else if (c->odu && odu_ok(B, POOL[b], h, w)) {
+  if (c->rbs && strips_ok(B, POOL[b], h, w)) {
+    k.path = OD_STRIPS;
+    k.w1_lds = c->rbs_w1l && !POOL[b];
+  } else if (tiles_ok(B, POOL[b])) {
+    k.path = OD_TILES;
+  } else if (c->odu && odu_ok(B, POOL[b], h, w)) {
     k.path = OD_ODU;
     k.strips = c->odw && odu_two_strips(h, w, B.ca.cin, B.ca.cout, POOL[b]) ? 2 : 1;
   }
@@ -347,7 +352,7 @@ int run_od_net(mmla_ctx* c, const uint8_t* img_u8, const float* img_f32, int64_t
                                          k.stem ? &W.stem : nullptr, img_u8, img_f32);
         LAUNCH(c, MMLA_STAGE_CONV, flops,
                tiles ? resblk_launch(r, B.ca.cin, B.ca.cout, pool, c->stream)
-                     : rbs_launch(r, B.ca.cin, B.ca.cout, pool, c->stream));
+                     : rbs_launch(r, B.ca.cin, B.ca.cout, pool, k.w1_lds, c->stream));
         break;
       }
       case OD_ODU: {   // t1 stays in LDS, bit-identical to the pair

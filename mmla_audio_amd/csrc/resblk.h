@@ -45,5 +45,9 @@ void resblk_split_weights(const float* w, int taps, int cin, int cout, int kpad,
 // Blocks 1-3 as rolling 16-column strips on 32x32x16 MFMAs (rbs.hip).  The weights are in the
 // conv_h3 layout (conv_h3_split_weights: w1h / w1l the 3x3, w2h / w2l the (4,1), wsh / wsl the 1x1
 // shortcut); a.h / a.w are the block's input size.  Block 1 (pool) needs the stem fused (img8 / imgf).
+// w1_lds (blocks 2-3 only; ignored for block 1): the kernel of rbs_w1l.hip, which keeps the 3x3 conv's
+// weights in LDS for the whole strip.  Same arguments, same bits.
 bool rbs_supported(int h, int w, int cin, int c, bool pool);
-hipError_t rbs_launch(const ResBlkArgs& a, int cin, int c, bool pool, hipStream_t stream);
+hipError_t rbs_launch(const ResBlkArgs& a, int cin, int c, bool pool, bool w1_lds, hipStream_t stream);
+// rbs_launch's callee for w1_lds (rbs_w1l.hip): blocks 2-3, arguments already checked
+hipError_t rbs_w1l_launch(const ResBlkArgs& a, hipStream_t stream);
