@@ -262,6 +262,53 @@ int mmla_si_head_fit(mmla_ctx* ctx, const float* emb, const int32_t* labels, int
                      const float* w0, const float* b0, const int32_t* perm, float* w, float* b,
                      float* history, uint32_t flags);
 
+/*
+ * Speaker registration, stage 2 of transfer_learning (speaker_identification.py:438-454): the whole
+ * network trainable under a fresh RMSprop (the reference: lr 1e-6, 20 epochs, batch 8).  Float32 HIP
+ * (si_bwd.hip), stated from the script and Keras 2.6's published source; TensorFlow is not available
+ * here: parity with TF itself is unpinned.
+ *   graph     SI-NET with the sigmoid head.  BatchNorm runs with its moving statistics, eps 1e-3 (the
+ *             base is called with training=False, :406, which stays in force after trainable = True);
+ *             Dropout is the identity; max-pool 'same' (T = 256 / 128 / 64: no pad occurs); Conv1D
+ *             padding for k = 4 is 1 before, 2 after.
+ *   trainable every Conv1D kernel and bias, every BN gamma and beta, the LSTM kernel, recurrent_kernel
+ *             and bias of both directions, the head.  moving_mean / moving_variance are not: they come
+ *             out bit-equal and their slots of a gradient are 0.
+ *   loss      of a batch of B windows: mean_b[-log(clip(s_c / sum_k s_k, 1e-7, 1 - 1e-7))] + R, with
+ *             R = 0.1 sum w^2 over the kernels of layer_with_weights-20, 22, 24, 26 + 0.2 sum w^2 over
+ *             those of layer_with_weights-33, 35, 37, 39 (kernel_regularizer=l2, :175-206; kernels
+ *             only).  The data term and its gradient at the logits are those of mmla_si_head_fit (zero
+ *             for a sample whose p_c is outside the clip range); R is not divided by B, its gradient
+ *             is 2 lambda w.
+ *   optimiser the update of mmla_si_head_fit (rho 0.9, eps 1e-7 outside the root, momentum 0), every
+ *             accumulator from 0, the head's included; the last batch of an epoch may be short.
+ *   history   [epochs, 4] = loss (data + R, each batch with the weights before its update, sample-
+ *             weighted mean), acc (first-index argmax), val_loss (data + R), val_acc with the weights
+ *             at the end of the epoch; the val columns are NaN when n_val == 0.
+ * Every sum has a fixed order and nothing is accumulated with atomics: the same inputs give the same
+ * bits.  A step is a fixed sequence of launches on the context's stream without host synchronisation.
+ * Both entries work on a copy of `packed` (weights.si_spec(n_classes) order, n_floats floats) and do not
+ * touch the context's loaded model; host or device pointers.
+ *
+ * mmla_si_loss_grad: x [n,256,39], labels [n], n in [1, 4096] as ONE batch -> loss[0] the data term,
+ *   loss[1] R; grad [n_floats] in the packed order.
+ * mmla_si_finetune: x / labels [n_train], val_x / val_labels [n_val] (n_val may be 0, pointers then
+ *   unused), perm [epochs, n_train] the sample order of every epoch -> packed_out [n_floats] (may be
+ *   `packed`), history [epochs, 4].  epochs == 0 returns the input blob.  min(batch, n_train) <= 4096.
+ * MMLA_E_INVALID, before any device work: n_classes outside [1, MMLA_SI_TRAIN_MAX_CLASSES], n_floats
+ * that is not the blob's size for that head, batch < 1, n_train < 1 (n < 1), n_val < 0, epochs < 0, a
+ * null pointer, and in host-pointer calls a label outside [0, K) or a perm row that is not a
+ * permutation (device pointers: the caller guarantees both; a perm entry is clamped into the set and a
+ * label only selects a lane, so a broken contract gives a wrong fit, not an access outside a buffer).
+ */
+int mmla_si_loss_grad(mmla_ctx* ctx, const float* packed, int64_t n_floats, int32_t n_classes,
+                      const float* x, const int32_t* labels, int64_t n, float* loss, float* grad,
+                      uint32_t flags);
+int mmla_si_finetune(mmla_ctx* ctx, const float* packed, int64_t n_floats, int32_t n_classes,
+                     const float* x, const int32_t* labels, int64_t n_train, const float* val_x,
+                     const int32_t* val_labels, int64_t n_val, int32_t epochs, int32_t batch, float lr,
+                     const int32_t* perm, float* packed_out, float* history, uint32_t flags);
+
 /* Fused WAV->class pipelines (no PNG, no host round trip): probs [n,K] f32 (nullable),
  * argmax [n] i32 (nullable; -1 for 'silent' clips), silent [n] u8 (nullable).  'silent' = fewer
  * than 4000 samples (lens[c], or clip_len without lens): OD record_on_pc.py:141-154 logs it and

@@ -97,6 +97,9 @@ SIGNATURES = {
     'mmla_si_embed': [_P, _P, _I64, _P, _U32],
     'mmla_si_head_fit': [_P, _P, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _I32, ctypes.c_float,
                          _P, _P, _P, _P, _P, _P, _U32],
+    'mmla_si_loss_grad': [_P, _P, _I64, _I32, _P, _P, _I64, _P, _P, _U32],
+    'mmla_si_finetune': [_P, _P, _I64, _I32, _P, _P, _I64, _P, _P, _I64, _I32, _I32, ctypes.c_float,
+                         _P, _P, _P, _U32],
     'mmla_od_pipeline': [_P, _P, _I64, _I64, _P, _I32, _P, _P, _P, _U32],
     'mmla_si_pipeline': [_P, _P, _I64, _I64, _P, _I32, _P, _P, _P, _U32],
     'mmla_ssim_u8': [_P, _P, _P, _I64, _I32, _I32, _I32, _P, _U32],
@@ -669,6 +672,51 @@ class Context:
             'mmla_si_head_fit')
         return w, b, hist
 
+    @staticmethod
+    def _si_windows(x, labels, what):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if x.ndim != 3 or x.shape[1:] != (256, 39) or labels.shape != (x.shape[0],):
+            raise ValueError(f'{what} {x.shape} / labels {labels.shape}: expected [n,256,39] and [n]')
+        return x, labels
+
+    def si_loss_grad(self, packed, n_classes, x, labels):
+        """The stage-2 loss of ONE batch and its gradient (mmla_si_loss_grad): packed = the SI blob of
+        weights.pack with an n_classes-way head, x [n,256,39], labels [n] -> (loss float32 [2] = data
+        term, L2 penalty; grad float32 [n_floats] in the packed order, 0 in the moving statistics)."""
+        packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
+        x, labels = self._si_windows(x, labels, 'x')
+        loss = np.empty(2, np.float32)
+        grad = np.empty_like(packed)
+        self._check(self.lib.mmla_si_loss_grad(self.h, _ptr(packed), packed.size, int(n_classes), _ptr(x),
+                                               _ptr(labels), x.shape[0], _ptr(loss), _ptr(grad), 0),
+                    'mmla_si_loss_grad')
+        return loss, grad
+
+    def si_finetune(self, packed, n_classes, x, labels, val_x, val_labels, perm, epochs, batch=8, lr=1e-6):
+        """Stage 2 of a registration (mmla_si_finetune): RMSprop through the whole SI network from the
+        blob `packed`.  x [n,256,39], labels [n]; val_* likewise (None or empty: no validation set);
+        perm [epochs,n] the sample order of every epoch.  -> (packed_out float32 [n_floats], history
+        [epochs,4] = loss, acc, val_loss, val_acc)."""
+        packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
+        x, labels = self._si_windows(x, labels, 'x')
+        n = x.shape[0]
+        epochs = int(epochs)
+        perm = np.ascontiguousarray(perm, dtype=np.int32).reshape(-1, n) if epochs else np.zeros((0, n), np.int32)
+        if perm.shape != (epochs, n):
+            raise ValueError(f'perm {perm.shape}: expected [{epochs},{n}]')
+        nv = 0 if val_labels is None else len(val_labels)
+        vx = vl = None
+        if nv:
+            vx, vl = self._si_windows(val_x, val_labels, 'val_x')
+        out = np.empty_like(packed)
+        hist = np.empty((epochs, 4), np.float32)
+        self._check(self.lib.mmla_si_finetune(
+            self.h, _ptr(packed), packed.size, int(n_classes), _ptr(x), _ptr(labels), n, _ptr(vx), _ptr(vl),
+            nv, epochs, int(batch), float(lr), _ptr(perm) if epochs else None, _ptr(out),
+            _ptr(hist) if epochs else None, 0), 'mmla_si_finetune')
+        return out, hist
+
     def od_pipeline(self, pcm, lens=None):
         """-> (probs [n,2], argmax [n] (-1 = 'silent'), silent [n] bool)."""
         a, ln, L = self._pcm(pcm, lens)
@@ -1055,6 +1103,20 @@ class Context:
             self.h, emb, labels, n_train, val_emb or None, val_labels or None, n_val, n_classes,
             n_restarts, epochs, batch, float(lr), w0, b0, perm, w, b, history or None,
             MMLA_DEVICE_PTR), 'mmla_si_head_fit(dev)')
+
+    def si_loss_grad_dev(self, packed, n_floats, n_classes, x, labels, n, loss, grad):
+        """mmla_si_loss_grad on device buffers (labels in [0, K) are the caller's to guarantee)"""
+        self._check(self.lib.mmla_si_loss_grad(self.h, packed, n_floats, n_classes, x, labels, n, loss, grad,
+                                               MMLA_DEVICE_PTR), 'mmla_si_loss_grad(dev)')
+
+    def si_finetune_dev(self, packed, n_floats, n_classes, x, labels, n_train, val_x, val_labels, n_val,
+                        epochs, batch, lr, perm, packed_out, history):
+        """mmla_si_finetune on device buffers: the caller guarantees labels in [0, K) and that every
+        perm row is a permutation; asynchronous on the context's stream"""
+        self._check(self.lib.mmla_si_finetune(
+            self.h, packed, n_floats, n_classes, x, labels, n_train, val_x or None, val_labels or None,
+            n_val, epochs, batch, float(lr), perm, packed_out, history, MMLA_DEVICE_PTR),
+            'mmla_si_finetune(dev)')
 
 
 _default = {}

@@ -5,6 +5,7 @@
 //   net_runners.cpp  conv_spatial, lstm_run, run_od_net, run_si_net (which kernel runs which block)
 //   pipeline.cpp     staging, micro-batching, the range guard; feature / forward / pipeline entry points
 //   capi.cpp         the auxiliary entry points and the head trainer (mmla_si_head_fit)
+//   si_finetune.cpp  the whole-network trainer (mmla_si_loss_grad, mmla_si_finetune) over si_bwd.hip
 // All but mmla_ctx (the type include/mmla.h names) lives in namespace mmla, which is not exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -259,7 +260,8 @@ enum Slot {
   S_IMG2, S_GATE_Y0, S_GATE_Y1, S_SSIM,   // mmla_od_pipeline_gated / mmla_ssim_u8
   S_NR_PROF, S_COND_Q, S_COND_KEPT,       // profile indices of the gate; mmla_condition's outputs
   S_ROOM_P, S_ROOM_A,                     // mmla_room_pipeline_conditioned: the SI outputs' staging
-  S_ENROL_VAD, S_ENROL_NW                 // mmla_si_enrol_embed: the temporary detectors, the window counts
+  S_ENROL_VAD, S_ENROL_NW,                // mmla_si_enrol_embed: the temporary detectors, the window counts
+  S_FT   // mmla_si_loss_grad / mmla_si_finetune: the blob's copy, its gradient and every activation
 };
 
 // mmla_ctx::cap_buf: staged raw capture, host frames, per-clip entry (d0, prev), converted clips and

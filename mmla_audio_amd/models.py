@@ -191,6 +191,15 @@ class SpeakerIdModel(_Model):
         W[name + '/bias'] = b.copy()
         self.W, self.n_classes, self.head = W, int(w.shape[1]), int(head)
 
+    def set_weights(self, W, n_classes, head=_lib.HEAD_SIGMOID):
+        """Replace every tensor of the model (one ``mmla_load_weights`` of the whole blob): the network
+        a fine-tuned registration produced.  self.W, n_classes and head follow only once the load
+        succeeded."""
+        blob = weights.pack(self.kind, W, int(n_classes))
+        self.ctx.load_weights(self.kind, blob, int(n_classes), int(head))
+        setattr(self.ctx, f'_owner_{self.kind}', self)
+        self.W, self.n_classes, self.head = dict(W), int(n_classes), int(head)
+
     def predict_wavs(self, pcm, lens=None):
         """Fused WAV -> speaker: -> (probs [N,K], argmax [N] (-1 = 'silent'), silent [N])."""
         self._ensure_loaded()

@@ -22,7 +22,8 @@ from .overlap_detection_post_processing import LABELS as _OD_LABELS
 RoomResult = namedtuple('RoomResult', 'od_probs od_argmax si_probs si_argmax silent kept_len pcm',
                         defaults=(None,))
 
-Registration = namedtuple('Registration', 'speaker_id_dict accuracy kept_len n_windows history')
+Registration = namedtuple('Registration', 'speaker_id_dict accuracy kept_len n_windows history '
+                          'fine_tune_history', defaults=(None,))
 
 MEAN = -1      # CaptureFormat.channel: pydub's set_channels(1) of a stereo capture
 
@@ -113,7 +114,7 @@ class Room:
         return np.concatenate([out[i, :lens[i]] for i in range(len(clips))])
 
     def register(self, recordings, names, mic=None, passes=1, silence_remove=True, seed=1, epochs=500,
-                 restarts=1, save_to=None):
+                 restarts=1, save_to=None, fine_tune=False, fine_tune_epochs=20):
         """Enrol the room's speakers (step 2 and 3 of the reference's manual: SpeakerIdentification/scripts/
         record_on_pc.py:300-346) on the context the room ticks on: ``recordings`` is one int16 array per
         speaker -- interleaved capture in a room with a capture format (it goes through ``Room.convert``:
@@ -127,12 +128,19 @@ class Room:
         the deployed bundle and speaker_id_dict.json there, so ``load_model(save_to)`` gives the same model.
         -> Registration(speaker_id_dict {str(k): names[k]}, accuracy (validation, of the kept restart),
         kept_len [K] (the reference asks to re-record when less than 50 s are left), n_windows [K], history
-        [restarts, epochs, 4]).  A speaker with no window left raises ValueError naming the speaker; the
-        room is unchanged when anything raises."""
+        [restarts, epochs, 4], fine_tune_history).  ``fine_tune=True`` adds stage 2 of the reference's
+        transfer_learning (``speaker_identification.fine_tune``): the fitted head plus the base, every
+        layer trainable, `fine_tune_epochs` epochs of RMSprop at 1e-6 on the MFCC windows of the same
+        conditioned recordings (``si_features_seq_batch`` of what the enrolment kept); the room then loads
+        the whole fine-tuned network once instead of the head, ``save_to`` holds it, accuracy is stage 2's
+        final val_acc and fine_tune_history its [fine_tune_epochs, 4] (None without stage 2).  A speaker
+        with no window left raises ValueError naming the speaker; the room is unchanged when anything
+        raises."""
         import json
         import os
 
         from . import _lib, noisereduce, tfbundle
+        from . import speaker_identification as _si
         from .speaker_identification import deployed_weights, fit_registration
         names = [str(x) for x in names]
         K = len(names)
@@ -145,6 +153,9 @@ class Room:
             raise ValueError(f'{K} speakers: the head trainer fits at most {_lib.SI_TRAIN_MAX_CLASSES}')
         if epochs < 1 or restarts < 1 or passes < 0:
             raise ValueError('epochs and restarts must be >= 1, passes >= 0')
+        ft_epochs = int(fine_tune_epochs) if fine_tune else 0
+        if ft_epochs < 0:
+            raise ValueError('fine_tune_epochs must be >= 0')
         ns = self.noises is None
         one = isinstance(self.noises, np.ndarray) and self.noises.ndim == 1
         noises = [] if ns else [np.ascontiguousarray(x, dtype=np.float32).ravel()
@@ -162,24 +173,38 @@ class Room:
         self.si._ensure_loaded()
         if not ns and passes > 0:
             noisereduce._set_noise_bank(self.ctx, noises, 16000)
-        emb, n_windows, kept_len = self.ctx.si_enrol_embed(
+        enrolled = self.ctx.si_enrol_embed(
             recs, profile=mic, passes=passes, silence_remove=silence_remove, vad_mode=self.vad_mode,
-            nonstationary=ns)
+            nonstationary=ns, return_pcm=ft_epochs > 0)
+        emb, n_windows, kept_len = enrolled[:3]
+        out_pcm = enrolled[3] if ft_epochs > 0 else None    # stage 2 needs the windows, not the embeddings
         for k in range(K):
             if n_windows[k] < 1:
                 raise ValueError(f'speaker {names[k]!r}: no audio left after conditioning '
                                  f'({len(recs[k])} samples recorded, {int(kept_len[k])} kept)')
         labels = np.repeat(np.arange(K, dtype=np.int32), n_windows)
         x = np.concatenate([emb[k, :n_windows[k]] for k in range(K)])
-        fit = fit_registration(x, labels, K, seed, 0, epochs, restarts, self.ctx)
+        fit = fit_registration(x, labels, K, seed, 0, epochs, restarts, self.ctx, ft_epochs)
+        W = deployed_weights(self.si.W, fit.w, fit.b)
+        accuracy, ft_history = fit.accuracy, None
+        if ft_epochs > 0:
+            feat, nw = self.ctx.si_features_seq_batch(out_pcm, lens=kept_len)
+            if nw.tolist() != list(n_windows):
+                raise RuntimeError(f'windows of the conditioned recordings {nw.tolist()} != {list(n_windows)}')
+            windows = np.concatenate([feat[k, :n_windows[k]] for k in range(K)])
+            W, ft_history = _si.fine_tune(W, K, windows, labels, fit.plan, ft_epochs, device=self.ctx)
+            accuracy = _si.fine_tune_accuracy(ft_history, fit.plan)
         speaker_id_dict = {str(k): names[k] for k in range(K)}
         if save_to is not None:
             os.makedirs(save_to, exist_ok=True)
-            tfbundle.save_deployed(save_to, deployed_weights(self.si.W, fit.w, fit.b), K)
+            tfbundle.save_deployed(save_to, W, K)
             with open(os.path.join(save_to, 'speaker_id_dict.json'), 'w') as f:
                 json.dump(speaker_id_dict, f)
-        self.si.set_head(fit.w, fit.b, _lib.HEAD_SIGMOID)
-        return Registration(speaker_id_dict, fit.accuracy, kept_len, n_windows, fit.history)
+        if ft_epochs > 0:
+            self.si.set_weights(W, K, _lib.HEAD_SIGMOID)
+        else:
+            self.si.set_head(fit.w, fit.b, _lib.HEAD_SIGMOID)
+        return Registration(speaker_id_dict, accuracy, kept_len, n_windows, fit.history, ft_history)
 
     @staticmethod
     def labels(result, speaker_id_dict):

@@ -5,8 +5,9 @@ the MFCC / delta / delta-delta / pad-to-256 path runs in the ``si_fe`` HIP kerne
 ``make_feature_experiment`` (:317-369), used by the registration/transfer-learning callers, keeps
 its chunked output layout.  ``transfer_learning`` (:401-477) and ``transfer_learning_on_experiment``
 (:480-503), the speaker registration of ``record_on_pc.py:340-346``, run the frozen base once
-(``si_embed``) and fit the sigmoid head in one persistent kernel (``si_train.hip``), then write the
-deployed model with ``tfbundle.save_deployed``.
+(``si_embed``) and fit the sigmoid head in one persistent kernel (``si_train.hip``), optionally
+fine-tune the whole network (stage 2, ``fine_tune=True``: ``si_bwd.hip``), then write the deployed
+model with ``tfbundle.save_deployed``.
 """
 import math
 import os
@@ -127,14 +128,17 @@ def _stratified_split(rng, idx, labels, ratio):
     return np.sort(np.concatenate(keep)), np.sort(np.concatenate(out))
 
 
-def _fit_plan(labels, K, seed, test_split_ratio, epochs, restarts):
+def _fit_plan(labels, K, seed, test_split_ratio, epochs, restarts, fine_tune_epochs=0):
     """Everything random about one registration, drawn with numpy from `seed`: the stratified test
     split (only when test_split_ratio > 0) and 70/30 validation split, and per restart the
     Glorot-uniform initial head (limit sqrt(6 / (512 + K)), zero bias) and the sample order of every
     epoch.  Restart r's draws come from their own generator, so they do not depend on `restarts`.
     Neither sklearn's train_test_split nor TensorFlow's initialiser and shuffle streams are reproduced:
     the same seed gives a different (equally distributed) split, head and order than the reference.
-    -> dict(train, val, test index arrays; w0 [R,512,K] f32; b0 [R,K] f32; perm [R,epochs,n_train] i32)"""
+    fine_tune_epochs > 0 adds perm2, the sample order of every stage-2 epoch, from a generator of its
+    own: every other entry of the plan is the one a stage-1-only registration draws.
+    -> dict(train, val, test index arrays; w0 [R,512,K] f32; b0 [R,K] f32; perm [R,epochs,n_train] i32;
+    perm2 [fine_tune_epochs,n_train] i32)"""
     labels = np.asarray(labels)
     rng = np.random.default_rng([int(seed), 0])
     idx = np.arange(len(labels))
@@ -150,7 +154,12 @@ def _fit_plan(labels, K, seed, test_split_ratio, epochs, restarts):
         w0[r] = rr.uniform(-lim, lim, size=(_lib.SI_EMBED, K))
         for e in range(epochs):
             perm[r, e] = rr.permutation(len(train))
-    return dict(train=train, val=val, test=test, w0=w0, b0=np.zeros((restarts, K), np.float32), perm=perm)
+    r2 = np.random.default_rng([int(seed), 0, 2])
+    perm2 = np.empty((int(fine_tune_epochs), len(train)), np.int32)
+    for e in range(int(fine_tune_epochs)):
+        perm2[e] = r2.permutation(len(train))
+    return dict(train=train, val=val, test=test, w0=w0, b0=np.zeros((restarts, K), np.float32), perm=perm,
+                perm2=perm2)
 
 
 def fit_head(emb, labels, val_emb, val_labels, w0, b0, perm, epochs, batch=16, lr=1e-4, device=None):
@@ -163,26 +172,56 @@ def fit_head(emb, labels, val_emb, val_labels, w0, b0, perm, epochs, batch=16, l
     return ctx.si_head_fit(emb, labels, val_emb, val_labels, w0, b0, perm, epochs, batch, lr)
 
 
-HeadFit = namedtuple('HeadFit', 'w b accuracy history best test')
+HeadFit = namedtuple('HeadFit', 'w b accuracy history best test plan', defaults=(None,))
 
 
-def fit_registration(emb, labels, K, seed, test_split_ratio, epochs, restarts, device=None):
+def fine_tune(W, K, x, labels, plan, epochs=20, batch=8, lr=1e-6, device=None):
+    """Stage 2 of transfer_learning (:438-454) on the device (``mmla_si_finetune``): the whole network
+    of the deployed tensors W (base + K-way sigmoid head) trainable under a fresh RMSprop(lr), `epochs`
+    epochs of batch `batch` over the plan's training windows in the plan's stage-2 order (``perm2``),
+    scored on its validation windows after every epoch.  x [n,256,39], labels [n] class indices.
+    -> ({name: tensor} fine-tuned, history [epochs,4] = loss, acc, val_loss, val_acc).  The BatchNorm
+    moving statistics are not trainable and come back bit-equal."""
+    from . import weights
+    ctx = _lib.default_context(device) if device is None or isinstance(device, int) else device
+    x = np.asarray(x)
+    labels = np.asarray(labels, dtype=np.int32)
+    tr, va = plan['train'], plan['val']
+    epochs = int(epochs)
+    if epochs < 0 or len(plan['perm2']) < epochs:
+        raise ValueError(f"{epochs} fine-tune epochs, the plan holds {len(plan['perm2'])} orders")
+    out, hist = ctx.si_finetune(weights.pack(weights.SI, W, K), K, x[tr].astype(np.float32), labels[tr],
+                                x[va].astype(np.float32), labels[va], plan['perm2'][:epochs], epochs, batch, lr)
+    return weights.unpack(weights.SI, out, K), hist
+
+
+_fine_tune = fine_tune      # transfer_learning's fine_tune= keyword shadows the function's name
+
+
+def fine_tune_accuracy(history, plan):
+    """model.evaluate after stage 2: the last epoch's val_acc (without a validation set: its acc)"""
+    return float(history[-1, 3] if len(plan['val']) else history[-1, 1])
+
+
+def fit_registration(emb, labels, K, seed, test_split_ratio, epochs, restarts, device=None,
+                     fine_tune_epochs=0):
     """The part of a registration behind the embeddings, shared by transfer_learning and Room.register:
     the plan drawn from `seed` (``_fit_plan``), `restarts` heads fitted side by side (``fit_head``) and
     the choice between them -- the best final validation accuracy, ties by the lower validation loss,
     then the lower index (without a validation set: the training figures).  emb [n,512], labels [n].
     -> HeadFit(w [512,K], b [K] of the kept restart, its accuracy, history [R,epochs,4], the kept
-    restart's index, the test split's indices)."""
+    restart's index, the test split's indices, the plan; with fine_tune_epochs > 0 the plan also holds
+    stage 2's orders, which changes nothing else)."""
     emb = np.asarray(emb)
     labels = np.asarray(labels, dtype=np.int32)
-    plan = _fit_plan(labels, K, seed, test_split_ratio, epochs, restarts)
+    plan = _fit_plan(labels, K, seed, test_split_ratio, epochs, restarts, fine_tune_epochs)
     tr, va = plan['train'], plan['val']
     w, b, hist = fit_head(emb[tr], labels[tr], emb[va], labels[va], plan['w0'], plan['b0'],
                           plan['perm'], epochs, batch=16, lr=1e-4, device=device)
     last = hist[:, -1]
     score = last[:, 2:] if len(va) else last[:, :2]      # (loss, acc) deciding between restarts
     best = min(range(restarts), key=lambda r: (-score[r, 1], score[r, 0], r))
-    return HeadFit(w[best], b[best], float(score[best, 1]), hist, best, plan['test'])
+    return HeadFit(w[best], b[best], float(score[best, 1]), hist, best, plan['test'], plan)
 
 
 def deployed_weights(base_W, w, b):
@@ -197,17 +236,23 @@ def deployed_weights(base_W, w, b):
 
 
 def transfer_learning(_x, _y, seed, _test_split_ratio, base_model_path, final_model_path, *,
-                      epochs=500, restarts=1, allow_synthetic=False, device=None):
-    """speaker_identification.py:401-477, stage 1: freeze the base model below its Dense head, fit
+                      epochs=500, restarts=1, allow_synthetic=False, device=None, fine_tune=False,
+                      fine_tune_epochs=20):
+    """speaker_identification.py:401-477.  Stage 1: freeze the base model below its Dense head, fit
     Dense(dim, sigmoid, name='customized_dense') on the registration windows (500 epochs, batch 16,
     RMSprop 1e-4), save the deployed model to final_model_path and return its accuracy (on the test
     split when _test_split_ratio > 0, else on the validation split, as the reference).  The base runs
     once (``si_embed``), the whole fit is one kernel launch; `restarts` heads are trained side by side
     and the one with the best final validation accuracy (ties: lower validation loss) is kept.
 
-    Not done: stage 2 (:438-447), which un-freezes the network for 20 epochs of RMSprop at 1e-6 --
-    the saved base tensors equal the loaded ones bit for bit.  Splits, initial head and shuffles come
-    from numpy (``_fit_plan``), not from sklearn / TensorFlow streams."""
+    Stage 2 (:438-454) is opt-in, ``fine_tune=True``: the kept restart's head plus the base go through
+    `fine_tune_epochs` epochs (the reference: 20) of RMSprop at 1e-6, batch 8, with the whole network
+    trainable (``fine_tune`` / ``mmla_si_finetune``: BatchNorm on its moving statistics, the l2 penalties
+    of res units 5, 6, 8, 9 in the loss); the saved bundle then holds the fine-tuned tensors and the
+    returned accuracy is stage 2's final val_acc (with a test split: the deployed model's accuracy on
+    it, as before).  With ``fine_tune=False`` (the default) stage 2 is not run and the saved base
+    tensors equal the loaded ones bit for bit.  Splits, initial head and shuffles come from numpy
+    (``_fit_plan``), not from sklearn / TensorFlow streams."""
     from . import models, tfbundle, weights
     _x = np.asarray(_x)
     _y = np.asarray(_y)
@@ -222,15 +267,24 @@ def transfer_learning(_x, _y, seed, _test_split_ratio, base_model_path, final_mo
         raise ValueError(f'_y names class {int(labels.max())} but holds only {K} distinct rows')
     if epochs < 1 or restarts < 1:
         raise ValueError('epochs and restarts must be >= 1')
+    ft_epochs = int(fine_tune_epochs) if fine_tune else 0
+    if ft_epochs < 0:
+        raise ValueError('fine_tune_epochs must be >= 0')
+    if fine_tune and K > _lib.SI_TRAIN_MAX_CLASSES:
+        raise ValueError(f'{K} speakers: fine-tuning fits at most {_lib.SI_TRAIN_MAX_CLASSES}')
     base = models.load_model(base_model_path, kind=weights.SI, device=device,
                              allow_synthetic=allow_synthetic)
     base._ensure_loaded()
     emb = base.ctx.si_embed(_x)
-    fit = fit_registration(emb, labels, K, seed, _test_split_ratio, epochs, restarts, base.ctx)
+    fit = fit_registration(emb, labels, K, seed, _test_split_ratio, epochs, restarts, base.ctx, ft_epochs)
     te = fit.test
-    os.makedirs(final_model_path, exist_ok=True)
-    tfbundle.save_deployed(final_model_path, deployed_weights(base.W, fit.w, fit.b), K)
+    W = deployed_weights(base.W, fit.w, fit.b)
     accuracy = fit.accuracy
+    if ft_epochs > 0:
+        W, history = _fine_tune(W, K, _x, labels, fit.plan, ft_epochs, device=base.ctx)
+        accuracy = fine_tune_accuracy(history, fit.plan)
+    os.makedirs(final_model_path, exist_ok=True)
+    tfbundle.save_deployed(final_model_path, W, K)
     if len(te):      # model.evaluate(x_test, y_test) on the model just saved
         deployed = models.load_model(final_model_path, device=base.ctx)
         accuracy = float((deployed.predict(_x[te]).argmax(axis=1) == labels[te]).mean())

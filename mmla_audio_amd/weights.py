@@ -201,5 +201,19 @@ def pack(kind, W, n_classes=None):
                            for n, _, _ in spec(kind, n_classes)])
 
 
+def unpack(kind, blob, n_classes=None):
+    """The inverse of ``pack``: the flat float32 blob -> {name: array} in the spec's shapes."""
+    blob = np.asarray(blob, dtype=np.float32).ravel()
+    items = spec(kind, n_classes)
+    if blob.size != sum(int(np.prod(s)) for _, s, _ in items):
+        raise ValueError(f'blob of {blob.size} floats, the spec holds {n_params(kind, n_classes)}')
+    W, at = {}, 0
+    for name, shape, _ in items:
+        n = int(np.prod(shape))
+        W[name] = blob[at:at + n].reshape(shape).copy()
+        at += n
+    return W
+
+
 def n_params(kind, n_classes=None):
     return int(sum(int(np.prod(s)) for _, s, _ in spec(kind, n_classes)))
