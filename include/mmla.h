@@ -132,6 +132,9 @@ int mmla_range_check(mmla_ctx* ctx, int64_t* f32_reruns);
  * clip_len samples (10 x clip_len bytes: 0.41 MB at 40960), a byte per 30 ms frame, and the gate's
  * scratch (~8.3 MB per clip at 40960 samples, at most 512 clips at a time); their micro-batches are
  * multiples of items_per_stream (at least one stream, even where a smaller size was set here).
+ * mmla_od_pipeline_mixed adds per clip the mixed-clip buffer (24000 int16: 48 KB) and 4 bytes of length,
+ * and per host-pointer call the pool and the plan (160 bytes per clip), which stay until
+ * mmla_release_workspace; a host-pointer mmla_od_mix holds the same (2 x clip_len bytes per clip).
  */
 int mmla_set_microbatch(mmla_ctx* ctx, int64_t od_clips, int64_t si_clips);
 /* The micro-batch sizes the next call would use. */
@@ -523,6 +526,49 @@ int mmla_room_pipeline_conditioned(mmla_ctx* ctx, const int16_t* pcm, int64_t n_
                                    int16_t* out_pcm, int32_t* kept_len, float* od_probs,
                                    int32_t* od_argmax, float* si_probs, int32_t* si_argmax,
                                    uint8_t* silent, uint32_t flags);
+
+/*
+ * Overlap synthesis: layered mixes of int16 recordings, the overlay chain of generate_overlap_segment
+ * (OverlapDetection/scripts/data_augmentation.py:20-34): pydub's AudioSegment.overlay(seg, position) with
+ * times = 1 and no gain is audioop.add(canvas[pos : pos + n], seg[:n], 2), n = min(len(seg),
+ * max(0, len(canvas) - pos)), every sum clamped to [-32768, 32767]; a chain of overlays applies that rule
+ * in order, and the order matters because every step saturates.  Bit-identical to CPython's audioop.add
+ * (pydub is not installed here: its slicing arithmetic is restated from its published source, parity
+ * with the library itself is unpinned).
+ *
+ * All clips read one pool [pool_len] int16 (the recordings laid end to end).  Clip c has n_layers[c]
+ * layers, 1 .. MMLA_MIX_MAX_LAYERS; the descriptor arrays src_off (int64 sample offset into the pool),
+ * src_len and pos are [n_clips, MMLA_MIX_MAX_LAYERS], entries at or past n_layers[c] are not read.  Layer 0
+ * is the canvas, at position 0 (pos[c][0] is not used).
+ *   canvas_len = min(src_len[c][0], clip_len)
+ *   s < canvas_len:  v = pool[off_0 + s]; then for l = 1 .. n_layers[c] - 1 in order, where
+ *                    pos_l <= s < pos_l + min(len_l, canvas_len - pos_l):  v = clamp(v + pool[off_l + s - pos_l])
+ *   canvas_len <= s < clip_len:  0
+ * mmla_od_mix: out [n_clips, out_stride] int16, only [0, clip_len) of a row is written (out_stride >=
+ *   clip_len, neither need be a multiple of anything); out_len [n_clips] = canvas_len (nullable).
+ *   clip_len in [1, 600000].  Host or device pointers (MMLA_DEVICE_PTR: one launch, asynchronous).
+ *   Host-pointer calls check the plan before any launch: MMLA_E_INVALID, with the clip and the layer in
+ *   mmla_last_error, for a layer count outside 1..MMLA_MIX_MAX_LAYERS, a negative offset, length or
+ *   position, or off + len > pool_len.  A device plan cannot be seen by the host: the kernel clips every
+ *   layer to the pool and skips one with a negative offset, length or position, so a bad plan gives a
+ *   wrong mix, never a read outside [0, pool_len).
+ * mmla_od_pipeline_mixed: the mix at clip_len = MMLA_OD_CLIP fused in front of mmla_od_pipeline.  The
+ *   pool and the plan are uploaded once per host-pointer call; per micro-batch (OD's size) the mix writes a
+ *   workspace buffer that the front-end and OD-NET read with lens = out_len, so the mixed PCM never
+ *   reaches the host.  silent[c] = canvas_len < 4000, argmax -1 there.  probs, argmax and silent are
+ *   bit-identical to mmla_od_pipeline on the output of mmla_od_mix with lens = out_len.  MMLA_E_INVALID
+ *   as mmla_od_mix, MMLA_E_NOWEIGHTS without OD weights; micro-batching, the range guard and its re-runs
+ *   as the conditioned pipelines (a re-run repeats the network alone on the clips already mixed).
+ *   Workspace per clip of a micro-batch: the mixed clip, 48 KB (mmla_set_microbatch).
+ */
+#define MMLA_MIX_MAX_LAYERS 8
+int mmla_od_mix(mmla_ctx* ctx, const int16_t* pool, int64_t pool_len, int64_t n_clips, const int32_t* n_layers,
+                const int64_t* src_off, const int32_t* src_len, const int32_t* pos, int32_t clip_len,
+                int16_t* out, int64_t out_stride, int32_t* out_len, uint32_t flags);
+int mmla_od_pipeline_mixed(mmla_ctx* ctx, const int16_t* pool, int64_t pool_len, int64_t n_clips,
+                           const int32_t* n_layers, const int64_t* src_off, const int32_t* src_len,
+                           const int32_t* pos, float* probs, int32_t* argmax, uint8_t* silent,
+                           uint32_t flags);
 
 /*
  * Speaker registration in a room, step 2 of the reference's manual: every speaker's recording (a

@@ -7,6 +7,7 @@ is never imported from here.)
 import ctypes
 import os
 import threading
+from collections import namedtuple
 
 import numpy as np
 
@@ -26,6 +27,7 @@ OD_MELS, OD_FRAMES, OD_CLIP = 128, 151, 24000
 SI_FRAMES, SI_DIMS, SI_SILENT_LEN = 256, 39, 4000
 SI_EMBED, SI_TRAIN_MAX_CLASSES = 512, 32
 ENROL_MAX_SAMPLES = 1966080
+MIX_MAX_LAYERS = 8
 
 
 def si_seq_frames(n):
@@ -103,6 +105,9 @@ SIGNATURES = {
     'mmla_od_pipeline': [_P, _P, _I64, _I64, _P, _I32, _P, _P, _P, _U32],
     'mmla_si_pipeline': [_P, _P, _I64, _I64, _P, _I32, _P, _P, _P, _U32],
     'mmla_ssim_u8': [_P, _P, _P, _I64, _I32, _I32, _I32, _P, _U32],
+    # ctx, pool, pool_len, n_clips, n_layers, src_off, src_len, pos, then the outputs
+    'mmla_od_mix': [_P, _P, _I64, _I64, _P, _P, _P, _P, _I32, _P, _I64, _P, _U32],
+    'mmla_od_pipeline_mixed': [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _U32],
     'mmla_od_pipeline_gated': [_P, _P, _I64, _I64, _P, _I32, _I32, ctypes.c_float, _P, _P, _P, _P,
                                _U32],
     'mmla_profile_enable': [_P, ctypes.c_int],
@@ -178,6 +183,39 @@ def png_unfilter(raw, h, row_bytes, bpp):
     if rc != MMLA_OK:
         raise ValueError('PNG image data: unknown scanline filter type')
     return out
+
+
+class MixPlan(namedtuple('MixPlan', 'n_layers src_off src_len pos')):
+    """The descriptors of a batch of layered mixes over one pool (mmla_od_mix): n_layers int32 [n] in
+    1..MIX_MAX_LAYERS; src_off int64, src_len int32, pos int32, each [n, MIX_MAX_LAYERS].  Layer 0 of a clip
+    is its canvas (at position 0), layer l reads src_len samples at pool[src_off] and lands at sample pos."""
+    __slots__ = ()
+
+    @classmethod
+    def from_layers(cls, clips):
+        """clips: per clip a list of (src_off, src_len, pos) layers, the canvas first"""
+        n = len(clips)
+        nl = np.array([len(c) for c in clips], np.int32)
+        if n and (nl.min() < 1 or nl.max() > MIX_MAX_LAYERS):
+            raise ValueError(f'a mix has 1..{MIX_MAX_LAYERS} layers, got {nl.min()}..{nl.max()}')
+        off = np.zeros((n, MIX_MAX_LAYERS), np.int64)
+        ln = np.zeros((n, MIX_MAX_LAYERS), np.int32)
+        pos = np.zeros((n, MIX_MAX_LAYERS), np.int32)
+        for i, c in enumerate(clips):
+            for l, (o, m, p) in enumerate(c):
+                off[i, l], ln[i, l], pos[i, l] = o, m, p
+        return cls(nl, off, ln, pos)
+
+    def arrays(self):
+        """-> the four arrays contiguous in the ABI's types, shapes checked"""
+        nl = np.ascontiguousarray(self.n_layers, dtype=np.int32).reshape(-1)
+        off = np.ascontiguousarray(self.src_off, dtype=np.int64)
+        ln = np.ascontiguousarray(self.src_len, dtype=np.int32)
+        pos = np.ascontiguousarray(self.pos, dtype=np.int32)
+        for name, a in (('src_off', off), ('src_len', ln), ('pos', pos)):
+            if a.shape != (nl.size, MIX_MAX_LAYERS):
+                raise ValueError(f'{name} {a.shape}: expected [{nl.size}, {MIX_MAX_LAYERS}]')
+        return nl, off, ln, pos
 
 
 def _ptr(a):
@@ -744,6 +782,51 @@ class Context:
             self.h, _ptr(a), n, a.shape[1], _ptr(ln), L, int(passes), float(threshold), _ptr(probs),
             _ptr(am), _ptr(silent), _ptr(ssim), _ns(nonstationary)), 'mmla_od_pipeline_gated')
         return probs, am, silent.astype(bool), ssim
+
+    # -- overlap synthesis: layered mixes over one pool of recordings ------------------------------
+    def od_mix(self, pool, plan, clip_len=OD_CLIP):
+        """pydub's overlay chain (audioop.add per layer, clamped, in order) for every clip of `plan` (a
+        MixPlan) over the int16 `pool` -> (clips int16 [n, clip_len], zeros behind each clip's canvas;
+        out_len int32 [n] = the canvas length)."""
+        pool = np.ascontiguousarray(pool, dtype=np.int16).reshape(-1)
+        nl, off, ln, pos = MixPlan(*plan).arrays()
+        n = nl.size
+        out = np.empty((n, int(clip_len)), np.int16)
+        olen = np.empty(n, np.int32)
+        hold = np.zeros(1, np.int16)       # a non-null pool for an empty one
+        self._check(self.lib.mmla_od_mix(self.h, _ptr(pool if pool.size else hold), pool.size, n, _ptr(nl),
+                                         _ptr(off), _ptr(ln), _ptr(pos), int(clip_len), _ptr(out),
+                                         int(clip_len), _ptr(olen), 0), 'mmla_od_mix')
+        return out, olen
+
+    def od_mix_dev(self, pool, pool_len, n, n_layers, src_off, src_len, pos, out, out_stride,
+                   clip_len=OD_CLIP, out_len=0):
+        """device plans are not checked: the kernel reads inside the pool only (see mmla.h)"""
+        self._check(self.lib.mmla_od_mix(self.h, pool, pool_len, n, n_layers, src_off, src_len, pos,
+                                         int(clip_len), out, out_stride, out_len or None, MMLA_DEVICE_PTR),
+                    'mmla_od_mix(dev)')
+
+    def od_pipeline_mixed(self, pool, plan):
+        """od_mix at 24000 samples fused in front of od_pipeline, the mixed clips staying on the device ->
+        (probs [n,2], argmax [n] (-1 = 'silent': a canvas below 4000 samples), silent [n] bool); the bits of
+        od_pipeline(*od_mix(pool, plan))."""
+        pool = np.ascontiguousarray(pool, dtype=np.int16).reshape(-1)
+        nl, off, ln, pos = MixPlan(*plan).arrays()
+        n = nl.size
+        probs = np.empty((n, 2), np.float32)
+        am = np.empty(n, np.int32)
+        silent = np.empty(n, np.uint8)
+        hold = np.zeros(1, np.int16)
+        self._check(self.lib.mmla_od_pipeline_mixed(
+            self.h, _ptr(pool if pool.size else hold), pool.size, n, _ptr(nl), _ptr(off), _ptr(ln), _ptr(pos),
+            _ptr(probs), _ptr(am), _ptr(silent), 0), 'mmla_od_pipeline_mixed')
+        return probs, am, silent.astype(bool)
+
+    def od_pipeline_mixed_dev(self, pool, pool_len, n, n_layers, src_off, src_len, pos, probs=0, argmax=0,
+                              silent=0):
+        self._check(self.lib.mmla_od_pipeline_mixed(
+            self.h, pool, pool_len, n, n_layers, src_off, src_len, pos, probs or None, argmax or None,
+            silent or None, MMLA_DEVICE_PTR), 'mmla_od_pipeline_mixed(dev)')
 
     # -- the PC loops' pre-conditioning (noise gate + silence removal) in front of the networks ---
     def _fused(self, name, n_classes, clips, profile, passes, silence_remove, items_per_stream, return_pcm,

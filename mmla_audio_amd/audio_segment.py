@@ -14,6 +14,10 @@ speaker_identification_post_processing.py:136-188) goes through
 GPU (mmla_ratecv, resample.hip; bit-identical to CPython's audioop, tests/test_gpu_resample.py);
 ``dBFS`` is pydub's ``20 * math.log(audioop.rms / 2^15, 10)`` and ``apply_gain`` ``audioop.mul(data, 2,
 10^(db/20))`` (host arithmetic, pinned against stdlib audioop in tests/test_resample_cpu.py).
+``duration_seconds``, millisecond slices and ``overlay`` are what ``generate_overlap_segment``
+(OverlapDetection/scripts/data_augmentation.py:20-34) calls: ``overlay`` is ``audioop.add`` on the canvas
+behind the position and runs on the GPU (mmla_od_mix, mix.hip; bit-identical to CPython's audioop,
+tests/test_gpu_od_mix.py), the millisecond arithmetic around it is restated from pydub's source.
 ``load`` is librosa.load(path, sr=22050 | None, mono=True) for WAV files; its resampling step is
 resampy's sinc interpolation on the GPU (mmla_resample_sinc) with the ``kaiser_best`` filter built
 here -- resampy is not installed in this image, so that step's parity is unpinned.
@@ -139,6 +143,111 @@ class AudioSegment:
 
     def get_array_of_samples(self):
         return self.data.copy()
+
+    # -- millisecond slices and overlay: the part of pydub that generate_overlap_segment calls
+    # (OverlapDetection/scripts/data_augmentation.py:20-34).  pydub is not installed here: __len__,
+    # frame_count(ms), _parse_position, __getitem__ and overlay are restated from its published source
+    # (0.25), Python-float arithmetic included, and parity with the library itself is unpinned
+    # (tests/mix_ref.py restates the same rules a second time; the sums are pinned against audioop.add).
+    @property
+    def duration_seconds(self):
+        """pydub: frame_count() / frame_rate"""
+        return self.frame_rate and self.frame_count / self.frame_rate or 0.0
+
+    def _ms_len(self):
+        """pydub's len(): round(1000 * (frame_count() / frame_rate)), in its order of operations"""
+        return round(1000 * (float(self.frame_count) / self.frame_rate))
+
+    def _parse_position(self, ms):
+        """pydub: a millisecond position -> int(frame_count(ms=...)) = int(ms * (frame_rate / 1000.0));
+        negative positions count from the end"""
+        if ms < 0:
+            ms = self._ms_len() - abs(ms)
+        if ms == float('inf'):
+            ms = self._ms_len()
+        return int(ms * (self.frame_rate / 1000.0))
+
+    def _frames(self, start, end):
+        """frames [start, end) as pydub's __getitem__ returns them: a slice that ends up to 2 ms past the
+        data (len() rounds to whole milliseconds) is filled up with silence, a larger gap is an error"""
+        ch = self.channels
+        d = self.data[max(start, 0) * ch:max(end, 0) * ch]
+        missing = (end - start) - d.size // ch
+        if missing > 0 and d.size:
+            if missing > 2 * (self.frame_rate / 1000.0):
+                raise ValueError(f'{missing} frames are missing from the slice: pydub raises '
+                                 'TooManyMissingFrames here')
+            d = np.concatenate([d, np.zeros(missing * ch, np.int16)])
+        return d
+
+    def __getitem__(self, millisecond):
+        """seg[a:b] in milliseconds (floats allowed), seg[t] = one millisecond, as pydub"""
+        if isinstance(millisecond, slice):
+            if millisecond.step:
+                raise ValueError('stepped millisecond slices are not built')
+            n = self._ms_len()
+            start = millisecond.start if millisecond.start is not None else 0
+            end = millisecond.stop if millisecond.stop is not None else n
+            start, end = min(start, n), min(end, n)
+        else:
+            start, end = millisecond, millisecond + 1
+        return self._spawn(self._frames(self._parse_position(start), self._parse_position(end)))
+
+    def _overlay_many(self, items):
+        """A chain of pydub overlays on this canvas in ONE pass: items = [(seg, position ms, times)], times
+        < 0 = loop to the end.  Every overlay is audioop.add on the canvas behind its position, clamped,
+        in order (mmla_od_mix on the GPU: the canvas and the segments are the pool, a repeat is one more
+        layer on the same samples, and more than 7 layers go through further calls on the result).
+        pydub's overlay returns seg1[:position] + the mixed seg1[position:], both millisecond slices: the
+        result has int(len() * frame_rate / 1000) frames, i.e. a canvas that is not a whole number of
+        milliseconds is cut, or filled up with silence, to one."""
+        ch = self.channels
+        n_ms = self._ms_len()
+        frames = self._parse_position(n_ms)
+        canvas = self._frames(0, frames) if items else self.data
+        if canvas.size // ch != frames:      # (an empty canvas stays empty)
+            return self._spawn(canvas)
+        layers = []                          # (segment samples, position in samples)
+        for seg, position, times in items:
+            seg = seg.set_frame_rate(self.frame_rate).set_channels(ch)
+            p = self._parse_position(min(position, n_ms)) * ch
+            m = seg.data.size
+            while times and m and p < canvas.size:      # pydub's `while times:`, the last repeat truncated
+                layers.append((seg.data, p))
+                p += m
+                times -= 1
+        if layers and canvas.size > 600000:
+            raise ValueError(f'overlay on a canvas of {canvas.size} samples: the mix takes at most 600000')
+        room = _lib.MIX_MAX_LAYERS - 1
+        for g in range(0, len(layers), room):
+            group = layers[g:g + room]
+            srcs, offs = {}, []      # every distinct segment once in the pool
+            pool = [canvas]
+            used = canvas.size
+            for d, p in group:
+                if id(d) not in srcs:
+                    srcs[id(d)] = used
+                    pool.append(d)
+                    used += d.size
+                offs.append((srcs[id(d)], d.size, p))
+            plan = _lib.MixPlan.from_layers([[(0, canvas.size, 0)] + offs])
+            out, _ = self.ctx.od_mix(np.concatenate(pool), plan, clip_len=canvas.size)
+            canvas = out[0]
+        return self._spawn(canvas)
+
+    def overlay(self, seg, position=0, loop=False, times=None, gain_during_overlay=None):
+        """pydub's overlay: `seg` (brought to this segment's rate and channels) added onto the canvas from
+        `position` ms on, audioop.add per sample (clamped to int16), cut at the canvas's end; times=k
+        repeats it back to back, loop=True until the end.  On the GPU (mmla_od_mix)."""
+        if gain_during_overlay:
+            raise NotImplementedError('gain_during_overlay is not built (the reference never passes it)')
+        if loop:
+            times = -1
+        elif times is None:
+            times = 1
+        elif times == 0:
+            return self._spawn(self.data)
+        return self._overlay_many([(seg, position, times)])
 
     def set_frame_rate(self, frame_rate):
         """audioop.ratecv(data, 2, channels, rate, frame_rate, None) on the GPU"""

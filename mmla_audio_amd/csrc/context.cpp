@@ -365,7 +365,7 @@ int mmla_release_workspace(mmla_ctx* c) {
   if (!c) return MMLA_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
   CHK(ws_release(c));   // (the stream has drained)
-  for (int i = 0; i < 5; ++i)   // the capture conversion's buffers; its states stay
+  for (int i = 0; i < kCapBufs; ++i)   // the capture conversion's and the mix's buffers; the states stay
     if (c->cap_buf[i]) {
       HIPCHK(c, hipFree(c->cap_buf[i]));
       c->cap_buf[i] = nullptr;

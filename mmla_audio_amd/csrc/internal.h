@@ -18,6 +18,7 @@
 #include "../../include/mmla.h"
 #include "nr.h"
 #include "od_fe.h"
+#include "mix.h"
 #include "si_fe.h"
 #include "ssim.h"
 #include "vad.h"
@@ -94,6 +95,7 @@ constexpr int64_t kMinMicrobatch = 64;
 constexpr size_t kPinSlotBytes = 64u << 10;
 constexpr size_t kPinInBytes = 1u << 20;
 constexpr int kPinSlots = 4;   // S_OUT0 .. S_OUT3
+constexpr int kCapBufs = 7;    // mmla_ctx::cap_buf (enum CapBuf)
 
 }  // namespace mmla
 
@@ -206,8 +208,8 @@ struct mmla_ctx {
   // the conversion's buffers (mmla::CapBuf).  Not workspace slots: an allocation failure in the
   // conditioned micro-batches behind the conversion frees every slot (ws_release), and the re-run must
   // find the converted clips
-  void* cap_buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t cap_bytes[5] = {0, 0, 0, 0, 0};
+  void* cap_buf[mmla::kCapBufs] = {};
+  size_t cap_bytes[mmla::kCapBufs] = {};
   // noise gate (nr.hip): tables + the bank of noise profiles' thresholds [nr_profiles][513]
   NrTables* nr_tables = nullptr;
   float* nr_thresh = nullptr;
@@ -261,12 +263,14 @@ enum Slot {
   S_NR_PROF, S_COND_Q, S_COND_KEPT,       // profile indices of the gate; mmla_condition's outputs
   S_ROOM_P, S_ROOM_A,                     // mmla_room_pipeline_conditioned: the SI outputs' staging
   S_ENROL_VAD, S_ENROL_NW,                // mmla_si_enrol_embed: the temporary detectors, the window counts
-  S_FT   // mmla_si_loss_grad / mmla_si_finetune: the blob's copy, its gradient and every activation
+  S_FT,  // mmla_si_loss_grad / mmla_si_finetune: the blob's copy, its gradient and every activation
+  S_MIX, S_MIX_LEN   // mmla_od_mix / mmla_od_pipeline_mixed: a micro-batch's mixed clips and their lengths
 };
 
 // mmla_ctx::cap_buf: staged raw capture, host frames, per-clip entry (d0, prev), converted clips and
-// their lengths
-enum CapBuf { CB_RAW = 0, CB_FRAMES, CB_ITEM, CB_OUT, CB_LENS };
+// their lengths; the pool and the plan of a host-pointer mix (they, too, must outlive a micro-batch that
+// is repeated after an allocation failure)
+enum CapBuf { CB_RAW = 0, CB_FRAMES, CB_ITEM, CB_OUT, CB_LENS, CB_MIX_POOL, CB_MIX_PLAN };
 
 int ws_get(mmla_ctx* c, int slot, size_t bytes, void** out);
 int ws_release(mmla_ctx* c);   // free every workspace slot (after the stream drains)

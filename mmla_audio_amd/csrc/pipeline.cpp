@@ -832,9 +832,151 @@ int capture_pipeline(mmla_ctx* c, CallKind kind, const int16_t* pcm, int64_t n, 
                           out_pcm, kept_len, o, flags);
 }
 
+// ---- layered mixes (mix.hip): mmla_od_mix, mmla_od_pipeline_mixed ------------------------------------
+
+static_assert(MIX_MAX_LAYERS == MMLA_MIX_MAX_LAYERS, "mix.h and mmla.h disagree");
+
+// A mix call's pool and plan.  check() is every test that needs no device; stage() gives the device view
+// (host mode: one upload per call into buffers that outlive the micro-batches).
+struct Mix {
+  const int16_t* pool;
+  int64_t pool_len, n;
+  const int32_t* n_layers;
+  const int64_t* src_off;
+  const int32_t* src_len;
+  const int32_t* pos;
+
+  int check(mmla_ctx* c, bool dev) const {
+    if (n < 0 || pool_len < 0 || (n > 0 && (!pool || !n_layers || !src_off || !src_len || !pos)))
+      return fail(c, MMLA_E_INVALID, "bad mix args");
+    if (dev) return MMLA_OK;   // a device plan cannot be seen here: the kernel reads inside the pool only
+    for (int64_t i = 0; i < n; ++i) {
+      if (n_layers[i] < 1 || n_layers[i] > MMLA_MIX_MAX_LAYERS)
+        return fail(c, MMLA_E_INVALID, "mix clip %lld: %d layers outside 1..%d", (long long)i, n_layers[i],
+                    MMLA_MIX_MAX_LAYERS);
+      for (int l = 0; l < n_layers[i]; ++l) {
+        const int64_t k = i * MMLA_MIX_MAX_LAYERS + l, off = src_off[k];
+        const char* what = off < 0 ? "a negative offset" : src_len[k] < 0 ? "a negative length"
+                           : pos[k] < 0 ? "a negative position"
+                           : off > pool_len - src_len[k] ? "samples past the end of the pool" : nullptr;
+        if (what)
+          return fail(c, MMLA_E_INVALID, "mix clip %lld layer %d has %s (offset %lld, length %d, position %d, "
+                      "pool %lld)", (long long)i, l, what, (long long)off, src_len[k], pos[k], (long long)pool_len);
+      }
+    }
+    return MMLA_OK;
+  }
+
+  // -> a with pool and the four descriptor arrays as device pointers for clip 0
+  int stage(mmla_ctx* c, bool dev, MixArgs* a) const {
+    *a = MixArgs{};
+    a->pool_len = pool_len;
+    if (dev) {
+      a->pool = pool;
+      a->n_layers = n_layers;
+      a->src_off = src_off;
+      a->src_len = src_len;
+      a->pos = pos;
+      return MMLA_OK;
+    }
+    void *pp = nullptr, *pd = nullptr;
+    CHK(cap_get(c, CB_MIX_POOL, (size_t)pool_len * sizeof(int16_t), &pp));
+    if (pool_len > 0)
+      HIPCHK(c, hipMemcpyAsync(pp, pool, (size_t)pool_len * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+    // offsets first (8-byte aligned), then lengths, positions, layer counts
+    const size_t m = (size_t)n * MMLA_MIX_MAX_LAYERS;
+    CHK(cap_get(c, CB_MIX_PLAN, m * 16 + (size_t)n * 4, &pd));
+    char* d = static_cast<char*>(pd);
+    const hipMemcpyKind k = hipMemcpyHostToDevice;
+    HIPCHK(c, hipMemcpyAsync(d, src_off, m * 8, k, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + m * 8, src_len, m * 4, k, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + m * 12, pos, m * 4, k, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + m * 16, n_layers, (size_t)n * 4, k, c->stream));
+    a->pool = static_cast<const int16_t*>(pp);
+    a->src_off = reinterpret_cast<const int64_t*>(d);
+    a->src_len = reinterpret_cast<const int32_t*>(d + m * 8);
+    a->pos = reinterpret_cast<const int32_t*>(d + m * 12);
+    a->n_layers = reinterpret_cast<const int32_t*>(d + m * 16);
+    return MMLA_OK;
+  }
+};
+
+// clips [c0, c0 + cnt) of the staged plan `all` into out [cnt][out_stride], out_len [cnt] (device)
+int mix_run(mmla_ctx* c, const MixArgs& all, int64_t c0, int64_t cnt, int32_t clip_len, int16_t* out,
+            int64_t out_stride, int32_t* out_len) {
+  MixArgs a = all;
+  a.n_clips = cnt;
+  a.n_layers += c0;
+  a.src_off += c0 * MMLA_MIX_MAX_LAYERS;
+  a.src_len += c0 * MMLA_MIX_MAX_LAYERS;
+  a.pos += c0 * MMLA_MIX_MAX_LAYERS;
+  a.clip_len = clip_len;
+  a.out = out;
+  a.out_stride = out_stride;
+  a.out_len = out_len;
+  // algorithmic bytes: the clip written, and at most one pool sample read per layer and sample
+  LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * clip_len * 2.0 * (1 + MMLA_MIX_MAX_LAYERS), mix_launch(a, c->stream));
+  return MMLA_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mmla_od_mix(mmla_ctx* c, const int16_t* pool, int64_t pool_len, int64_t n, const int32_t* n_layers,
+                const int64_t* src_off, const int32_t* src_len, const int32_t* pos, int32_t clip_len,
+                int16_t* out, int64_t out_stride, int32_t* out_len, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  const bool dev0 = flags & MMLA_DEVICE_PTR;
+  const Mix mix{pool, pool_len, n, n_layers, src_off, src_len, pos};
+  if (clip_len < 1 || clip_len > 600000)
+    return fail(c, MMLA_E_INVALID, "clip_len must be in [1, 600000]");
+  if (n > 0 && (!out || out_stride < clip_len))
+    return fail(c, MMLA_E_INVALID, "od_mix needs out and out_stride >= clip_len");
+  CHK(mix.check(c, dev0));
+  if (n == 0) return MMLA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  MixArgs all;
+  CHK(mix.stage(c, dev0, &all));
+  return clip_call(c, FEATURES_OD, n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev) -> int {
+    if (dev) return mix_run(c, all, c0, cnt, clip_len, out + c0 * out_stride, out_stride, out_len ? out_len + c0 : nullptr);
+    void *pm = nullptr, *pl = nullptr;
+    CHK(ws_get(c, S_MIX, (size_t)cnt * clip_len * sizeof(int16_t), &pm));
+    CHK(ws_get(c, S_MIX_LEN, (size_t)cnt * sizeof(int32_t), &pl));
+    CHK(mix_run(c, all, c0, cnt, clip_len, static_cast<int16_t*>(pm), clip_len, static_cast<int32_t*>(pl)));
+    HIPCHK(c, hipMemcpy2DAsync(out + c0 * out_stride, out_stride * sizeof(int16_t), pm, clip_len * sizeof(int16_t),
+                               clip_len * sizeof(int16_t), cnt, hipMemcpyDeviceToHost, c->stream));
+    if (out_len)
+      HIPCHK(c, hipMemcpyAsync(out_len + c0, pl, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    return MMLA_OK;
+  });
+}
+
+int mmla_od_pipeline_mixed(mmla_ctx* c, const int16_t* pool, int64_t pool_len, int64_t n, const int32_t* n_layers,
+                           const int64_t* src_off, const int32_t* src_len, const int32_t* pos, float* probs,
+                           int32_t* argmax, uint8_t* silent, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  const bool dev0 = flags & MMLA_DEVICE_PTR;
+  const Mix mix{pool, pool_len, n, n_layers, src_off, src_len, pos};
+  CHK(mix.check(c, dev0));
+  if (const char* m = missing_weights(c, COND_OD)) return fail(c, MMLA_E_NOWEIGHTS, "%s weights not loaded", m);
+  if (n == 0) return MMLA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  MixArgs all;
+  CHK(mix.stage(c, dev0, &all));
+  // Per micro-batch: the mix into S_MIX / S_MIX_LEN, then mmla_od_pipeline's body on those clips with lens =
+  // out_len under the range guard (a guard re-run repeats the network alone on the clips already mixed)
+  return clip_call(c, COND_OD, n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev) -> int {
+    void *pm = nullptr, *pl = nullptr;
+    CHK(ws_get(c, S_MIX, (size_t)cnt * MMLA_OD_CLIP * sizeof(int16_t), &pm));
+    CHK(ws_get(c, S_MIX_LEN, (size_t)cnt * sizeof(int32_t), &pl));
+    CHK(mix_run(c, all, c0, cnt, MMLA_OD_CLIP, static_cast<int16_t*>(pm), MMLA_OD_CLIP, static_cast<int32_t*>(pl)));
+    const Pcm p{static_cast<const int16_t*>(pm), MMLA_OD_CLIP, static_cast<const int32_t*>(pl), MMLA_OD_CLIP, 0};
+    return guarded(c, dev, c->od_f32_only, [&]() -> int {
+      return od_fe_net(c, p, c0, cnt, dev, probs, argmax, silent);
+    });
+  });
+}
 
 int mmla_od_features(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
                      const int32_t* lens, int32_t clip_len, float* db, float* norm, float* zcr,

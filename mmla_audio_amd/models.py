@@ -119,6 +119,14 @@ class OverlapDetectionModel(_Model):
         self._ensure_loaded()
         return self.ctx.od_pipeline(pcm, lens)
 
+    def predict_mixed(self, pool, plan):
+        """predict_wavs on clips synthesised on the device: `plan` (a _lib.MixPlan, e.g. from
+        data_augmentation.overlap_plan) mixes recordings of the int16 `pool` into 1.5 s clips by the
+        reference's overlay chain (data_augmentation.py:20-34), and the network reads them where they
+        are -> (probs [N,2], argmax [N] (-1 = 'silent': a canvas below 4000 samples), silent [N])."""
+        self._ensure_loaded()
+        return self.ctx.od_pipeline_mixed(pool, plan)
+
     def predict_wavs_gated(self, pcm, noise=None, lens=None, passes=4, threshold=0.3):
         """predict_wavs with the edge loop's silent check (record_on_pi.py:103-124): every clip is
         denoised `passes` times against the float32 noise clip `noise` (16 kHz), a clip whose feature

@@ -22,6 +22,8 @@ from .overlap_detection_post_processing import LABELS as _OD_LABELS
 RoomResult = namedtuple('RoomResult', 'od_probs od_argmax si_probs si_argmax silent kept_len pcm',
                         defaults=(None,))
 
+OverlapCheck = namedtuple('OverlapCheck', 'confusion recall precision probs argmax labels talkers n_windows')
+
 Registration = namedtuple('Registration', 'speaker_id_dict accuracy kept_len n_windows history '
                           'fine_tune_history', defaults=(None,))
 
@@ -113,6 +115,35 @@ class Room:
         out, lens = self.ctx.capture_convert(clips, items_per_stream=len(clips), fresh=True)
         return np.concatenate([out[i, :lens[i]] for i in range(len(clips))])
 
+    def _enrol(self, recordings, mic, passes, silence_remove, return_pcm):
+        """The conditioning of whole recordings that register and overlap_check share: one int16 recording
+        per speaker (through ``Room.convert`` in a room with a capture format), all conditioned in one batch
+        with the room's gate (its noise bank with mic[k], default 0; the non-stationary gate when ``noises
+        is None``) and a fresh detector each -- the live streams' detectors and converters are left alone.
+        -> (the 16 kHz recordings, ``Context.si_enrol_embed``'s result)"""
+        from . import _lib, noisereduce
+        K = len(recordings)
+        ns = self.noises is None
+        one = isinstance(self.noises, np.ndarray) and self.noises.ndim == 1
+        noises = [] if ns else [np.ascontiguousarray(x, dtype=np.float32).ravel()
+                                for x in ([self.noises] if one else self.noises)]
+        mic = np.zeros(K, np.int32) if mic is None else np.ascontiguousarray(mic, dtype=np.int32)
+        if mic.shape != (K,):
+            raise ValueError(f'mic must hold one entry per speaker, got shape {mic.shape}')
+        if not ns and (mic.min() < 0 or mic.max() >= len(noises)):
+            raise ValueError(f'mic must hold one index into the {len(noises)} noise clips per speaker')
+        recs = [self.convert(r) if self.capture is not None
+                else np.ascontiguousarray(r, dtype=np.int16).reshape(-1) for r in recordings]
+        longest = max(len(r) for r in recs)
+        if longest > _lib.ENROL_MAX_SAMPLES:
+            raise ValueError(f'a recording of {longest} samples at 16 kHz exceeds {_lib.ENROL_MAX_SAMPLES}')
+        self.si._ensure_loaded()
+        if not ns and passes > 0:
+            noisereduce._set_noise_bank(self.ctx, noises, 16000)
+        return recs, self.ctx.si_enrol_embed(
+            recs, profile=mic, passes=passes, silence_remove=silence_remove, vad_mode=self.vad_mode,
+            nonstationary=ns, return_pcm=return_pcm)
+
     def register(self, recordings, names, mic=None, passes=1, silence_remove=True, seed=1, epochs=500,
                  restarts=1, save_to=None, fine_tune=False, fine_tune_epochs=20):
         """Enrol the room's speakers (step 2 and 3 of the reference's manual: SpeakerIdentification/scripts/
@@ -139,7 +170,7 @@ class Room:
         import json
         import os
 
-        from . import _lib, noisereduce, tfbundle
+        from . import _lib, tfbundle
         from . import speaker_identification as _si
         from .speaker_identification import deployed_weights, fit_registration
         names = [str(x) for x in names]
@@ -156,26 +187,7 @@ class Room:
         ft_epochs = int(fine_tune_epochs) if fine_tune else 0
         if ft_epochs < 0:
             raise ValueError('fine_tune_epochs must be >= 0')
-        ns = self.noises is None
-        one = isinstance(self.noises, np.ndarray) and self.noises.ndim == 1
-        noises = [] if ns else [np.ascontiguousarray(x, dtype=np.float32).ravel()
-                                for x in ([self.noises] if one else self.noises)]
-        mic = np.zeros(K, np.int32) if mic is None else np.ascontiguousarray(mic, dtype=np.int32)
-        if mic.shape != (K,):
-            raise ValueError(f'mic must hold one entry per speaker, got shape {mic.shape}')
-        if not ns and (mic.min() < 0 or mic.max() >= len(noises)):
-            raise ValueError(f'mic must hold one index into the {len(noises)} noise clips per speaker')
-        recs = [self.convert(r) if self.capture is not None
-                else np.ascontiguousarray(r, dtype=np.int16).reshape(-1) for r in recordings]
-        longest = max(len(r) for r in recs)
-        if longest > _lib.ENROL_MAX_SAMPLES:
-            raise ValueError(f'a recording of {longest} samples at 16 kHz exceeds {_lib.ENROL_MAX_SAMPLES}')
-        self.si._ensure_loaded()
-        if not ns and passes > 0:
-            noisereduce._set_noise_bank(self.ctx, noises, 16000)
-        enrolled = self.ctx.si_enrol_embed(
-            recs, profile=mic, passes=passes, silence_remove=silence_remove, vad_mode=self.vad_mode,
-            nonstationary=ns, return_pcm=ft_epochs > 0)
+        recs, enrolled = self._enrol(recordings, mic, passes, silence_remove, ft_epochs > 0)
         emb, n_windows, kept_len = enrolled[:3]
         out_pcm = enrolled[3] if ft_epochs > 0 else None    # stage 2 needs the windows, not the embeddings
         for k in range(K):
@@ -205,6 +217,42 @@ class Room:
         else:
             self.si.set_head(fit.w, fit.b, _lib.HEAD_SIGMOID)
         return Registration(speaker_id_dict, accuracy, kept_len, n_windows, fit.history, ft_history)
+
+    def overlap_check(self, recordings, mic=None, passes=1, silence_remove=True, n_overlapped=256,
+                      n_single=256, seed=1):
+        """Does the room's OD model tell overlap from single speech for ITS speakers, through its microphones
+        and its noise gate?  ``recordings`` is one int16 recording per speaker, as for ``register``, and is
+        conditioned exactly as ``register`` conditions it (``_enrol``).  What is kept of every recording is
+        cut into whole 24000-sample windows, all windows form one pool, ``data_augmentation.overlap_plan``
+        (seeded by ``seed``) draws n_overlapped mixes of 2-5 speakers in the reference's shares and n_single
+        single windows, and one ``mmla_od_pipeline_mixed`` mixes and classifies them on the context the room
+        ticks on; the mixed PCM never reaches the host.  -> OverlapCheck(confusion [2,2] (rows = truth,
+        columns = predicted), recall and precision of 'overlapped' (overlap_detector_temp.py:455-466), probs
+        [n,2], argmax [n], labels [n] (1 = overlapped), talkers [n], n_windows [K]).  Fewer than two speakers
+        with a window left raises ValueError naming the speakers without one; the room (detectors,
+        converters, models) is unchanged."""
+        import random
+
+        from . import _lib
+        from .data_augmentation import confusion, overlap_plan
+        K = len(recordings)
+        if K < 2:
+            raise ValueError(f'{K} recordings: an overlap check needs at least two speakers')
+        if passes < 0 or n_overlapped < 0 or n_single < 0:
+            raise ValueError('passes, n_overlapped and n_single must be >= 0')
+        recs, (_, _, kept_len, pcm) = self._enrol(recordings, mic, passes, silence_remove, True)
+        n_windows = np.asarray(kept_len, np.int64) // _lib.OD_CLIP
+        if np.count_nonzero(n_windows) < 2:
+            short = [k for k in range(K) if n_windows[k] == 0]
+            raise ValueError(f'speakers {short}: fewer than {_lib.OD_CLIP} samples left after conditioning '
+                             f'({[len(recs[k]) for k in short]} recorded, {[int(kept_len[k]) for k in short]} '
+                             'kept); an overlap check needs two speakers with a whole window')
+        pool = np.concatenate([pcm[k, :n_windows[k] * _lib.OD_CLIP] for k in range(K)])
+        plan, labels, talkers = overlap_plan(n_windows * _lib.OD_CLIP, range(K), n_overlapped, n_single,
+                                             random.Random(seed))
+        probs, argmax, _ = self.od.predict_mixed(pool, plan)
+        matrix, recall, precision = confusion(labels, argmax)
+        return OverlapCheck(matrix, recall, precision, probs, argmax, labels, talkers, n_windows.astype(np.int32))
 
     @staticmethod
     def labels(result, speaker_id_dict):
