@@ -312,6 +312,72 @@ int mmla_si_finetune(mmla_ctx* ctx, const float* packed, int64_t n_floats, int32
                      const int32_t* val_labels, int64_t n_val, int32_t epochs, int32_t batch, float lr,
                      const int32_t* perm, float* packed_out, float* history, uint32_t flags);
 
+/*
+ * Adapting OD-NET to a room: OverlapDetector.continue_train_model (overlap_detector.py:480-509), the
+ * trained detector fitted further on labelled feature images.  Float32 HIP (od_bwd.hip, with conv.hip's
+ * exact-f32 MFMA convolution and si_bwd.hip's BiLSTM), stated from the script and Keras 2.6's published
+ * source; TensorFlow is not available here: parity with TF itself is unpinned.
+ *   graph     OD-NET (oracle/nets_torch.Nets.od_forward): img_u8 [n, h, w, 3] PNG values taken as float;
+ *             stem Conv2D 1x1; nine res blocks BN - ELU - Conv 3x3 - BN - ELU - Conv (4,1) with pool =
+ *             (T,F,F,T,F,F,T,F,F): a pool block adds MaxPool2D(2,'same') of the main path to a 1x1
+ *             stride-2 shortcut.  Conv 'same': the (4,1) kernel pads 1 above, 2 below; the pool pads odd
+ *             sizes with -inf (ties go to the first candidate in row-major order).  Mean over H, a BiLSTM
+ *             over the ceil(w / 8) columns (D 128, U 256, the backward direction over the reversed
+ *             sequence), Dropout(0.25), LeakyReLU(float32(0.3)), Dense(2), softmax.  h in [8, 128], w in
+ *             [8, 151]: 1..19 LSTM steps.
+ *   training  BatchNorm on batch statistics: per channel over n h w, mean and biased variance, eps 1e-3;
+ *             after every step moving <- 0.99 moving + 0.01 batch, the variance Bessel-corrected (x N /
+ *             max(N - 1, 1): rank-4 inputs take Keras's fused path).  Dropout: x * float32(1 / 0.75) *
+ *             keep, keep = drop_mask != 0, an input drawn on the host (no RNG runs on the device); a null
+ *             drop_mask keeps every unit (the scale stays).  Validation passes run in inference mode:
+ *             moving statistics, no dropout, no scale.
+ *   loss      weighted_categorical_crossentropy (:62-79): p <- p / sum p, clip(p, 1e-7, 1 - 1e-7), sample
+ *             loss -class_w[c] log p_c, batch mean.  A sample clipped at either end contributes zero
+ *             gradient.  No L2 term (ResLSTM builds every block with regularized=0).
+ *   optimiser Keras Adadelta, rho 0.95, eps 1e-7: a <- rho a + (1 - rho) g^2; u = sqrt(d + eps) /
+ *             sqrt(a + eps) g; v <- v - lr u; d <- rho d + (1 - rho) u^2; every accumulator from 0 (a
+ *             checkpoint's optimizer slots are not read).  lr [epochs] is constant within an epoch.
+ *             Trainable: every kernel, bias, gamma, beta, the LSTM tensors, the head.  moving_mean /
+ *             moving_variance are not: their gradient slots are 0 and only the update above moves them.
+ *   stopping  EarlyStopping(monitor='val_loss', patience) without restore_best_weights: the fit ends after
+ *             the first epoch whose val_loss has not improved on the best for `patience` epochs; the last
+ *             epoch's weights are returned.  patience == 0 or n_val == 0 turns it off.  It costs one
+ *             history-row read-back per epoch; with it off a fit has no host synchronisation.
+ *             ModelCheckpoint is not mirrored.
+ *   history   [epochs, 5] = loss (each batch in training mode with the weights before its update, sample-
+ *             weighted mean), acc (first-index argmax), val_loss, val_acc (NaN when n_val == 0), lr.  Rows
+ *             after an early stop are NaN.
+ * Every sum has a fixed order and nothing is accumulated with atomics: the same inputs give the same bits.
+ * Both entries work on a copy of `packed` (weights.od_spec() order, n_floats floats) in a workspace slot of
+ * their own and do not touch the context's loaded model.  packed, the images, labels, perm, drop_mask and
+ * every output are host or device pointers (flags); class_w [2] and lr [epochs] are always host pointers.
+ *
+ * mmla_od_loss_grad: ONE training-mode batch of n <= MMLA_OD_TRAIN_MAX_BATCH images, drop_mask [n, 512]
+ *   (nullable) -> loss [1], grad [n_floats] in the packed order, moving_out [n_floats] (nullable): the
+ *   blob with only the moving statistics advanced one step.
+ * mmla_od_finetune: img_u8 / labels [n_train], val_img / val_labels [n_val] (n_val may be 0, pointers then
+ *   unused), perm [epochs, n_train] the sample order of every epoch, drop_mask [epochs, n_train, 512]
+ *   indexed by sample (nullable) -> packed_out [n_floats] (may be `packed`), history [epochs, 5],
+ *   epochs_run [1].  epochs == 0 returns the input blob.
+ * MMLA_E_INVALID, before any device work: n_floats that is not the OD blob's size, h or w outside the
+ * range, batch < 1, min(batch, n_train) > MMLA_OD_TRAIN_MAX_BATCH (n outside [1, MAX_BATCH]), n_train < 1,
+ * n_val < 0, epochs < 0, patience < 0, a null pointer, a class_w or lr that is negative or not finite, and
+ * in host-pointer calls a label outside {0, 1} or a perm row that is not a permutation (device pointers:
+ * a perm entry is clamped into the set, a label selects a lane by its lowest bit, a mask byte is read as
+ * zero / non-zero, so a broken contract gives a wrong fit, not an access outside a buffer).
+ */
+#define MMLA_OD_TRAIN_MAX_BATCH 64
+int mmla_od_loss_grad(mmla_ctx* ctx, const float* packed, int64_t n_floats, const uint8_t* img_u8,
+                      const int32_t* labels, int64_t n, int32_t h, int32_t w, const float* class_w,
+                      const uint8_t* drop_mask, float* loss, float* grad, float* moving_out,
+                      uint32_t flags);
+int mmla_od_finetune(mmla_ctx* ctx, const float* packed, int64_t n_floats, const uint8_t* img_u8,
+                     const int32_t* labels, int64_t n_train, const uint8_t* val_img,
+                     const int32_t* val_labels, int64_t n_val, int32_t h, int32_t w, const float* class_w,
+                     int32_t epochs, int32_t batch, const float* lr, const int32_t* perm,
+                     const uint8_t* drop_mask, int32_t patience, float* packed_out, float* history,
+                     int32_t* epochs_run, uint32_t flags);
+
 /* Fused WAV->class pipelines (no PNG, no host round trip): probs [n,K] f32 (nullable),
  * argmax [n] i32 (nullable; -1 for 'silent' clips), silent [n] u8 (nullable).  'silent' = fewer
  * than 4000 samples (lens[c], or clip_len without lens): OD record_on_pc.py:141-154 logs it and

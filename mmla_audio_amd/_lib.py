@@ -26,6 +26,7 @@ PREC_F32, PREC_F16X3 = 0, 1
 OD_MELS, OD_FRAMES, OD_CLIP = 128, 151, 24000
 SI_FRAMES, SI_DIMS, SI_SILENT_LEN = 256, 39, 4000
 SI_EMBED, SI_TRAIN_MAX_CLASSES = 512, 32
+OD_TRAIN_MAX_BATCH, OD_DROP_UNITS = 64, 512
 ENROL_MAX_SAMPLES = 1966080
 MIX_MAX_LAYERS = 8
 
@@ -101,6 +102,12 @@ SIGNATURES = {
                          _P, _P, _P, _P, _P, _P, _U32],
     'mmla_si_loss_grad': [_P, _P, _I64, _I32, _P, _P, _I64, _P, _P, _U32],
     'mmla_si_finetune': [_P, _P, _I64, _I32, _P, _P, _I64, _P, _P, _I64, _I32, _I32, ctypes.c_float,
+                         _P, _P, _P, _U32],
+    # ctx, packed, n_floats, img_u8, labels, n, h, w, class_w, drop_mask, loss, grad, moving_out
+    'mmla_od_loss_grad': [_P, _P, _I64, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _U32],
+    # ctx, packed, n_floats, img_u8, labels, n_train, val_img, val_labels, n_val, h, w, class_w, epochs, batch,
+    # lr, perm, drop_mask, patience, packed_out, history, epochs_run
+    'mmla_od_finetune': [_P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _I32,
                          _P, _P, _P, _U32],
     'mmla_od_pipeline': [_P, _P, _I64, _I64, _P, _I32, _P, _P, _P, _U32],
     'mmla_si_pipeline': [_P, _P, _I64, _I64, _P, _I32, _P, _P, _P, _U32],
@@ -755,6 +762,73 @@ class Context:
             _ptr(hist) if epochs else None, 0), 'mmla_si_finetune')
         return out, hist
 
+    @staticmethod
+    def _od_images(img, labels, what):
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if img.ndim != 4 or img.shape[3] != 3 or labels.shape != (img.shape[0],):
+            raise ValueError(f'{what} {img.shape} / labels {labels.shape}: expected [n,h,w,3] and [n]')
+        return img, labels
+
+    def od_loss_grad(self, packed, img, labels, class_w=(1.0, 1.0), drop_mask=None, moving=False):
+        """The training-mode loss of ONE batch of OD feature images and its gradient (mmla_od_loss_grad):
+        packed = the OD blob of weights.pack, img uint8 [n,h,w,3], labels [n] in {0,1}, drop_mask uint8
+        [n,512] (None: every unit kept) -> (loss float32 [1], grad float32 [n_floats] in the packed order, 0
+        in the moving statistics[, the blob with only the moving statistics advanced one step])."""
+        packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
+        img, labels = self._od_images(img, labels, 'img')
+        n, h, w = img.shape[:3]
+        cw = np.ascontiguousarray(class_w, dtype=np.float32).reshape(2)
+        if drop_mask is not None:
+            drop_mask = np.ascontiguousarray(drop_mask, dtype=np.uint8)
+            if drop_mask.shape != (n, OD_DROP_UNITS):
+                raise ValueError(f'drop_mask {drop_mask.shape}: expected [{n},{OD_DROP_UNITS}]')
+        loss = np.empty(1, np.float32)
+        grad = np.empty_like(packed)
+        mov = np.empty_like(packed) if moving else None
+        self._check(self.lib.mmla_od_loss_grad(self.h, _ptr(packed), packed.size, _ptr(img), _ptr(labels), n, h, w,
+                                               _ptr(cw), _ptr(drop_mask), _ptr(loss), _ptr(grad), _ptr(mov), 0),
+                    'mmla_od_loss_grad')
+        return (loss, grad, mov) if moving else (loss, grad)
+
+    def od_finetune(self, packed, img, labels, val_img, val_labels, class_w, lr, perm, drop_mask, epochs,
+                    batch=16, patience=0):
+        """OverlapDetector.continue_train_model on the device (mmla_od_finetune): Adadelta through the whole
+        OD network from the blob `packed`, BatchNorm on batch statistics.  img uint8 [n,h,w,3], labels [n];
+        val_* likewise (None or empty: no validation set); lr [epochs]; perm [epochs,n] the sample order
+        of every epoch; drop_mask uint8 [epochs,n,512] indexed by sample (None: every unit kept).
+        -> (packed_out float32 [n_floats], history [epochs,5] = loss, acc, val_loss, val_acc, lr (NaN rows
+        after an early stop), epochs_run)."""
+        packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
+        img, labels = self._od_images(img, labels, 'img')
+        n, h, w = img.shape[:3]
+        epochs = int(epochs)
+        cw = np.ascontiguousarray(class_w, dtype=np.float32).reshape(2)
+        lr = np.ascontiguousarray(lr, dtype=np.float32).ravel()[:epochs]
+        perm = np.ascontiguousarray(perm, dtype=np.int32).reshape(-1, n)[:epochs] if epochs else np.zeros((0, n), np.int32)
+        perm = np.ascontiguousarray(perm)
+        if perm.shape != (epochs, n) or lr.shape != (epochs,):
+            raise ValueError(f'perm {perm.shape} / lr {lr.shape}: expected [{epochs},{n}] and [{epochs}]')
+        if drop_mask is not None:
+            drop_mask = np.ascontiguousarray(np.asarray(drop_mask, dtype=np.uint8)[:epochs])
+            if drop_mask.shape != (epochs, n, OD_DROP_UNITS):
+                raise ValueError(f'drop_mask {drop_mask.shape}: expected [{epochs},{n},{OD_DROP_UNITS}]')
+        nv = 0 if val_labels is None else len(val_labels)
+        vi = vl = None
+        if nv:
+            vi, vl = self._od_images(val_img, val_labels, 'val_img')
+            if vi.shape[1:] != img.shape[1:]:
+                raise ValueError(f'val_img {vi.shape}: expected [n,{h},{w},3]')
+        out = np.empty_like(packed)
+        hist = np.empty((epochs, 5), np.float32)
+        ran = np.zeros(1, np.int32)
+        self._check(self.lib.mmla_od_finetune(
+            self.h, _ptr(packed), packed.size, _ptr(img), _ptr(labels), n, _ptr(vi), _ptr(vl), nv, h, w, _ptr(cw),
+            epochs, int(batch), _ptr(lr) if epochs else None, _ptr(perm) if epochs else None,
+            _ptr(drop_mask) if epochs else None, int(patience), _ptr(out), _ptr(hist) if epochs else None,
+            _ptr(ran), 0), 'mmla_od_finetune')
+        return out, hist, int(ran[0])
+
     def od_pipeline(self, pcm, lens=None):
         """-> (probs [n,2], argmax [n] (-1 = 'silent'), silent [n] bool)."""
         a, ln, L = self._pcm(pcm, lens)
@@ -1200,6 +1274,26 @@ class Context:
             self.h, packed, n_floats, n_classes, x, labels, n_train, val_x or None, val_labels or None,
             n_val, epochs, batch, float(lr), perm, packed_out, history, MMLA_DEVICE_PTR),
             'mmla_si_finetune(dev)')
+
+    def od_loss_grad_dev(self, packed, n_floats, img, labels, n, h, w, class_w, drop_mask, loss, grad,
+                         moving_out=0):
+        """mmla_od_loss_grad on device buffers (class_w: a host float32 [2] array)"""
+        cw = np.ascontiguousarray(class_w, dtype=np.float32).reshape(2)
+        self._check(self.lib.mmla_od_loss_grad(self.h, packed, n_floats, img, labels, n, h, w, _ptr(cw),
+                                               drop_mask or None, loss, grad, moving_out or None,
+                                               MMLA_DEVICE_PTR), 'mmla_od_loss_grad(dev)')
+
+    def od_finetune_dev(self, packed, n_floats, img, labels, n_train, val_img, val_labels, n_val, h, w, class_w,
+                        epochs, batch, lr, perm, drop_mask, patience, packed_out, history, epochs_run):
+        """mmla_od_finetune on device buffers (class_w, lr: host float32 arrays): the caller guarantees
+        labels in {0, 1} and that every perm row is a permutation; asynchronous on the context's stream
+        unless patience > 0 and n_val > 0"""
+        cw = np.ascontiguousarray(class_w, dtype=np.float32).reshape(2)
+        lr = np.ascontiguousarray(lr, dtype=np.float32).ravel()
+        self._check(self.lib.mmla_od_finetune(
+            self.h, packed, n_floats, img, labels, n_train, val_img or None, val_labels or None, n_val, h, w,
+            _ptr(cw), epochs, batch, _ptr(lr), perm, drop_mask or None, patience, packed_out, history,
+            epochs_run, MMLA_DEVICE_PTR), 'mmla_od_finetune(dev)')
 
 
 _default = {}

@@ -1,0 +1,600 @@
+// libmmla: adapting OD-NET to a room -- mmla_od_loss_grad and mmla_od_finetune (include/mmla.h).
+// Which kernel runs which layer, forward and backward, over a copy of the packed OD blob in workspace
+// slot S_ODFT; the context's loaded model is not touched.  Every forward convolution and every stride-1
+// data gradient is conv.hip's conv_launch (exact f32 MFMA); the weight gradients, BatchNorm in training
+// mode, the pools and the head are od_bwd.hip's; the BiLSTM is si_bwd.hip's with T = ceil(w / 8) steps.
+// A training step is a fixed sequence of launches on the context's stream; the only host synchronisation
+// of a fit is the read-back of one history row per epoch when early stopping is on.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "conv.h"
+#include "internal.h"
+#include "od_bwd.h"
+#include "si_bwd.h"
+
+namespace mmla {
+namespace {
+
+constexpr int kMinH = 8, kMaxH = OD_H, kMinW = 8, kMaxW = OD_W;
+constexpr int C = ODB_MAX_C;
+
+// offsets (in floats) of the tensors of weights.od_spec() in the packed blob
+struct BlkOff {
+  size_t bn_in, ca_w, ca_b, bn_mid, cb_w, cb_b, sc_w, sc_b;
+  int cin, cout;
+  bool pool;
+};
+struct OdOff {
+  size_t stem_w, stem_b;
+  BlkOff u[9];
+  size_t lk[2], lr[2], lb[2], dw, db, total;
+};
+
+OdOff od_offsets() {
+  OdOff o{};
+  size_t at = 0;
+  auto take = [&](size_t n) {
+    const size_t r = at;
+    at += n;
+    return r;
+  };
+  o.stem_w = take(3 * 16);
+  o.stem_b = take(16);
+  int cin = 16;
+  for (int i = 0; i < 9; ++i) {
+    BlkOff& u = o.u[i];
+    u.cin = cin;
+    u.cout = CH[i];
+    u.pool = POOL[i];
+    u.bn_in = take(4 * (size_t)cin);
+    u.ca_w = take(9 * (size_t)cin * u.cout);
+    u.ca_b = take(u.cout);
+    u.bn_mid = take(4 * (size_t)u.cout);
+    u.cb_w = take(4 * (size_t)u.cout * u.cout);
+    u.cb_b = take(u.cout);
+    if (u.pool) {
+      u.sc_w = take((size_t)cin * u.cout);
+      u.sc_b = take(u.cout);
+    }
+    cin = u.cout;
+  }
+  for (int d = 0; d < 2; ++d) {
+    o.lk[d] = take((size_t)SIB_LSTM_D * SIB_LSTM_G);
+    o.lr[d] = take((size_t)SIB_LSTM_U * SIB_LSTM_G);
+    o.lb[d] = take(SIB_LSTM_G);
+  }
+  o.dw = take((size_t)ODB_HEAD_D * 2);
+  o.db = take(2);
+  o.total = at;
+  return o;
+}
+
+struct BlkAct {
+  int h, w, ho, wo;        // the block's input and output sizes
+  float *t1, *t2, *out;    // conv 1's output; conv 2's where a pool follows; the block's output
+  uint8_t* idx;            // the pool's winner per output
+  float *stat_in, *stat_mid;
+};
+
+struct Engine {
+  mmla_ctx* c = nullptr;
+  OdOff off;
+  int cap = 0, h = 0, w = 0, T = 0, hl = 0;   // hl x T: the last block's output
+  float cw[2] = {1.0f, 1.0f};
+  float *W = nullptr, *G = nullptr, *acc_g = nullptr, *acc_d = nullptr, *wt = nullptr, *stem_w = nullptr,
+        *stem_b = nullptr, *zero = nullptr, *part = nullptr, *stat_all = nullptr;
+  uint8_t* trainable = nullptr;
+  double* st = nullptr;
+  float *xb = nullptr, *net0 = nullptr, *seq = nullptr, *emb = nullptr, *dzh = nullptr, *demb = nullptr;
+  int32_t* lb = nullptr;
+  uint8_t* mb = nullptr;
+  BlkAct ba[9];
+  float* gbuf[3] = {nullptr, nullptr, nullptr};
+  SibLstm lstm{};
+};
+
+OdbConv geom(int B, int h, int w, int cin, int cout, int kh, int kw, int stride) {
+  const int ho = (h + stride - 1) / stride, wo = (w + stride - 1) / stride;
+  // Keras 'same': the smaller half first ((4,1): 1 above, 2 below)
+  const int ph = std::max((ho - 1) * stride + kh - h, 0) / 2, pw = std::max((wo - 1) * stride + kw - w, 0) / 2;
+  return OdbConv{B, h, w, cin, ho, wo, cout, kh, kw, stride, ph, pw};
+}
+
+void set_dims(Engine& e, int h, int w) {
+  e.h = h;
+  e.w = w;
+  for (int i = 0; i < 9; ++i) {
+    BlkAct& a = e.ba[i];
+    a.h = h;
+    a.w = w;
+    if (POOL[i]) {
+      h = (h + 1) / 2;
+      w = (w + 1) / 2;
+    }
+    a.ho = h;
+    a.wo = w;
+  }
+  e.hl = h;
+  e.T = w;
+}
+
+// carve: first pass (base == nullptr) only measures
+struct Carver {
+  char* base;
+  size_t total = 0;
+  template <typename T>
+  T* take(size_t count) {
+    const size_t at = total;
+    total += (count * sizeof(T) + 255) & ~(size_t)255;
+    return base ? reinterpret_cast<T*>(base + at) : nullptr;
+  }
+};
+
+void carve(Engine& e, Carver& cv, bool train) {
+  const size_t B = e.cap, n = e.off.total, T = e.T;
+  const size_t pix = (size_t)e.h * e.w;
+  e.W = cv.take<float>(n);
+  e.G = cv.take<float>(n);
+  e.acc_g = train ? cv.take<float>(n) : nullptr;
+  e.acc_d = train ? cv.take<float>(n) : nullptr;
+  e.trainable = train ? cv.take<uint8_t>(n) : nullptr;
+  e.wt = cv.take<float>(9 * C * C);
+  e.stem_w = cv.take<float>(3 * 32);
+  e.stem_b = cv.take<float>(32);
+  e.zero = cv.take<float>(C);
+  e.st = cv.take<double>(SIB_ST);
+  e.stat_all = cv.take<float>(18 * (size_t)ODB_STAT);
+  e.xb = cv.take<float>(B * pix * 3);
+  e.lb = cv.take<int32_t>(B);
+  e.mb = cv.take<uint8_t>(B * ODB_HEAD_D);
+  e.net0 = cv.take<float>(B * pix * 16);
+  size_t part = (size_t)ODB_RED_SLABS * 2 * C;
+  part = std::max(part, odb_wgrad_part_floats(geom((int)B, e.h, e.w, 3, 16, 1, 1, 1)));
+  for (int i = 0; i < 9; ++i) {
+    const BlkOff& u = e.off.u[i];
+    BlkAct& a = e.ba[i];
+    const size_t in = (size_t)a.h * a.w, out = (size_t)a.ho * a.wo;
+    a.t1 = cv.take<float>(B * in * u.cout);
+    a.t2 = u.pool ? cv.take<float>(B * in * u.cout) : nullptr;
+    a.idx = u.pool ? cv.take<uint8_t>(B * out * u.cout) : nullptr;
+    a.out = cv.take<float>(B * out * u.cout);
+    a.stat_in = e.stat_all ? e.stat_all + (size_t)(2 * i) * ODB_STAT : nullptr;
+    a.stat_mid = e.stat_all ? e.stat_all + (size_t)(2 * i + 1) * ODB_STAT : nullptr;
+    part = std::max(part, odb_wgrad_part_floats(geom((int)B, a.h, a.w, u.cin, u.cout, 3, 3, 1)));
+    part = std::max(part, odb_wgrad_part_floats(geom((int)B, a.h, a.w, u.cout, u.cout, 4, 1, 1)));
+    if (u.pool) part = std::max(part, odb_wgrad_part_floats(geom((int)B, a.h, a.w, u.cin, u.cout, 1, 1, 2)));
+  }
+  e.part = cv.take<float>(part);
+  e.seq = cv.take<float>(B * T * SIB_LSTM_D);
+  e.emb = cv.take<float>(B * ODB_HEAD_D);
+  e.dzh = cv.take<float>(B * 2);
+  e.demb = cv.take<float>(B * ODB_HEAD_D);
+  for (int q = 0; q < 3; ++q) e.gbuf[q] = cv.take<float>(B * pix * 32);
+  SibLstm& l = e.lstm;
+  l.gates = cv.take<float>(2 * T * B * SIB_LSTM_G);
+  l.cs = cv.take<float>(2 * T * B * SIB_LSTM_U);
+  l.hs = cv.take<float>(2 * T * B * SIB_LSTM_U);
+  l.dz = cv.take<float>(2 * T * B * SIB_LSTM_G);
+  l.dh = cv.take<float>(2 * B * SIB_LSTM_U);
+  l.dc = cv.take<float>(2 * B * SIB_LSTM_U);
+  l.dxs = cv.take<float>(2 * B * T * SIB_LSTM_D);
+  if (cv.base) {
+    for (int d = 0; d < 2; ++d) {
+      l.wk[d] = e.W + e.off.lk[d];
+      l.wr[d] = e.W + e.off.lr[d];
+      l.bias[d] = e.W + e.off.lb[d];
+      l.dwk[d] = e.G + e.off.lk[d];
+      l.dwr[d] = e.G + e.off.lr[d];
+      l.dbias[d] = e.G + e.off.lb[d];
+    }
+    l.seq = e.seq;
+    l.emb = e.emb;
+    l.demb = e.demb;
+    l.T = e.T;
+  }
+}
+
+#define RUN(expr) HIPCHK(e.c, (expr))
+
+// y = conv(act(x)) + bias (+ res): conv.hip on the blob's own kernel (cout is a multiple of 32 but for the
+// stem, which runs on a padded copy)
+hipError_t conv_fwd(const OdbConv& g, const float* x, const float* wt, const float* bias, int cout_pad,
+                    const float* stat, int epi, const float* res, int hp, int wp, float* y, hipStream_t s) {
+  ConvArgs a{};
+  a.x = x;
+  a.wt = wt;
+  a.bias = bias;
+  a.scale = stat ? stat + 2 * C : nullptr;
+  a.shift = stat ? stat + 3 * C : nullptr;
+  a.res = res;
+  a.y = y;
+  a.n = g.B;
+  a.h = g.h;
+  a.w = g.w;
+  a.cin = g.cin;
+  a.ho = g.ho;
+  a.wo = g.wo;
+  a.cout = g.cout;
+  a.cout_pad = cout_pad;
+  a.ldy = g.cout;
+  a.kh = g.kh;
+  a.kw = g.kw;
+  a.stride = g.stride;
+  a.pad_h = g.pad_h;
+  a.pad_w = g.pad_w;
+  a.hp = hp;
+  a.wp = wp;
+  a.pro = stat ? PRO_BN_ELU : PRO_NONE;
+  a.epi = epi;
+  return conv_launch(a, s);
+}
+
+inline int pad32(int c) { return (c + 31) / 32 * 32; }
+
+// the data gradient of the stride-1 convolution g: da [B, h, w, cin] = dy (*) flipped, transposed kernel
+int conv_bwd_data(Engine& e, const OdbConv& g, const float* w, const float* dy, float* da) {
+  hipStream_t s = e.c->stream;
+  const int cp = pad32(g.cin);
+  RUN(odb_conv_transpose(g, cp, w, e.wt, s));
+  const OdbConv t{g.B, g.h, g.w, g.cout, g.h, g.w, g.cin, g.kh, g.kw, 1, g.kh - 1 - g.pad_h, g.kw - 1 - g.pad_w};
+  RUN(conv_fwd(t, dy, e.wt, e.zero, cp, nullptr, EPI_BIAS, nullptr, 0, 0, da, s));
+  return MMLA_OK;
+}
+
+int batch_norm(Engine& e, bool train, const float* x, int64_t n_pos, int c, size_t bn, float* stat) {
+  if (train)
+    RUN(odb_bn_batch(x, n_pos, c, e.W + bn, stat, e.part, e.c->stream));
+  else
+    RUN(odb_bn_moving(e.W + bn, c, stat, e.c->stream));
+  return MMLA_OK;
+}
+
+// forward of the B images in xb / lb / mb; train: batch statistics (the moving ones advance), dropout, the
+// pools' winners and dz kept; else the moving statistics and no dropout.  acc: += loss sum, += hits
+int forward(Engine& e, int B, bool train, double* acc) {
+  hipStream_t s = e.c->stream;
+  const float* W = e.W;
+  RUN(odb_pad_cols(W + e.off.stem_w, 3, 16, 32, e.stem_w, s));
+  RUN(odb_pad_cols(W + e.off.stem_b, 1, 16, 32, e.stem_b, s));
+  RUN(conv_fwd(geom(B, e.h, e.w, 3, 16, 1, 1, 1), e.xb, e.stem_w, e.stem_b, 32, nullptr, EPI_BIAS, nullptr, 0, 0,
+               e.net0, s));
+  const float* net = e.net0;
+  for (int i = 0; i < 9; ++i) {
+    const BlkOff& u = e.off.u[i];
+    const BlkAct& a = e.ba[i];
+    const int64_t n_pos = (int64_t)B * a.h * a.w;
+    CHK(batch_norm(e, train, net, n_pos, u.cin, u.bn_in, a.stat_in));
+    RUN(conv_fwd(geom(B, a.h, a.w, u.cin, u.cout, 3, 3, 1), net, W + u.ca_w, W + u.ca_b, u.cout, a.stat_in,
+                 EPI_BIAS, nullptr, 0, 0, a.t1, s));
+    CHK(batch_norm(e, train, a.t1, n_pos, u.cout, u.bn_mid, a.stat_mid));
+    const OdbConv g2 = geom(B, a.h, a.w, u.cout, u.cout, 4, 1, 1);
+    if (u.pool) {
+      RUN(conv_fwd(g2, a.t1, W + u.cb_w, W + u.cb_b, u.cout, a.stat_mid, EPI_BIAS, nullptr, 0, 0, a.t2, s));
+      if (train) RUN(odb_pool_winner(a.t2, a.idx, B, a.h, a.w, u.cout, s));
+      RUN(conv_fwd(geom(B, a.h, a.w, u.cin, u.cout, 1, 1, 2), net, W + u.sc_w, W + u.sc_b, u.cout, nullptr,
+                   EPI_ADD_POOL, a.t2, a.h, a.w, a.out, s));
+    } else {
+      RUN(conv_fwd(g2, a.t1, W + u.cb_w, W + u.cb_b, u.cout, a.stat_mid, EPI_ADD, net, 0, 0, a.out, s));
+    }
+    net = a.out;
+  }
+  RUN(odb_mean_h(net, e.seq, B, e.hl, e.T, C, s));
+  e.lstm.B = B;
+  RUN(sib_lstm_fwd(e.lstm, s));
+  OdbHead h{e.emb, train ? e.mb : nullptr, W + e.off.dw, W + e.off.db, e.lb, {e.cw[0], e.cw[1]},
+            train ? e.dzh : nullptr, acc, B, (float)B};
+  RUN(odb_head_loss(h, s));
+  return MMLA_OK;
+}
+
+// the gradient of the batch-mean loss at every trainable tensor -> G, after forward(train)
+int backward(Engine& e, int B) {
+  hipStream_t s = e.c->stream;
+  const float* W = e.W;
+  float* G = e.G;
+  OdbHead h{e.emb, e.mb, W + e.off.dw, W + e.off.db, e.lb, {e.cw[0], e.cw[1]}, e.dzh, nullptr, B, (float)B};
+  RUN(odb_head_bwd(h, G + e.off.dw, G + e.off.db, e.demb, s));
+  RUN(sib_lstm_bwd(e.lstm, s));
+  float *cur = e.gbuf[0], *f1 = e.gbuf[1], *f2 = e.gbuf[2];
+  RUN(odb_mean_h_bwd(e.lstm.dxs, cur, B, e.hl, e.T, C, s));
+  for (int i = 8; i >= 0; --i) {
+    const BlkOff& u = e.off.u[i];
+    const BlkAct& a = e.ba[i];
+    const float* inp = i ? e.ba[i - 1].out : e.net0;
+    const int64_t n_in = (int64_t)B * a.h * a.w, n_out = (int64_t)B * a.ho * a.wo;
+    const OdbConv g1 = geom(B, a.h, a.w, u.cin, u.cout, 3, 3, 1), g2 = geom(B, a.h, a.w, u.cout, u.cout, 4, 1, 1);
+    const float* dt2 = cur;
+    if (u.pool) {   // cur = d(shortcut) = d(pooled t2)
+      const OdbConv gs = geom(B, a.h, a.w, u.cin, u.cout, 1, 1, 2);
+      RUN(odb_conv_wgrad(gs, inp, nullptr, nullptr, cur, e.part, G + u.sc_w, s));
+      RUN(odb_bias_grad(cur, n_out, u.cout, e.part, G + u.sc_b, s));
+      RUN(odb_pool_bwd(cur, a.idx, f1, B, a.h, a.w, u.cout, s));
+      dt2 = f1;
+    }
+    RUN(odb_conv_wgrad(g2, a.t1, a.stat_mid + 2 * C, a.stat_mid + 3 * C, dt2, e.part, G + u.cb_w, s));
+    RUN(odb_bias_grad(dt2, n_in, u.cout, e.part, G + u.cb_b, s));
+    CHK(conv_bwd_data(e, g2, W + u.cb_w, dt2, f2));
+    RUN(odb_bn_elu_bwd(a.t1, f2, n_in, u.cout, a.stat_mid, e.part, nullptr, f1, G + u.bn_mid, s));
+    RUN(odb_conv_wgrad(g1, inp, a.stat_in + 2 * C, a.stat_in + 3 * C, f1, e.part, G + u.ca_w, s));
+    RUN(odb_bias_grad(f1, n_in, u.cout, e.part, G + u.ca_b, s));
+    CHK(conv_bwd_data(e, g1, W + u.ca_w, f1, f2));
+    if (!u.pool) {   // d net = d out (the identity shortcut) + the main path's, in place
+      RUN(odb_bn_elu_bwd(inp, f2, n_in, u.cin, a.stat_in, e.part, cur, cur, G + u.bn_in, s));
+      continue;
+    }
+    const OdbConv gs = geom(B, a.h, a.w, u.cin, u.cout, 1, 1, 2);
+    const int cp = pad32(u.cin);
+    RUN(odb_conv_transpose(gs, cp, W + u.sc_w, e.wt, s));
+    RUN(odb_shortcut_bwd_data(gs, cp, cur, e.wt, f1, s));
+    RUN(odb_bn_elu_bwd(inp, f2, n_in, u.cin, a.stat_in, e.part, f1, f1, G + u.bn_in, s));
+    std::swap(cur, f1);
+  }
+  const OdbConv g0 = geom(B, e.h, e.w, 3, 16, 1, 1, 1);
+  RUN(odb_conv_wgrad(g0, e.xb, nullptr, nullptr, cur, e.part, G + e.off.stem_w, s));
+  RUN(odb_bias_grad(cur, (int64_t)B * e.h * e.w, 16, e.part, G + e.off.stem_b, s));
+  return MMLA_OK;
+}
+
+int check_common(mmla_ctx* c, const char* who, int64_t n_floats, int32_t h, int32_t w, const float* class_w) {
+  const int64_t want = (int64_t)od_offsets().total;
+  if (n_floats != want)
+    return fail(c, MMLA_E_INVALID, "%s: n_floats %lld, the OD blob has %lld", who, (long long)n_floats,
+                (long long)want);
+  if (h < kMinH || h > kMaxH || w < kMinW || w > kMaxW)
+    return fail(c, MMLA_E_INVALID, "%s: image %d x %d outside [%d, %d] x [%d, %d]", who, h, w, kMinH, kMaxH, kMinW,
+                kMaxW);
+  if (!class_w) return fail(c, MMLA_E_INVALID, "%s: null pointer", who);
+  for (int k = 0; k < 2; ++k)
+    if (!std::isfinite(class_w[k]) || class_w[k] < 0.0f)
+      return fail(c, MMLA_E_INVALID, "%s: class_w[%d] = %g is negative or not finite", who, k, class_w[k]);
+  return MMLA_OK;
+}
+
+int check_labels(mmla_ctx* c, const char* what, const int32_t* l, int64_t n) {
+  for (int64_t i = 0; i < n; ++i)
+    if (l[i] < 0 || l[i] > 1)
+      return fail(c, MMLA_E_INVALID, "%s[%lld] = %d outside {0, 1}", what, (long long)i, l[i]);
+  return MMLA_OK;
+}
+
+int prepare(Engine& e, bool train) {
+  hipStream_t s = e.c->stream;
+  const size_t wbytes = e.off.total * sizeof(float);
+  HIPCHK(e.c, hipMemsetAsync(e.G, 0, wbytes, s));   // the moving-statistics slots stay 0
+  HIPCHK(e.c, hipMemsetAsync(e.zero, 0, C * sizeof(float), s));
+  HIPCHK(e.c, hipMemsetAsync(e.st, 0, SIB_ST * sizeof(double), s));
+  if (!train) return MMLA_OK;
+  HIPCHK(e.c, hipMemsetAsync(e.acc_g, 0, wbytes, s));   // a new optimiser: every accumulator from 0
+  HIPCHK(e.c, hipMemsetAsync(e.acc_d, 0, wbytes, s));
+  HIPCHK(e.c, hipMemsetAsync(e.trainable, 1, e.off.total, s));
+  for (int i = 0; i < 9; ++i) {   // trainable = everything but moving_mean / moving_variance
+    const BlkOff& u = e.off.u[i];
+    HIPCHK(e.c, hipMemsetAsync(e.trainable + u.bn_in + 2 * u.cin, 0, 2 * (size_t)u.cin, s));
+    HIPCHK(e.c, hipMemsetAsync(e.trainable + u.bn_mid + 2 * u.cout, 0, 2 * (size_t)u.cout, s));
+  }
+  return MMLA_OK;
+}
+
+}  // namespace
+}  // namespace mmla
+
+using namespace mmla;
+
+#undef RUN
+#define RUN(expr) HIPCHK(c, (expr))
+
+extern "C" {
+
+int mmla_od_loss_grad(mmla_ctx* c, const float* packed, int64_t n_floats, const uint8_t* img_u8,
+                      const int32_t* labels, int64_t n, int32_t h, int32_t w, const float* class_w,
+                      const uint8_t* drop_mask, float* loss, float* grad, float* moving_out, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  CHK(check_common(c, "od_loss_grad", n_floats, h, w, class_w));
+  if (n < 1 || n > MMLA_OD_TRAIN_MAX_BATCH)
+    return fail(c, MMLA_E_INVALID, "od_loss_grad: n %lld outside [1, %d]", (long long)n, MMLA_OD_TRAIN_MAX_BATCH);
+  if (!packed || !img_u8 || !labels || !loss || !grad) return fail(c, MMLA_E_INVALID, "od_loss_grad: null pointer");
+  const bool dev = flags & MMLA_DEVICE_PTR;
+  if (!dev) CHK(check_labels(c, "labels", labels, n));
+  HIPCHK(c, hipSetDevice(c->device));
+  Engine e;
+  e.c = c;
+  e.cap = (int)n;
+  e.off = od_offsets();
+  e.cw[0] = class_w[0];
+  e.cw[1] = class_w[1];
+  set_dims(e, h, w);
+  const size_t img_bytes = (size_t)h * w * 3;
+  float* lp = nullptr;
+  uint8_t *simg = nullptr, *smask = nullptr;
+  int32_t* sl = nullptr;
+  size_t total = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    void* p = nullptr;
+    if (pass) CHK(ws_get(c, S_ODFT, total, &p));
+    Carver cv{static_cast<char*>(p)};
+    carve(e, cv, false);
+    lp = cv.take<float>(1);
+    if (!dev) {
+      simg = cv.take<uint8_t>((size_t)n * img_bytes);
+      sl = cv.take<int32_t>(n);
+      smask = drop_mask ? cv.take<uint8_t>((size_t)n * ODB_HEAD_D) : nullptr;
+    }
+    total = cv.total;
+  }
+  hipStream_t s = c->stream;
+  const size_t wbytes = e.off.total * sizeof(float);
+  const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  const hipMemcpyKind out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const uint8_t *dimg = img_u8, *dmask = drop_mask;
+  const int32_t* dl = labels;
+  if (!dev) {
+    HIPCHK(c, hipMemcpyAsync(simg, img_u8, (size_t)n * img_bytes, in, s));
+    HIPCHK(c, hipMemcpyAsync(sl, labels, (size_t)n * sizeof(int32_t), in, s));
+    if (drop_mask) HIPCHK(c, hipMemcpyAsync(smask, drop_mask, (size_t)n * ODB_HEAD_D, in, s));
+    dimg = simg;
+    dl = sl;
+    dmask = smask;
+  }
+  HIPCHK(c, hipMemcpyAsync(e.W, packed, wbytes, in, s));
+  CHK(prepare(e, false));
+  RUN(odb_gather(dimg, dl, dmask, nullptr, 0, (int)n, (int)n, (int)img_bytes, e.xb, e.lb, e.mb, s));
+  CHK(forward(e, (int)n, true, e.st));
+  CHK(backward(e, (int)n));
+  RUN(odb_loss_out(e.st, (int)n, lp, s));
+  HIPCHK(c, hipMemcpyAsync(grad, e.G, wbytes, out, s));
+  HIPCHK(c, hipMemcpyAsync(loss, lp, sizeof(float), out, s));
+  // the forward advanced the copy's moving statistics and nothing else of it
+  if (moving_out) HIPCHK(c, hipMemcpyAsync(moving_out, e.W, wbytes, out, s));
+  return finish(c, dev);
+}
+
+int mmla_od_finetune(mmla_ctx* c, const float* packed, int64_t n_floats, const uint8_t* img_u8,
+                     const int32_t* labels, int64_t n_train, const uint8_t* val_img, const int32_t* val_labels,
+                     int64_t n_val, int32_t h, int32_t w, const float* class_w, int32_t epochs, int32_t batch,
+                     const float* lr, const int32_t* perm, const uint8_t* drop_mask, int32_t patience,
+                     float* packed_out, float* history, int32_t* epochs_run, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  CHK(check_common(c, "od_finetune", n_floats, h, w, class_w));
+  if (batch < 1) return fail(c, MMLA_E_INVALID, "od_finetune: batch %d < 1", batch);
+  if (n_train < 1) return fail(c, MMLA_E_INVALID, "od_finetune: n_train %lld < 1", (long long)n_train);
+  if (n_val < 0 || epochs < 0 || patience < 0 || n_train > (1 << 24) || n_val > (1 << 24))
+    return fail(c, MMLA_E_INVALID, "od_finetune: bad sizes (n_val %lld, epochs %d, patience %d)", (long long)n_val,
+                epochs, patience);
+  if (std::min<int64_t>(batch, n_train) > MMLA_OD_TRAIN_MAX_BATCH)
+    return fail(c, MMLA_E_INVALID, "od_finetune: a batch of more than %d images", MMLA_OD_TRAIN_MAX_BATCH);
+  if (!packed || !img_u8 || !labels || !packed_out || !epochs_run ||
+      (epochs > 0 && (!perm || !history || !lr)) || (n_val > 0 && (!val_img || !val_labels)))
+    return fail(c, MMLA_E_INVALID, "od_finetune: null pointer");
+  for (int ep = 0; ep < epochs; ++ep)
+    if (!std::isfinite(lr[ep]) || lr[ep] < 0.0f)
+      return fail(c, MMLA_E_INVALID, "od_finetune: lr[%d] = %g is negative or not finite", ep, lr[ep]);
+  const bool dev = flags & MMLA_DEVICE_PTR;
+  if (!dev) {
+    CHK(check_labels(c, "labels", labels, n_train));
+    CHK(check_labels(c, "val_labels", val_labels, n_val));
+    std::vector<uint8_t> seen(n_train);
+    for (int ep = 0; ep < epochs; ++ep) {
+      std::fill(seen.begin(), seen.end(), 0);
+      const int32_t* p = perm + (size_t)ep * n_train;
+      for (int64_t i = 0; i < n_train; ++i) {
+        if (p[i] < 0 || p[i] >= n_train || seen[p[i]])
+          return fail(c, MMLA_E_INVALID, "od_finetune: perm row %d is not a permutation of 0..%lld", ep,
+                      (long long)(n_train - 1));
+        seen[p[i]] = 1;
+      }
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  Engine e;
+  e.c = c;
+  e.off = od_offsets();
+  e.cw[0] = class_w[0];
+  e.cw[1] = class_w[1];
+  set_dims(e, h, w);
+  const size_t wbytes = e.off.total * sizeof(float);
+  const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  const hipMemcpyKind out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (epochs == 0) {   // the input blob, unchanged
+    if (!dev) {
+      if (packed_out != packed) std::memcpy(packed_out, packed, wbytes);
+      *epochs_run = 0;
+      return MMLA_OK;
+    }
+    if (packed_out != packed) HIPCHK(c, hipMemcpyAsync(packed_out, packed, wbytes, in, s));
+    HIPCHK(c, hipMemsetAsync(epochs_run, 0, sizeof(int32_t), s));
+    return finish(c, dev);
+  }
+  e.cap = (int)std::max<int64_t>(std::min<int64_t>(batch, n_train), std::min<int64_t>(n_val, 16));
+  const size_t img_bytes = (size_t)h * w * 3;
+  const uint8_t *dimg = img_u8, *dvimg = val_img, *dmask = drop_mask;
+  const int32_t *dl = labels, *dvl = val_labels, *dperm = perm;
+  float* dhist = history;
+  size_t total = 0;
+  uint8_t *simg = nullptr, *svimg = nullptr, *smask = nullptr;
+  int32_t *sl = nullptr, *svl = nullptr, *sperm = nullptr;
+  float *shist = nullptr, *dlr = nullptr;
+  for (int pass = 0; pass < 2; ++pass) {
+    void* p = nullptr;
+    if (pass) CHK(ws_get(c, S_ODFT, total, &p));
+    Carver cv{static_cast<char*>(p)};
+    carve(e, cv, true);
+    dlr = cv.take<float>(epochs);
+    if (!dev) {
+      simg = cv.take<uint8_t>((size_t)n_train * img_bytes);
+      sl = cv.take<int32_t>(n_train);
+      svimg = cv.take<uint8_t>((size_t)n_val * img_bytes);
+      svl = cv.take<int32_t>(n_val);
+      sperm = cv.take<int32_t>((size_t)epochs * n_train);
+      smask = drop_mask ? cv.take<uint8_t>((size_t)epochs * n_train * ODB_HEAD_D) : nullptr;
+      shist = cv.take<float>((size_t)epochs * 5);
+    }
+    total = cv.total;
+  }
+  HIPCHK(c, hipMemcpyAsync(dlr, lr, (size_t)epochs * sizeof(float), hipMemcpyHostToDevice, s));
+  if (!dev) {
+    HIPCHK(c, hipMemcpyAsync(simg, img_u8, (size_t)n_train * img_bytes, in, s));
+    HIPCHK(c, hipMemcpyAsync(sl, labels, (size_t)n_train * sizeof(int32_t), in, s));
+    if (n_val > 0) {
+      HIPCHK(c, hipMemcpyAsync(svimg, val_img, (size_t)n_val * img_bytes, in, s));
+      HIPCHK(c, hipMemcpyAsync(svl, val_labels, (size_t)n_val * sizeof(int32_t), in, s));
+    }
+    HIPCHK(c, hipMemcpyAsync(sperm, perm, (size_t)epochs * n_train * sizeof(int32_t), in, s));
+    if (drop_mask) HIPCHK(c, hipMemcpyAsync(smask, drop_mask, (size_t)epochs * n_train * ODB_HEAD_D, in, s));
+    dimg = simg;
+    dl = sl;
+    dvimg = svimg;
+    dvl = svl;
+    dperm = sperm;
+    dmask = smask;
+    dhist = shist;
+  }
+  HIPCHK(c, hipMemcpyAsync(e.W, packed, wbytes, in, s));
+  CHK(prepare(e, true));
+  RUN(odb_fill(dhist, (int64_t)epochs * 5, __builtin_nanf(""), s));   // rows after an early stop
+  const bool stopping = patience > 0 && n_val > 0;
+  float best = INFINITY;
+  int wait = 0, ran = 0;
+  for (int ep = 0; ep < epochs; ++ep) {
+    const int32_t* order = dperm + (size_t)ep * n_train;
+    const uint8_t* mask = dmask ? dmask + (size_t)ep * n_train * ODB_HEAD_D : nullptr;
+    for (int64_t b0 = 0; b0 < n_train; b0 += batch) {
+      const int nb = (int)std::min<int64_t>(batch, n_train - b0);
+      RUN(odb_gather(dimg, dl, mask, order, (int)b0, nb, (int)n_train, (int)img_bytes, e.xb, e.lb, e.mb, s));
+      CHK(forward(e, nb, true, e.st));
+      CHK(backward(e, nb));
+      RUN(sib_fold_batch(e.st, nb, s));
+      RUN(odb_adadelta(e.W, e.acc_g, e.acc_d, e.G, e.trainable, (int64_t)e.off.total, dlr, ep, s));
+    }
+    for (int64_t v0 = 0; v0 < n_val; v0 += e.cap) {
+      const int nb = (int)std::min<int64_t>(e.cap, n_val - v0);
+      RUN(odb_gather(dvimg, dvl, nullptr, nullptr, (int)v0, nb, (int)n_val, (int)img_bytes, e.xb, e.lb, e.mb, s));
+      CHK(forward(e, nb, false, e.st + 5));
+    }
+    RUN(odb_end_epoch(e.st, (int)n_train, (int)n_val, dlr, ep, dhist + (size_t)ep * 5, s));
+    ran = ep + 1;
+    if (!stopping) continue;
+    // EarlyStopping(monitor='val_loss', patience): one row read back per epoch
+    float row[5];
+    HIPCHK(c, hipMemcpyAsync(row, dhist + (size_t)ep * 5, sizeof(row), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (row[2] < best) {
+      best = row[2];
+      wait = 0;
+    } else if (++wait >= patience) {
+      break;
+    }
+  }
+  HIPCHK(c, hipMemcpyAsync(packed_out, e.W, wbytes, out, s));
+  if (dev) {
+    HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(epochs_run), ran, 1, s));
+  } else {
+    HIPCHK(c, hipMemcpyAsync(history, dhist, (size_t)epochs * 5 * sizeof(float), out, s));
+    *epochs_run = ran;
+  }
+  return finish(c, dev);
+}
+
+}  // extern "C"

@@ -9,7 +9,7 @@
 
 constexpr int SIB_LSTM_U = 256;    // LSTM units per direction
 constexpr int SIB_LSTM_D = 128;    // LSTM input width
-constexpr int SIB_LSTM_T = 8;      // LSTM steps
+constexpr int SIB_LSTM_T = 8;      // LSTM steps of SI-NET (SibLstm::T; OD-NET runs 1..19, od_bwd.h)
 constexpr int SIB_LSTM_G = 4 * SIB_LSTM_U;
 
 struct SibConv {
@@ -54,24 +54,25 @@ struct SibLstm {
   const float* wk[2];     // [128, 1024]
   const float* wr[2];     // [256, 1024]
   const float* bias[2];   // [1024]
-  const float* seq;       // [B, 8, 128]
-  float* gates;           // [2, 8, B, 1024] post-activation i, f, g, o by processing step
-  float* cs;              // [2, 8, B, 256]
-  float* hs;              // [2, 8, B, 256]
-  float* emb;             // [B, 512] = h_fwd(after x[7]), h_bwd(after x[0])
+  const float* seq;       // [B, T, 128]
+  float* gates;           // [2, T, B, 1024] post-activation i, f, g, o by processing step
+  float* cs;              // [2, T, B, 256]
+  float* hs;              // [2, T, B, 256]
+  float* emb;             // [B, 512] = h_fwd(after x[T - 1]), h_bwd(after x[0])
   // backward
   const float* demb;      // [B, 512]
-  float* dz;              // [2, 8, B, 1024] gradient at the gates' pre-activations
+  float* dz;              // [2, T, B, 1024] gradient at the gates' pre-activations
   float* dh;              // [2, B, 256] scratch
   float* dc;              // [2, B, 256] scratch
-  float* dxs;             // [2, B, 8, 128]
+  float* dxs;             // [2, B, T, 128]
   float* dwk[2];          // gradients, the layouts of wk, wr, bias
   float* dwr[2];
   float* dbias[2];
   int B;
+  int T;                  // steps, >= 1 (SI-NET: SIB_LSTM_T)
 };
-hipError_t sib_lstm_fwd(const SibLstm& a, hipStream_t stream);   // 8 launches
-hipError_t sib_lstm_bwd(const SibLstm& a, hipStream_t stream);   // 17 launches
+hipError_t sib_lstm_fwd(const SibLstm& a, hipStream_t stream);   // T launches
+hipError_t sib_lstm_bwd(const SibLstm& a, hipStream_t stream);   // 2 T + 1 launches
 
 struct SibHead {
   const float* emb;        // [B, 512]

@@ -232,12 +232,13 @@ __global__ void avgpool4_bwd_kernel(const float* __restrict__ dxs, float* __rest
 }
 
 // ---- BiLSTM -------------------------------------------------------------------------------------------
-// Buffers are indexed by processing step s: the forward direction reads x[s], the backward one x[7 - s].
+// Buffers are indexed by processing step s of a.T: the forward direction reads x[s], the backward one
+// x[T - 1 - s].
 
 constexpr int LS_NB = 8;    // samples per workgroup
 constexpr int LS_IN = SIB_LSTM_D + SIB_LSTM_U;
 
-__device__ inline int step_time(int dir, int s) { return dir ? SIB_LSTM_T - 1 - s : s; }
+__device__ inline int step_time(int dir, int s, int T) { return dir ? T - 1 - s : s; }
 
 // workgroup = 64 units of one direction x 4 splits of the 384 inputs; thread (u, q) sums its 96 inputs
 // into the four gate columns of unit u for up to 8 samples, the 4 partials are added in LDS in order
@@ -251,16 +252,16 @@ __global__ void __launch_bounds__(LS_NT) lstm_fwd_step_kernel(SibLstm a, int s) 
   const int nb = min(LS_NB, a.B - b0);
   const int ul = threadIdx.x % LS_UB, q4 = threadIdx.x / LS_UB;
   const int u = blockIdx.x * LS_UB + ul;
-  const int t = step_time(dir, s);
+  const int t = step_time(dir, s, a.T);
   const size_t BU = (size_t)a.B * SIB_LSTM_U;
   for (int i = threadIdx.x; i < LS_NB * LS_IN; i += LS_NT) {
     const int b = i / LS_IN, d = i % LS_IN;
     float v = 0.0f;
     if (b < nb) {
       if (d < SIB_LSTM_D)
-        v = a.seq[((size_t)(b0 + b) * SIB_LSTM_T + t) * SIB_LSTM_D + d];
+        v = a.seq[((size_t)(b0 + b) * a.T + t) * SIB_LSTM_D + d];
       else if (s > 0)
-        v = a.hs[((size_t)dir * SIB_LSTM_T + s - 1) * BU + (size_t)(b0 + b) * SIB_LSTM_U + d - SIB_LSTM_D];
+        v = a.hs[((size_t)dir * a.T + s - 1) * BU + (size_t)(b0 + b) * SIB_LSTM_U + d - SIB_LSTM_D];
     }
     xin[b][d] = v;
   }
@@ -303,7 +304,7 @@ __global__ void __launch_bounds__(LS_NT) lstm_fwd_step_kernel(SibLstm a, int s) 
 #pragma unroll
   for (int b = 0; b < LS_NB; ++b) {
     if (b < nb) {
-      const size_t row = ((size_t)dir * SIB_LSTM_T + s) * a.B + b0 + b;
+      const size_t row = ((size_t)dir * a.T + s) * a.B + b0 + b;
       const float gi = sigmoidf_(acc[0][b]), gf = sigmoidf_(acc[1][b]);
       const float gg = tanhf(acc[2][b]), go = sigmoidf_(acc[3][b]);
       const float cp = s > 0 ? a.cs[(row - a.B) * SIB_LSTM_U + u] : 0.0f;
@@ -316,7 +317,7 @@ __global__ void __launch_bounds__(LS_NT) lstm_fwd_step_kernel(SibLstm a, int s) 
       gr[3 * SIB_LSTM_U] = go;
       a.cs[row * SIB_LSTM_U + u] = cv;
       a.hs[row * SIB_LSTM_U + u] = hv;
-      if (s == SIB_LSTM_T - 1) a.emb[(size_t)(b0 + b) * 2 * SIB_LSTM_U + dir * SIB_LSTM_U + u] = hv;
+      if (s == a.T - 1) a.emb[(size_t)(b0 + b) * 2 * SIB_LSTM_U + dir * SIB_LSTM_U + u] = hv;
     }
   }
 }
@@ -327,10 +328,10 @@ __global__ void lstm_bwd_gates_kernel(SibLstm a, int s) {
   const int n = 2 * a.B * SIB_LSTM_U;
   if (i >= n) return;
   const int u = i % SIB_LSTM_U, b = (i / SIB_LSTM_U) % a.B, dir = i / (SIB_LSTM_U * a.B);
-  const bool last = s == SIB_LSTM_T - 1;
+  const bool last = s == a.T - 1;
   const float dh = last ? a.demb[(size_t)b * 2 * SIB_LSTM_U + dir * SIB_LSTM_U + u] : a.dh[i];
   float dc = last ? 0.0f : a.dc[i];
-  const size_t row = ((size_t)dir * SIB_LSTM_T + s) * a.B + b;
+  const size_t row = ((size_t)dir * a.T + s) * a.B + b;
   const float* gr = a.gates + row * SIB_LSTM_G + u;
   const float gi = gr[0], gf = gr[SIB_LSTM_U], gg = gr[2 * SIB_LSTM_U], go = gr[3 * SIB_LSTM_U];
   const float tc = tanhf(a.cs[row * SIB_LSTM_U + u]);
@@ -354,7 +355,7 @@ __global__ void __launch_bounds__(256) lstm_bwd_mm_kernel(SibLstm a, int s, int 
   const int nb = min(LS_NB, a.B - b0);
   const float* __restrict__ wrow = r < SIB_LSTM_D ? a.wk[dir] + (size_t)r * SIB_LSTM_G
                                                   : a.wr[dir] + (size_t)(r - SIB_LSTM_D) * SIB_LSTM_G;
-  const float* __restrict__ dz = a.dz + (((size_t)dir * SIB_LSTM_T + s) * a.B + b0) * SIB_LSTM_G;
+  const float* __restrict__ dz = a.dz + (((size_t)dir * a.T + s) * a.B + b0) * SIB_LSTM_G;
   float acc[LS_NB];
 #pragma unroll
   for (int b = 0; b < LS_NB; ++b) acc[b] = 0.0f;
@@ -370,10 +371,10 @@ __global__ void __launch_bounds__(256) lstm_bwd_mm_kernel(SibLstm a, int s, int 
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) acc[b] += __shfl_xor(acc[b], m, 64);
   if (lane == 0) {
-    const int t = step_time(dir, s);
+    const int t = step_time(dir, s, a.T);
     for (int b = 0; b < nb; ++b) {
       if (r < SIB_LSTM_D)
-        a.dxs[(((size_t)dir * a.B + b0 + b) * SIB_LSTM_T + t) * SIB_LSTM_D + r] = acc[b];
+        a.dxs[(((size_t)dir * a.B + b0 + b) * a.T + t) * SIB_LSTM_D + r] = acc[b];
       else
         a.dh[((size_t)dir * a.B + b0 + b) * SIB_LSTM_U + r - SIB_LSTM_D] = acc[b];
     }
@@ -385,14 +386,14 @@ __global__ void __launch_bounds__(256) lstm_bwd_w_kernel(SibLstm a) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   const int r = blockIdx.y, dir = blockIdx.z;
   float acc = 0.0f;
-  for (int s = 0; s < SIB_LSTM_T; ++s) {
+  for (int s = 0; s < a.T; ++s) {
     if (r >= SIB_LSTM_D && r < LS_IN && s == 0) continue;   // h before the first step is 0
-    const int t = step_time(dir, s);
+    const int t = step_time(dir, s, a.T);
     for (int b = 0; b < a.B; ++b) {
-      const size_t row = ((size_t)dir * SIB_LSTM_T + s) * a.B + b;
+      const size_t row = ((size_t)dir * a.T + s) * a.B + b;
       float in = 1.0f;
       if (r < SIB_LSTM_D)
-        in = a.seq[((size_t)b * SIB_LSTM_T + t) * SIB_LSTM_D + r];
+        in = a.seq[((size_t)b * a.T + t) * SIB_LSTM_D + r];
       else if (r < LS_IN)
         in = a.hs[(row - a.B) * SIB_LSTM_U + r - SIB_LSTM_D];
       acc = fmaf(in, a.dz[row * SIB_LSTM_G + j], acc);
@@ -617,7 +618,7 @@ hipError_t sib_avgpool4_bwd(const float* dxs, float* dx, int B, hipStream_t stre
 
 hipError_t sib_lstm_fwd(const SibLstm& a, hipStream_t stream) {
   const dim3 grid(SIB_LSTM_U / LS_UB, 2, (a.B + LS_NB - 1) / LS_NB);
-  for (int s = 0; s < SIB_LSTM_T; ++s) {
+  for (int s = 0; s < a.T; ++s) {
     hipLaunchKernelGGL(lstm_fwd_step_kernel, grid, dim3(LS_NT), 0, stream, a, s);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -626,7 +627,7 @@ hipError_t sib_lstm_fwd(const SibLstm& a, hipStream_t stream) {
 }
 
 hipError_t sib_lstm_bwd(const SibLstm& a, hipStream_t stream) {
-  for (int s = SIB_LSTM_T - 1; s >= 0; --s) {
+  for (int s = a.T - 1; s >= 0; --s) {
     hipLaunchKernelGGL(lstm_bwd_gates_kernel, grid1((int64_t)2 * a.B * SIB_LSTM_U, 256), dim3(256), 0, stream,
                        a, s);
     hipError_t e = hipGetLastError();

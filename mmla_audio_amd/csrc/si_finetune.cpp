@@ -149,6 +149,7 @@ void carve(Engine& e, Carver& cv, bool train) {
       l.dbias[d] = e.G + e.off.lb[d];
     }
     l.seq = e.seq;
+    l.T = SIB_LSTM_T;
     l.emb = e.emb;
     l.demb = e.demb;
   }

@@ -106,6 +106,15 @@ class OverlapDetectionModel(_Model):
         super().__init__(W, 2, _lib.HEAD_SOFTMAX, device, synthetic)
         setattr(self.ctx, f'_owner_{self.kind}', self)
 
+    def set_weights(self, W):
+        """Replace every tensor of the model in place (one ``mmla_load_weights`` of the whole blob): the
+        network an adaptation produced (``overlap_detector.continue_train``).  self.W follows only once
+        the load succeeded."""
+        blob = weights.pack(self.kind, W)
+        self.ctx.load_weights(self.kind, blob, 2, _lib.HEAD_SOFTMAX)
+        setattr(self.ctx, f'_owner_{self.kind}', self)
+        self.W = dict(W)
+
     def predict(self, x, batch_size=None, verbose=0):
         self._ensure_loaded()
         x = np.asarray(x)

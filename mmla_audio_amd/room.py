@@ -24,6 +24,8 @@ RoomResult = namedtuple('RoomResult', 'od_probs od_argmax si_probs si_argmax sil
 
 OverlapCheck = namedtuple('OverlapCheck', 'confusion recall precision probs argmax labels talkers n_windows')
 
+OverlapAdapt = namedtuple('OverlapAdapt', 'before after history epochs_run n_windows')
+
 Registration = namedtuple('Registration', 'speaker_id_dict accuracy kept_len n_windows history '
                           'fine_tune_history', defaults=(None,))
 
@@ -253,6 +255,79 @@ class Room:
         probs, argmax, _ = self.od.predict_mixed(pool, plan)
         matrix, recall, precision = confusion(labels, argmax)
         return OverlapCheck(matrix, recall, precision, probs, argmax, labels, talkers, n_windows.astype(np.int32))
+
+    def overlap_adapt(self, recordings, mic=None, passes=1, silence_remove=True, n_overlapped=256, n_single=256,
+                      epochs=20, batch=16, weighted=True, patience=10, seed=1, save_to=None, install=True):
+        """The remedy when ``overlap_check`` says the room's OD model does poorly for its speakers: fit it
+        further on their own voices (``overlap_detector.continue_train``: the reference's
+        ``continue_train_model`` on the device).  ``recordings`` is one int16 recording per speaker, conditioned
+        as ``overlap_check`` conditions it.  Each speaker's first 80 % of whole 24000-sample windows go to the
+        training pool and the rest to the validation pool, so validation mixes are made of audio the fit never
+        saw.  ``data_augmentation.overlap_plan`` (one random.Random(seed)) draws n_overlapped + n_single
+        training mixes, then a quarter as many (at least one each) validation mixes; ``od_mix`` mixes them and
+        the project's front end makes the feature images.  The validation mixes are scored with the current
+        model (`before`), the fit runs `epochs` epochs at most (Adadelta, the cosine schedule, class weights
+        when `weighted`, early stopping with `patience`), and they are scored again (`after`).  ``install``
+        loads the new weights into the room in place; ``save_to`` writes them (``tfbundle.save_overlap``).
+        -> OverlapAdapt(before, after: (confusion [2,2], recall, precision); history [epochs, 5];
+        epochs_run; n_windows [K]).  A speaker without a window in either pool raises ValueError naming the
+        speaker; the room (detectors, converters, both models) is unchanged when anything raises, and with
+        ``install=False``."""
+        import os
+        import random
+
+        from . import _lib, overlap_detector, tfbundle
+        from .data_augmentation import confusion, overlap_plan
+        K = len(recordings)
+        if K < 2:
+            raise ValueError(f'{K} recordings: an overlap adaptation needs at least two speakers')
+        if passes < 0 or n_overlapped < 1 or n_single < 1 or epochs < 0 or batch < 1 or patience < 0:
+            raise ValueError('passes, epochs and patience must be >= 0; n_overlapped, n_single and batch >= 1')
+        recs, (_, _, kept_len, pcm) = self._enrol(recordings, mic, passes, silence_remove, True)
+        n_windows = np.asarray(kept_len, np.int64) // _lib.OD_CLIP
+        n_tr = n_windows * 4 // 5
+        for k in range(K):
+            if n_tr[k] < 1 or n_windows[k] - n_tr[k] < 1:
+                raise ValueError(f'speaker {k}: {int(n_windows[k])} whole windows of {_lib.OD_CLIP} samples left '
+                                 f'after conditioning ({len(recs[k])} samples recorded, {int(kept_len[k])} kept); '
+                                 'the training and the validation pool each need one')
+        clip = _lib.OD_CLIP
+        pool_tr = np.concatenate([pcm[k, :n_tr[k] * clip] for k in range(K)])
+        pool_va = np.concatenate([pcm[k, n_tr[k] * clip:n_windows[k] * clip] for k in range(K)])
+        rng = random.Random(seed)
+        plan_tr, labels_tr, _ = overlap_plan(n_tr * clip, range(K), n_overlapped, n_single, rng)
+        plan_va, labels_va, _ = overlap_plan((n_windows - n_tr) * clip, range(K), max(n_overlapped // 4, 1),
+                                             max(n_single // 4, 1), rng)
+
+        def images(pool, plan):
+            clips, lens = self.ctx.od_mix(pool, plan)
+            return self.ctx.od_features(clips, lens=lens, db=False, norm=False, zcr=False)['img']
+
+        img_tr, img_va = images(pool_tr, plan_tr), images(pool_va, plan_va)
+
+        def score():
+            return confusion(labels_va, self.od.predict(img_va).argmax(axis=1))
+
+        before = score()
+        plan = overlap_detector.fit_plan(labels_tr, seed, epochs, val_ratio=0)
+        n = len(labels_tr)
+        plan['train'], plan['val'] = np.arange(n), n + np.arange(len(labels_va))
+        old = self.od.W
+        W, history, epochs_run = overlap_detector.continue_train(
+            old, np.concatenate([img_tr, img_va]), np.concatenate([labels_tr, labels_va]), plan, epochs, batch,
+            weighted=weighted, patience=patience, device=self.ctx)
+        try:
+            self.od.set_weights(W)
+            after = score()
+            if save_to is not None:
+                os.makedirs(save_to, exist_ok=True)
+                tfbundle.save_overlap(save_to, W)
+        except BaseException:
+            self.od.set_weights(old)
+            raise
+        if not install:
+            self.od.set_weights(old)
+        return OverlapAdapt(before, after, history, epochs_run, n_windows.astype(np.int32))
 
     @staticmethod
     def labels(result, speaker_id_dict):

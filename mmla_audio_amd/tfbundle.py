@@ -284,6 +284,27 @@ def save_deployed(model_dir, W, n_classes):
                'layer_with_weights-1/bias': W[head + '/bias']}
     for i, (name, _, _) in enumerate(items[:-2]):
         tensors[f'variables/{i}'] = W[name]
+    _write_bundle(model_dir, tensors)
+
+
+def save_overlap(model_dir, W):
+    """Write OD-NET -- what ``continue_train_model`` leaves behind -- as a variable bundle under
+    ``<model_dir>/variables/`` in the base-model layout ``layout`` documents for ``timit2.0``: every conv, BN
+    and Dense variable under its own ``layer_with_weights-k``, the Bidirectional LSTM's six tensors as
+    ``variables/i`` by their index in ``weights.od_spec`` order (116..121).  W: {canonical name: array}.
+    ``load_bundle`` / ``models.load_model`` return every tensor bit for bit.  As with ``save_deployed`` only
+    the variables are written, and parity of the key layout with a real TF save is unpinned."""
+    from . import weights
+    weights.check(weights.OD, W)
+    tensors = {}
+    for i, (name, _, role) in enumerate(weights.od_spec()):
+        tensors[f'variables/{i}' if role.startswith('lstm_') else name] = W[name]
+    _write_bundle(model_dir, tensors)
+
+
+def _write_bundle(model_dir, tensors):
+    """{bundle key: array} -> variables.index + variables.data-00000-of-00001: float32 at 8-byte-aligned
+    offsets, each with its masked CRC-32C"""
     data = bytearray()
     entries = []
     for key in sorted(tensors):
