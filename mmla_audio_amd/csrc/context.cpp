@@ -201,6 +201,7 @@ static const EnvSwitch kEnvSwitches[] = {
     {"MMLA_VADW", nullptr, &mmla_ctx::vadw_all},
     {"MMLA_RB_TILE", &mmla_ctx::rbs, nullptr},   // 1 selects the tiles: the strips off
     {"MMLA_NO_RBS_W1L", &mmla_ctx::rbs_w1l, nullptr},
+    {"MMLA_NO_RBS_TAILPAIR", &mmla_ctx::rbs_tailpair, nullptr},
     {"MMLA_NO_PIN_OUT", &mmla_ctx::pin_small, nullptr},   // takes effect where create makes the pinned buffers
 };
 

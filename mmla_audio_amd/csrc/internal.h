@@ -161,6 +161,9 @@ struct mmla_ctx {
   // MMLA_NO_RBS_W1L=1 at create: rbs.hip's kernel, which streams them from global memory every chunk
   // (A/B, bit-identical)
   bool rbs_w1l = true;
+  // ... block 1 with the 7-column last strips of two consecutive clips in one workgroup (rbs_tp.hip); env
+  // MMLA_NO_RBS_TAILPAIR=1 at create: rbs.hip's kernel, one workgroup per clip for them (A/B, bit-identical)
+  bool rbs_tailpair = true;
   // batches of <= lstm_split_max clips: the 3xFP16 BiLSTM with each direction's hidden units on eight workgroups
   // (nets.hip bilstm_h3_split_kernel); env MMLA_NO_LSTM_SPLIT=1 at create: one workgroup per direction
   bool lstm_split = true;

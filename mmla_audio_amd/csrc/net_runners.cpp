@@ -164,6 +164,8 @@ struct OdChoice {
   int strips;
   // OD_STRIPS only: blocks 2-3 with the 3x3 conv's weights in LDS (rbs_w1l.hip)
   bool w1_lds;
+  // OD_STRIPS only: block 1 with the clips' ragged last strips paired (rbs_tp.hip)
+  bool tail_pair;
 };
 
 bool strips_ok(const ResUnitW& B, bool pool, int h, int w) {
@@ -188,11 +190,12 @@ bool odu_ok(const ResUnitW& B, bool pool, int h, int w) {
 
 // stop: the debug trace's last stage (-1: none); a trace of the stem alone (0) needs it in HBM
 OdChoice od_choose(const mmla_ctx* c, const ResUnitW& B, int b, int h, int w, int stop) {
-  OdChoice k{OD_PAIR, false, 1, false};
+  OdChoice k{OD_PAIR, false, 1, false, false};
   if (c->precision != MMLA_PREC_F16X3) return k;
   if (c->rbs && strips_ok(B, POOL[b], h, w)) {
     k.path = OD_STRIPS;
     k.w1_lds = c->rbs_w1l && !POOL[b];
+    k.tail_pair = c->rbs_tailpair && POOL[b];
   } else if (tiles_ok(B, POOL[b])) {
     k.path = OD_TILES;
   } else if (c->odu && odu_ok(B, POOL[b], h, w)) {
@@ -352,7 +355,7 @@ int run_od_net(mmla_ctx* c, const uint8_t* img_u8, const float* img_f32, int64_t
                                          k.stem ? &W.stem : nullptr, img_u8, img_f32);
         LAUNCH(c, MMLA_STAGE_CONV, flops,
                tiles ? resblk_launch(r, B.ca.cin, B.ca.cout, pool, c->stream)
-                     : rbs_launch(r, B.ca.cin, B.ca.cout, pool, k.w1_lds, c->stream));
+                     : rbs_launch(r, B.ca.cin, B.ca.cout, pool, k.w1_lds, k.tail_pair, c->stream));
         break;
       }
       case OD_ODU: {   // t1 stays in LDS, bit-identical to the pair

@@ -38,7 +38,8 @@
 //
 // The strip body is rbs_body.h.  This file holds the two kernels whose GEMM 1 streams its weights from
 // global memory every chunk: block 1, and blocks 2-3 as they run under MMLA_NO_RBS_W1L=1.  By default
-// blocks 2-3 run rbs_w1l.hip's kernel, which keeps GEMM 1's weights in LDS for the whole strip.
+// blocks 2-3 run rbs_w1l.hip's kernel, which keeps GEMM 1's weights in LDS for the whole strip, and block 1
+// runs rbs_tp.hip's, which pairs the clips' ragged tenth strips (MMLA_NO_RBS_TAILPAIR=1: this file's).
 #define RBS_KERNEL rbs_kernel
 #define RBS_W1L false
 #include "rbs_body.h"
@@ -66,13 +67,13 @@ bool rbs_supported(int h, int w, int cin, int c, bool pool) {
   return c == 32 && ((h == 128 && w == 151 && cin == 16 && pool) || (h == 64 && w == 76 && cin == 32 && !pool));
 }
 
-hipError_t rbs_launch(const ResBlkArgs& a, int cin, int c, bool pool, bool w1_lds, hipStream_t s) {
+hipError_t rbs_launch(const ResBlkArgs& a, int cin, int c, bool pool, bool w1_lds, bool tail_pair, hipStream_t s) {
   if (a.n == 0) return hipSuccess;
   if (!rbs_supported(a.h, a.w, cin, c, pool) || !a.y || !a.w1h || !a.w1l || !a.w2h || !a.w2l)
     return hipErrorInvalidValue;
   if (pool) {
     if (!a.wsh || !a.wsl || !a.bs) return hipErrorInvalidValue;
-    if (a.img8 || a.imgf) return launch<128, 151, 16, true, true>(a, s);
+    if (a.img8 || a.imgf) return tail_pair ? rbs_tp_launch(a, s) : launch<128, 151, 16, true, true>(a, s);
     return hipErrorInvalidValue;   // block 1 runs with the stem fused
   }
   if (!a.x || a.x == a.y) return hipErrorInvalidValue;

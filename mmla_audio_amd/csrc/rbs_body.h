@@ -1,10 +1,17 @@
-// The strip kernel of OD-NET res_blocks 1-3 (rbs.hip documents the algorithm), instantiated by rbs.hip
-// and rbs_w1l.hip.  The including file defines, before the #include,
+// The strip kernel of OD-NET res_blocks 1-3 (rbs.hip documents the algorithm), instantiated by rbs.hip,
+// rbs_w1l.hip and rbs_tp.hip.  The including file defines, before the #include,
 //   RBS_KERNEL  the kernel template's name in that translation unit, and
 //   RBS_W1L     where GEMM 1 reads its split 3x3 weights: false: from global memory through a register
 //               ring, every chunk (rbs.hip: block 1, and blocks 2-3 under MMLA_NO_RBS_W1L=1); true: from
 //               an LDS copy the workgroup makes once per strip (rbs_w1l.hip).
-// The switch is a macro and not a template parameter so that rbs.hip's kernels keep their names and
+//   RBS_TAILPAIR  (optional, default false; block 1 only: rbs_tp.hip) true: the grid is 9 n + ceil(n / 2)
+//               workgroups instead of 10 n: the ragged tenth strips (7 of 16 columns in the image) of clips
+//               2p and 2p + 1 share one workgroup, each in its own half of the halo ring and of the tile.
+//               Only the column tables computed before the chunk loop differ (rbs_tp.hip has the map).
+//   RBS_SC_DEDUP  (optional, default false; with RBS_TAILPAIR: rbs_tp.hip turns it on) true: the
+//               shortcut's stem is computed once per pool window, two channels per lane of a quad, and
+//               assembled by DPP broadcasts.
+// The switches are macros and not template parameters so that rbs.hip's kernels keep their names and
 // compile to the code they had as the only user of this body (a wrapper kernel around an inlined device
 // function compiled to a different schedule and seven more VGPRs for blocks 2-3).
 #pragma once
@@ -12,6 +19,12 @@
 #include "resblk.h"
 #if !defined(RBS_KERNEL) || !defined(RBS_W1L)
 #error "define RBS_KERNEL and RBS_W1L before including rbs_body.h"
+#endif
+#ifndef RBS_TAILPAIR
+#define RBS_TAILPAIR false
+#endif
+#ifndef RBS_SC_DEDUP
+#define RBS_SC_DEDUP false
 #endif
 
 namespace {
@@ -109,8 +122,23 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) RBS_KERNEL(Re
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 5;                       // lane half: k group / channel group
   const uint32_t bid = xcd_block_id();
-  const int clip = (int)(bid / G::STRIPS);
-  const int w0 = (int)(bid - (uint32_t)clip * G::STRIPS) * TW;
+  constexpr bool TP = RBS_TAILPAIR, SCD = RBS_SC_DEDUP;
+  static_assert(!TP || (STEM && W % TW == TW / 2 - 1), "paired tails: block 1, two 7-column tails in one strip");
+  static_assert(!SCD || TP, "the de-duplicated shortcut stem belongs to the paired-tails kernel");
+  // TP: workgroups 0 .. FS n - 1 are the full strips (clip bid / FS, strip bid % FS); workgroup FS n + p is
+  // the tails of clips 2p (part 0: ring columns 0-8, tile columns 0-7) and 2p + 1 (part 1: ring columns
+  // 9-17, tile columns 8-15; absent, has_b false, when n is odd and p the last pair).  All wave-uniform.
+  constexpr int FS = TP ? G::STRIPS - 1 : G::STRIPS;
+  const bool pair = TP && bid >= (uint32_t)a.n * FS;
+  const int clip = pair ? 2 * (int)(bid - (uint32_t)a.n * FS) : (int)(bid / FS);
+  const int w0 = pair ? FS * TW : (int)(bid - (uint32_t)clip * FS) * TW;
+  const bool has_b = pair && clip + 1 < a.n;
+  // ring column x (0 .. 17) -> its part and image column; false: outside the image (or of the absent clip)
+  auto ring_col = [&](int x, int& part, int& iw) -> bool {
+    part = TP && pair && x >= G::XW / 2;
+    iw = w0 - 1 + x - (TP ? part * (G::XW / 2) : 0);
+    return iw >= 0 && iw < W && (!TP || !part || has_b);
+  };
   const int lofs = lane * 8;
   float rmax = 0.0f;   // 3xFP16 range guard: the largest |operand| this thread split (ResBlkArgs::range_flag)
 
@@ -192,31 +220,38 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) RBS_KERNEL(Re
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x) + (int64_t)clip * H * W * CIN, (short)0,
                                         (int)(H * ROWB), 0x00020000);
   // block 1: the clip's image (u8 or float NHWC) through a buffer descriptor as well
+  // (TP: a pair's two clips are contiguous and share one descriptor; part 1's pixels start H W pixels
+  // in.  Rows -1 and >= H of a part are then no longer out of range, so whoever loads them masks by row:
+  // load_src by its own test, the last chunk's staging by r0 + rr < H)
   const bool im8 = STEM && a.img8 != nullptr;
   const __amdgpu_buffer_rsrc_t rimg = !STEM ? w_rsrc(nullptr) :
       __builtin_amdgcn_make_buffer_rsrc(im8 ? (void*)(a.img8 + (int64_t)clip * H * W * 3)
                                             : (void*)(a.imgf + (int64_t)clip * H * W * 3),
-                                        (short)0, (int)(H * W * 3 * (im8 ? 1 : 4)), 0x00020000);
+                                        (short)0, TP ? __builtin_amdgcn_readfirstlane((int)(H * W * 3 * (im8 ? 1 : 4)) * (has_b ? 2 : 1))
+                                                     : (int)(H * W * 3 * (im8 ? 1 : 4)), 0x00020000);
   // per task: LDS column offset (bits 0-9), tile row (10-13), column inside the image (14), task exists
   // (15), its source byte offset within a row (16-31)
+  // (TP: the source offset, which then includes part 1's clip, has a register of its own: tsrc)
   uint32_t tinfo[G::MAXT];
+  uint32_t tsrc[TP ? G::MAXT : 1];
 #pragma unroll
   for (int j = 0; j < G::MAXT; ++j) {
     const int t = tid + j * NT;
     const int px = t / G::QPP;
     const int rr = px / G::XW, x = px - rr * G::XW;
-    const int iw = w0 - 1 + x;
-    const bool col_ok = iw >= 0 && iw < W;
+    int part, iw;
+    const bool col_ok = ring_col(x, part, iw);
     const uint32_t tc = !col_ok ? 0u : STEM ? (uint32_t)iw * (a.img8 ? 3u : 12u) : (uint32_t)(iw * CIN + 4 * q) * 4u;
+    if constexpr (TP) tsrc[j] = tc + (uint32_t)(part * H * W) * (a.img8 ? 3u : 12u);
     tinfo[j] = (uint32_t)(xoff<CIN>(0, x, q >> 1) + 4 * (q & 1)) | ((uint32_t)(rr & 15) << 10) |
-               ((uint32_t)col_ok << 14) | ((uint32_t)(rr < R) << 15) | (tc << 16);
+               ((uint32_t)col_ok << 14) | ((uint32_t)(rr < R) << 15) | ((TP ? 0u : tc) << 16);
   }
   // the image pixel {r, g, b, 1} (1: inside the image), or x channels 4q .. 4q+3
   // (no branch around a load: a load inside a divergent branch is waited for inside it; the raw image
   // bytes are converted where they are used)
-  auto load_src = [&](int ih, int iw, bool col_ok) -> float4 {
+  auto load_src = [&](int ih, int iw, bool col_ok, int part = 0) -> float4 {
     if constexpr (STEM) {
-      const int pix = ih * W + iw;
+      const int pix = TP ? (part * H + ih) * W + iw : ih * W + iw;
       const bool ok = col_ok && ih >= 0 && ih < H;
       if (im8) {
         const uint32_t off = ok ? (uint32_t)pix * 3u : 0x80000000u;
@@ -245,7 +280,8 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) RBS_KERNEL(Re
   // row offset is out of range, as in load_src)
   auto load_task = [&](int r0, int j) -> float4 {
     const uint32_t ti = tinfo[j];
-    const uint32_t off = (ti >> 14) & 1u ? (uint32_t)((r0 + (int)((ti >> 10) & 15)) * (STEM ? W * 3 * (im8 ? 1 : 4) : (int)ROWB)) + (ti >> 16)
+    const uint32_t off = (ti >> 14) & 1u ? (uint32_t)((r0 + (int)((ti >> 10) & 15)) * (STEM ? W * 3 * (im8 ? 1 : 4) : (int)ROWB)) +
+                                               (TP ? tsrc[TP ? j : 0] : ti >> 16)
                                          : 0x80000000u;
     if constexpr (STEM) {
       if (im8) {
@@ -299,23 +335,33 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) RBS_KERNEL(Re
     stage4((int)slot * G::XROW + (int)(ti & 1023), r0 + rr < H, v, MASK_);
   };
   // the ring's columns outside the image (strip 0: image column -1; the last strip: columns >= W),
-  // zeroed once in every slot and both planes: no task writes them
+  // zeroed once in every slot and both planes: no task writes them (TP, a pair: ring columns 8 and 17,
+  // image column W of either part, and all of an absent part 1)
   for (int e = tid; e < 2 * G::XRING * G::XW * G::QPP; e += NT) {
     const int pl = e / (G::XRING * G::XW * G::QPP), r = e - pl * (G::XRING * G::XW * G::QPP);
     const int slot = r / (G::XW * G::QPP), x = (r / G::QPP) % G::XW, qq = r % G::QPP;
-    const int iw = w0 - 1 + x;
-    if (iw < 0 || iw >= W)
+    int part, iw;
+    if (!ring_col(x, part, iw))
       *reinterpret_cast<f16x4*>(sx + pl * G::XPLANE + xoff<CIN>(slot, x, qq >> 1) + 4 * (qq & 1)) = f16x4{};
   }
   // ---- GEMM 1 for t1 rows j0, j0 + 1 (one 32-pixel tile, natural order: pixel n = lane & 31 is row
   //      j0 + (n >> 4), column n & 15) as t1^T: acc[4 jj + i] = channel 8 jj + 4 h + i of pixel n ----
   const int n = lane & 31, nr = n >> 4, nc = n & 15;
-  // this lane's x column offsets for dx = 0..2 and its k groups (ks)
+  // this lane's x column offsets for dx = 0..2 and its k groups (ks): ring column nc + dx.  TP, a pair:
+  // part 1's tile columns 8-14 read ring columns nc + 1 + dx (its ring half starts at 9, its tile half
+  // at the even column 8 so that its pool windows stay aligned), and the junk tile columns 7 and 15 read
+  // the zero ring column of their own part (8, 17) for every dx, so that no lane of one part reads a
+  // ring column of the other and a junk column's t1 is what a column outside the image gives
+  auto tile_ring = [&](int c, int dx) -> int {
+    if (!(TP && pair)) return c + dx;
+    const int p = c >= TW / 2, cl = c - p * (TW / 2);
+    return p * (G::XW / 2) + (cl == TW / 2 - 1 ? G::XW / 2 - 1 : cl + dx);
+  };
   int xco[3][G::KPT];
 #pragma unroll
   for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-    for (int ks = 0; ks < G::KPT; ++ks) xco[dx][ks] = xoff<CIN>(0, nc + dx, G::KPT == 2 ? 2 * ks + h : h);
+    for (int ks = 0; ks < G::KPT; ++ks) xco[dx][ks] = xoff<CIN>(0, tile_ring(nc, dx), G::KPT == 2 ? 2 * ks + h : h);
 
   // GEMM 1's weight ring (PF k-steps ahead), first steps issued early; W1L: no loads, the fragments
   // come from sw1 one k-step ahead like the x fragments
@@ -423,9 +469,10 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) RBS_KERNEL(Re
       const int t = tid + j * NT;
       const int px = t / G::QPP;
       const int rr = px / G::XW, x = px - rr * G::XW;
-      const int ih = rr - 1, iw = w0 - 1 + x;
-      const bool col_ok = iw >= 0 && iw < W;
-      const float4 v = load_src(ih, iw, col_ok);
+      const int ih = rr - 1;
+      int part, iw;
+      const bool col_ok = ring_col(x, part, iw);
+      const float4 v = load_src(ih, iw, col_ok, part);
       if (t < T0 && col_ok)
         stage4(xoff<CIN>((ih + 1) % G::XRING, x, q >> 1) + 4 * (q & 1), ih >= 0, v, std::true_type{});
     }
@@ -451,8 +498,15 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) RBS_KERNEL(Re
   __syncthreads();   // wave 0 is done with x rows -1, 0 (the first chunk overwrites their slots)
 
   // block 1's shortcut pixel of a chunk: this lane's pool window's top-left, conv row 8 k + 2 wave
+  // (TP, a pair: windows 4-7 are part 1's, at the same image columns as windows 0-3; sc_ok: inside the
+  // image, and of a clip that exists)
   const int win = n >> 2;
-  const int sc_col = w0 + 2 * win;
+  const int sc_part = TP && pair && win >= 4;
+  const int sc_col = w0 + 2 * (win - 4 * sc_part);
+  const bool sc_ok_tp = sc_col < W && (!sc_part || has_b);
+  auto sc_ok = [&]() -> bool {
+    if constexpr (TP) return sc_ok_tp; else return sc_col < W;
+  };
   // its shortcut bias, read once: a global load inside the chunk loop would queue behind the next
   // chunk's image prefetch (vector loads complete in issue order)
   float bsc = 0.0f;
@@ -497,7 +551,7 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) RBS_KERNEL(Re
       for (int jj = 0; jj < 4; ++jj)
         rsd[jj] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, off, jj * 32, 0));
     } else {
-      scpx = load_src(o0, sc_col, sc_col < W);
+      scpx = load_src(o0, sc_col, sc_ok(), sc_part);
     }
     if (k + G::PD < G::NCHUNK) {
 #pragma unroll
@@ -583,7 +637,41 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) RBS_KERNEL(Re
       f32x16 sacc;
 #pragma unroll
       for (int i = 0; i < 16; ++i) sacc[i] = 0.0f;
-      {
+      if constexpr (SCD) {
+        // lanes n, n ^ 1, n ^ 2, n ^ 3 are one window (A row m = window m >> 2): lane n computes stem
+        // channels 8 h + 2 j, + 1 (j = n & 3) with the expressions below, splits the pair (split4's
+        // operations) and the quad's four lanes exchange their packed pairs by DPP quad broadcasts.  The
+        // same operand bits; the wave folds the same set of values into the range maximum
+        const float4 px = img_px(scpx);
+        const int j = n & 3;
+        float o2[2];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          const float4 wv = spar[3 * C / 4 + 8 * h + 2 * j + c];
+          float s = px.x * wv.x;
+          s = fmaf(px.y, wv.y, s);
+          s = fmaf(px.z, wv.z, s);
+          o2[c] = sc_ok() ? 16.0f * (s + wv.w) : 0.0f;
+        }
+        rmax = fmaxf(rmax, fmaxf(fabsf(o2[0]), fabsf(o2[1])));
+        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+        const f16x2 hp = {(_Float16)o2[0], (_Float16)o2[1]};
+        const uint32_t hu = __builtin_bit_cast(uint32_t, hp);
+        const uint32_t lu = split_lo2(o2[0], o2[1], hu);
+        uint4 au, bu;
+        au.x = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hu, 0x00, 0xf, 0xf, false);   // quad_perm:[0,0,0,0]
+        au.y = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hu, 0x55, 0xf, 0xf, false);   // [1,1,1,1]
+        au.z = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hu, 0xaa, 0xf, 0xf, false);   // [2,2,2,2]
+        au.w = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hu, 0xff, 0xf, 0xf, false);   // [3,3,3,3]
+        bu.x = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lu, 0x00, 0xf, 0xf, false);
+        bu.y = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lu, 0x55, 0xf, 0xf, false);
+        bu.z = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lu, 0xaa, 0xf, 0xf, false);
+        bu.w = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lu, 0xff, 0xf, 0xf, false);
+        const f16x8 ah = __builtin_bit_cast(f16x8, au), al = __builtin_bit_cast(f16x8, bu);
+        sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wsl_, sacc, 0, 0, 0);
+        sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wsh_, sacc, 0, 0, 0);
+        sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wsh_, sacc, 0, 0, 0);
+      } else {
         float o8[8];
         const float4 px = img_px(scpx);
 #pragma unroll
@@ -592,7 +680,7 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) RBS_KERNEL(Re
           float s = px.x * wv.x;
           s = fmaf(px.y, wv.y, s);
           s = fmaf(px.z, wv.z, s);
-          o8[c] = sc_col < W ? 16.0f * (s + wv.w) : 0.0f;
+          o8[c] = sc_ok() ? 16.0f * (s + wv.w) : 0.0f;
         }
         rmax = fmaxf(rmax, fmaxf(amax4(o8[0], o8[1], o8[2], o8[3]), amax4(o8[4], o8[5], o8[6], o8[7])));
         f16x4 h0, l0, h1, l1;
@@ -611,8 +699,10 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) RBS_KERNEL(Re
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {
         const int wdw = 2 * jj + h;                  // window: conv columns w0 + 2 wdw, + 1
-        const int cc = w0 + 2 * wdw;
-        if (cc >= W) continue;
+        // TP, a pair: windows 4-7 (jj >= 2) are part 1's windows 0-3: the next clip, the same columns
+        const int op = TP && pair && jj >= 2;
+        const int cc = w0 + 2 * (wdw - 4 * op);
+        if (cc >= W || (TP && op && !has_b)) continue;
         float m0 = fmaf(acc[4 * jj + 0], a.u2, b2);  // (row 0, col 0)
         float m1 = fmaf(acc[4 * jj + 1], a.u2, b2);  // (row 0, col 1)
         float m2 = fmaf(acc[4 * jj + 2], a.u2, b2);  // (row 1, col 0)
@@ -622,7 +712,7 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) RBS_KERNEL(Re
           m3 = m2;
         }
         const float mx = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)) + fmaf(sacc[4 * jj], a.us, bs);
-        a.y[(((int64_t)clip * HP + prow) * WP + (w0 >> 1) + wdw) * C + co] = mx;
+        a.y[(((int64_t)(clip + op) * HP + prow) * WP + (w0 >> 1) + wdw - 4 * op) * C + co] = mx;
       }
     }
     RBS_T(7);

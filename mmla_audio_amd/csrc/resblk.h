@@ -47,7 +47,12 @@ void resblk_split_weights(const float* w, int taps, int cin, int cout, int kpad,
 // shortcut); a.h / a.w are the block's input size.  Block 1 (pool) needs the stem fused (img8 / imgf).
 // w1_lds (blocks 2-3 only; ignored for block 1): the kernel of rbs_w1l.hip, which keeps the 3x3 conv's
 // weights in LDS for the whole strip.  Same arguments, same bits.
+// tail_pair (block 1 only; ignored for blocks 2-3): the kernel of rbs_tp.hip, in which the 7-column last
+// strips of two consecutive clips share a workgroup.  Same arguments, same bits.
 bool rbs_supported(int h, int w, int cin, int c, bool pool);
-hipError_t rbs_launch(const ResBlkArgs& a, int cin, int c, bool pool, bool w1_lds, hipStream_t stream);
-// rbs_launch's callee for w1_lds (rbs_w1l.hip): blocks 2-3, arguments already checked
+hipError_t rbs_launch(const ResBlkArgs& a, int cin, int c, bool pool, bool w1_lds, bool tail_pair,
+                      hipStream_t stream);
+// rbs_launch's callees for w1_lds (rbs_w1l.hip: blocks 2-3) and tail_pair (rbs_tp.hip: block 1 with the
+// stem fused), arguments already checked
 hipError_t rbs_w1l_launch(const ResBlkArgs& a, hipStream_t stream);
+hipError_t rbs_tp_launch(const ResBlkArgs& a, hipStream_t stream);
