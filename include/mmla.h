@@ -313,6 +313,84 @@ int mmla_si_finetune(mmla_ctx* ctx, const float* packed, int64_t n_floats, int32
                      const int32_t* perm, float* packed_out, float* history, uint32_t flags);
 
 /*
+ * Training the SI base model from scratch: the reference's train(x_train, y_train, x_validate, y_validate)
+ * (speaker_identification.py:221-250, driven by the __main__ at :506-555) on res_model's graph (:115-219).
+ * Float32 HIP: si_bwd.hip's convolutions, pools, BiLSTM, L2 terms and RMSprop, and si_base.hip for what
+ * separates training from fine-tuning.  Stated from the script and Keras 2.6's published source;
+ * TensorFlow is not available here: parity with TF itself is unpinned, in particular for the three
+ * statements marked (*).
+ *   graph     as mmla_si_finetune above, with Dropout(0.25) on the [32, 128] map in front of
+ *             AveragePooling1D(4), Dropout(0.2) on the 512-wide BiLSTM output, and a softmax head
+ *             Dense(512 -> K), K <= MMLA_SI_BASE_MAX_CLASSES.
+ *   training  Keras runs the network with training=True.  BatchNorm: per channel over the B T positions,
+ *             the mean, then the biased variance of the centred values (two passes), eps 1e-3; after every
+ *             step moving <- 0.99 moving + 0.01 batch, with that same BIASED variance (*): a rank-3
+ *             input takes Keras's non-fused path (nn.moments, then _assign_moving_average of the variance
+ *             it normalised with), unlike OD-NET's rank-4 inputs below.  Validation passes run in inference
+ *             mode: moving statistics, no dropout.
+ *   dropout   no mask is passed in.  Keep-bits are words of Philox4x32-10 with key = (low, high half of
+ *             drop_seed's 64 bits; any int64_t value is a seed), counter = (element / 4, sample id, epoch, site), word = element % 4; site 0 is
+ *             the [32, 128] map (element = 128 t + channel), site 1 the embedding.  The sample id is the
+ *             row of the training set (sample_ids[i], or i), not the slot in the batch.  An element is kept
+ *             iff its word >= 0x40000000 (site 0) or 0x33333333 (site 1), and kept values are scaled by
+ *             float32(1 / 0.75) and float32(1 / 0.8).  TensorFlow's own generator is not reproduced.
+ *   loss      of a batch of B windows: mean_b[logsumexp(z_b) - z_b[label]] + R, no clip (*): a Keras 2.6
+ *             softmax output carries _keras_logits and categorical_crossentropy takes the logits path.
+ *             dz = (softmax - onehot) / B.  R and its gradient as in mmla_si_finetune.  A hit is counted
+ *             when the first maximum of z is the label.
+ *   optimiser RMSprop as in mmla_si_finetune, every accumulator from 0; trainable is everything but
+ *             moving_mean / moving_variance, whose gradient slots are 0 and which only the update above moves.
+ *             Conv1D biases: every Conv1D output reaches the loss only through batch-statistics BNs, which
+ *             cancel a per-channel constant, so their gradient is identically zero.  Their slots are
+ *             reported as exactly 0 and they come out bit-equal; float32 Keras sums rounding noise there,
+ *             which RMSprop turns into steps of up to 3.16 lr.
+ *   callbacks EarlyStopping(val_loss, patience): the fit ends after the epoch in which val_loss has failed
+ *             `patience` times in a row to go below its best; no restore_best_weights.
+ *             ModelCheckpoint(val_categorical_accuracy, save_best_only, mode 'max', period): at every
+ *             ckpt_period-th epoch whose val_categorical_accuracy is strictly above the best saved so far,
+ *             the weights are copied on the device to best_out and best_epoch (0-based) is set.  Each is
+ *             off when its argument is 0 or n_val == 0; while either is on, one history row is read back
+ *             per epoch, otherwise a fit has no host synchronisation.
+ *   history   [epochs, 4] = loss, categorical_accuracy (training mode, each batch with the weights before
+ *             its update, sample-weighted), val_loss, val_categorical_accuracy (NaN when n_val == 0); rows
+ *             after an early stop are NaN.
+ * (*) the third: the initial state (weights.initial in the Python package) draws with numpy, not with
+ * TensorFlow's generator.
+ * Every sum has a fixed order and nothing is accumulated with atomics: the same inputs give the same bits.
+ * Both training entries work on a copy of `packed` (weights.si_spec(n_classes) order) in the fine-tune's
+ * workspace slot and do not touch the context's loaded model.  Host or device pointers (flags), epochs_run
+ * and best_epoch included.
+ *
+ * mmla_si_base_drop_mask: the keep-bits of n samples as bytes, mask_a [n, 32, 128], mask_b [n, 512];
+ *   sample_ids [n] nullable (= 0..n-1); n in [1, 2^20].
+ * mmla_si_base_loss_grad: ONE training-mode batch, n in [1, 4096] -> loss[0] the data term, loss[1] R,
+ *   grad [n_floats], moving_out [n_floats] (nullable): the blob with only the moving statistics advanced
+ *   one step.
+ * mmla_si_base_train: perm [epochs, n_train] -> packed_out [n_floats] the final state (may be `packed`),
+ *   best_out [n_floats] (needed when ckpt_period > 0 and n_val > 0; written only when best_epoch >= 0),
+ *   history [epochs, 4], epochs_run [1], best_epoch [1] (-1 if none).  epochs == 0 returns the input blob.
+ * MMLA_E_INVALID, before any device work: n_classes outside [1, MMLA_SI_BASE_MAX_CLASSES], n_floats that is
+ * not the blob's size for that head, batch < 1, n_train < 1 (n outside its range), n_val < 0, epochs < 0,
+ * epoch < 0, patience < 0, ckpt_period < 0, lr negative or not finite, a null pointer, and in host-pointer
+ * calls a label outside [0, K), a perm row that is not a permutation or a sample id < 0 (device pointers: a
+ * perm entry is clamped into the set, a label is clamped into [0, K), a sample id is only a counter word,
+ * so a broken contract gives a wrong fit, not an access outside a buffer).
+ */
+#define MMLA_SI_BASE_MAX_CLASSES 1024
+int mmla_si_base_drop_mask(mmla_ctx* ctx, int64_t drop_seed, int32_t epoch, const int32_t* sample_ids,
+                           int64_t n, uint8_t* mask_a, uint8_t* mask_b, uint32_t flags);
+int mmla_si_base_loss_grad(mmla_ctx* ctx, const float* packed, int64_t n_floats, int32_t n_classes,
+                           const float* x, const int32_t* labels, int64_t n, int64_t drop_seed,
+                           int32_t epoch, const int32_t* sample_ids, float* loss, float* grad,
+                           float* moving_out, uint32_t flags);
+int mmla_si_base_train(mmla_ctx* ctx, const float* packed, int64_t n_floats, int32_t n_classes,
+                       const float* x, const int32_t* labels, int64_t n_train, const float* val_x,
+                       const int32_t* val_labels, int64_t n_val, int32_t epochs, int32_t batch, float lr,
+                       const int32_t* perm, int64_t drop_seed, int32_t patience, int32_t ckpt_period,
+                       float* packed_out, float* best_out, float* history, int32_t* epochs_run,
+                       int32_t* best_epoch, uint32_t flags);
+
+/*
  * Adapting OD-NET to a room: OverlapDetector.continue_train_model (overlap_detector.py:480-509), the
  * trained detector fitted further on labelled feature images.  Float32 HIP (od_bwd.hip, with conv.hip's
  * exact-f32 MFMA convolution and si_bwd.hip's BiLSTM), stated from the script and Keras 2.6's published

@@ -7,7 +7,8 @@ here with ctypes under the reference's own names:
   overlap_features_generator.OverlapFeaturesGenerator   (reference overlap_features_generator.py)
   speaker_identification.input_feature_gen / delta /
       make_feature_experiment / transfer_learning /
-      transfer_learning_on_experiment                   (reference speaker_identification.py)
+      transfer_learning_on_experiment / res_model /
+      train / make_feature_timit                        (reference speaker_identification.py)
   overlap_detector.continue_train / cosine_lr /
       cal_weighted_penalty                              (reference overlap_detector.py, cosine_annealing.py)
   models.load_model(path).predict(x) / .predict_wavs    (tf.keras.models.load_model)

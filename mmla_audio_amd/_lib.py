@@ -26,6 +26,7 @@ PREC_F32, PREC_F16X3 = 0, 1
 OD_MELS, OD_FRAMES, OD_CLIP = 128, 151, 24000
 SI_FRAMES, SI_DIMS, SI_SILENT_LEN = 256, 39, 4000
 SI_EMBED, SI_TRAIN_MAX_CLASSES = 512, 32
+SI_BASE_MAX_CLASSES = 1024
 OD_TRAIN_MAX_BATCH, OD_DROP_UNITS = 64, 512
 ENROL_MAX_SAMPLES = 1966080
 MIX_MAX_LAYERS = 8
@@ -103,6 +104,14 @@ SIGNATURES = {
     'mmla_si_loss_grad': [_P, _P, _I64, _I32, _P, _P, _I64, _P, _P, _U32],
     'mmla_si_finetune': [_P, _P, _I64, _I32, _P, _P, _I64, _P, _P, _I64, _I32, _I32, ctypes.c_float,
                          _P, _P, _P, _U32],
+    # ctx, drop_seed, epoch, sample_ids, n, mask_a, mask_b
+    'mmla_si_base_drop_mask': [_P, _I64, _I32, _P, _I64, _P, _P, _U32],
+    # ctx, packed, n_floats, n_classes, x, labels, n, drop_seed, epoch, sample_ids, loss, grad, moving_out
+    'mmla_si_base_loss_grad': [_P, _P, _I64, _I32, _P, _P, _I64, _I64, _I32, _P, _P, _P, _P, _U32],
+    # ctx, packed, n_floats, n_classes, x, labels, n_train, val_x, val_labels, n_val, epochs, batch, lr, perm,
+    # drop_seed, patience, ckpt_period, packed_out, best_out, history, epochs_run, best_epoch
+    'mmla_si_base_train': [_P, _P, _I64, _I32, _P, _P, _I64, _P, _P, _I64, _I32, _I32, ctypes.c_float, _P, _I64,
+                           _I32, _I32, _P, _P, _P, _P, _P, _U32],
     # ctx, packed, n_floats, img_u8, labels, n, h, w, class_w, drop_mask, loss, grad, moving_out
     'mmla_od_loss_grad': [_P, _P, _I64, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _U32],
     # ctx, packed, n_floats, img_u8, labels, n_train, val_img, val_labels, n_val, h, w, class_w, epochs, batch,
@@ -223,6 +232,12 @@ class MixPlan(namedtuple('MixPlan', 'n_layers src_off src_len pos')):
             if a.shape != (nl.size, MIX_MAX_LAYERS):
                 raise ValueError(f'{name} {a.shape}: expected [{nl.size}, {MIX_MAX_LAYERS}]')
         return nl, off, ln, pos
+
+
+def _seed64(seed):
+    """any Python integer's low 64 bits as the int64_t the ABI takes for a seed"""
+    v = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >> 63 else v
 
 
 def _ptr(a):
@@ -762,6 +777,73 @@ class Context:
             _ptr(hist) if epochs else None, 0), 'mmla_si_finetune')
         return out, hist
 
+    def si_base_drop_mask(self, drop_seed, epoch, sample_ids, n=None):
+        """The dropout keep-bits of a base-model fit as bytes (mmla_si_base_drop_mask): sample_ids [n]
+        (None: 0..n-1) -> (mask_a uint8 [n,32,128] in front of the avg-pool, mask_b uint8 [n,512] on the
+        embedding); 1 = kept."""
+        ids = None
+        if sample_ids is not None:
+            ids = np.ascontiguousarray(sample_ids, dtype=np.int32).ravel()
+            n = ids.size
+        n = int(n)
+        mask_a = np.empty((max(n, 0), 32, 128), np.uint8)
+        mask_b = np.empty((max(n, 0), 512), np.uint8)
+        self._check(self.lib.mmla_si_base_drop_mask(self.h, _seed64(drop_seed), int(epoch), _ptr(ids), n,
+                                                    _ptr(mask_a), _ptr(mask_b), 0), 'mmla_si_base_drop_mask')
+        return mask_a, mask_b
+
+    def si_base_loss_grad(self, packed, n_classes, x, labels, drop_seed=0, epoch=0, sample_ids=None,
+                          moving=False):
+        """The training-mode loss of ONE batch of SI base-model training and its gradient
+        (mmla_si_base_loss_grad): BatchNorm on batch statistics, both dropouts (keep-bits of drop_seed,
+        epoch, sample_ids), the softmax head's loss on the logits.  -> (loss float32 [2] = data term, L2
+        penalty; grad float32 [n_floats], 0 in the moving statistics) and, with moving=True, the blob with
+        only its moving statistics advanced one step."""
+        packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
+        x, labels = self._si_windows(x, labels, 'x')
+        ids = None
+        if sample_ids is not None:
+            ids = np.ascontiguousarray(sample_ids, dtype=np.int32).ravel()
+            if ids.shape != labels.shape:
+                raise ValueError(f'sample_ids {ids.shape}: expected {labels.shape}')
+        loss = np.empty(2, np.float32)
+        grad = np.empty_like(packed)
+        mov = np.empty_like(packed) if moving else None
+        self._check(self.lib.mmla_si_base_loss_grad(
+            self.h, _ptr(packed), packed.size, int(n_classes), _ptr(x), _ptr(labels), x.shape[0], _seed64(drop_seed),
+            int(epoch), _ptr(ids), _ptr(loss), _ptr(grad), _ptr(mov), 0), 'mmla_si_base_loss_grad')
+        return (loss, grad, mov) if moving else (loss, grad)
+
+    def si_base_train(self, packed, n_classes, x, labels, val_x, val_labels, perm, epochs, batch=32, lr=1e-4,
+                      drop_seed=0, patience=0, ckpt_period=0):
+        """The reference's train() on the device (mmla_si_base_train): RMSprop through the whole SI network
+        in training mode from the blob `packed`.  x [n,256,39], labels [n]; val_* likewise (None or empty:
+        no validation set); perm [epochs,n].  -> (packed_out, best float32 [n_floats] or None, history
+        [epochs,4] = loss, categorical_accuracy, val_loss, val_categorical_accuracy with NaN rows after an
+        early stop, epochs_run, best_epoch or -1)."""
+        packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
+        x, labels = self._si_windows(x, labels, 'x')
+        n = x.shape[0]
+        epochs = int(epochs)
+        perm = np.ascontiguousarray(perm, dtype=np.int32).reshape(-1, n) if epochs else np.zeros((0, n), np.int32)
+        if perm.shape != (epochs, n):
+            raise ValueError(f'perm {perm.shape}: expected [{epochs},{n}]')
+        nv = 0 if val_labels is None else len(val_labels)
+        vx = vl = None
+        if nv:
+            vx, vl = self._si_windows(val_x, val_labels, 'val_x')
+        out = np.empty_like(packed)
+        best = np.empty_like(packed)
+        hist = np.empty((epochs, 4), np.float32)
+        ran = np.zeros(1, np.int32)
+        best_ep = np.full(1, -1, np.int32)
+        self._check(self.lib.mmla_si_base_train(
+            self.h, _ptr(packed), packed.size, int(n_classes), _ptr(x), _ptr(labels), n, _ptr(vx), _ptr(vl), nv,
+            epochs, int(batch), float(lr), _ptr(perm) if epochs else None, _seed64(drop_seed), int(patience),
+            int(ckpt_period), _ptr(out), _ptr(best), _ptr(hist) if epochs else None, _ptr(ran), _ptr(best_ep), 0),
+            'mmla_si_base_train')
+        return out, (best if best_ep[0] >= 0 else None), hist, int(ran[0]), int(best_ep[0])
+
     @staticmethod
     def _od_images(img, labels, what):
         img = np.ascontiguousarray(img, dtype=np.uint8)
@@ -1274,6 +1356,30 @@ class Context:
             self.h, packed, n_floats, n_classes, x, labels, n_train, val_x or None, val_labels or None,
             n_val, epochs, batch, float(lr), perm, packed_out, history, MMLA_DEVICE_PTR),
             'mmla_si_finetune(dev)')
+
+    def si_base_drop_mask_dev(self, drop_seed, epoch, sample_ids, n, mask_a, mask_b):
+        """mmla_si_base_drop_mask on device buffers (sample_ids 0: 0..n-1)"""
+        self._check(self.lib.mmla_si_base_drop_mask(self.h, _seed64(drop_seed), epoch, sample_ids or None, n, mask_a,
+                                                    mask_b, MMLA_DEVICE_PTR), 'mmla_si_base_drop_mask(dev)')
+
+    def si_base_loss_grad_dev(self, packed, n_floats, n_classes, x, labels, n, drop_seed, epoch, sample_ids,
+                              loss, grad, moving_out=0):
+        """mmla_si_base_loss_grad on device buffers (labels in [0, K) are the caller's to guarantee)"""
+        self._check(self.lib.mmla_si_base_loss_grad(
+            self.h, packed, n_floats, n_classes, x, labels, n, _seed64(drop_seed), epoch, sample_ids or None, loss,
+            grad, moving_out or None, MMLA_DEVICE_PTR), 'mmla_si_base_loss_grad(dev)')
+
+    def si_base_train_dev(self, packed, n_floats, n_classes, x, labels, n_train, val_x, val_labels, n_val,
+                          epochs, batch, lr, perm, drop_seed, patience, ckpt_period, packed_out, best_out,
+                          history, epochs_run, best_epoch):
+        """mmla_si_base_train on device buffers (epochs_run, best_epoch: device int32 words): the caller
+        guarantees labels in [0, K) and that every perm row is a permutation; asynchronous on the context's
+        stream unless a callback is on (patience or ckpt_period > 0 with n_val > 0)"""
+        self._check(self.lib.mmla_si_base_train(
+            self.h, packed, n_floats, n_classes, x, labels, n_train, val_x or None, val_labels or None, n_val,
+            epochs, batch, float(lr), perm or None, _seed64(drop_seed), patience, ckpt_period, packed_out,
+            best_out or None, history or None, epochs_run, best_epoch, MMLA_DEVICE_PTR),
+            'mmla_si_base_train(dev)')
 
     def od_loss_grad_dev(self, packed, n_floats, img, labels, n, h, w, class_w, drop_mask, loss, grad,
                          moving_out=0):

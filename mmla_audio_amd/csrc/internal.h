@@ -5,7 +5,8 @@
 //   net_runners.cpp  conv_spatial, lstm_run, run_od_net, run_si_net (which kernel runs which block)
 //   pipeline.cpp     staging, micro-batching, the range guard; feature / forward / pipeline entry points
 //   capi.cpp         the auxiliary entry points and the head trainer (mmla_si_head_fit)
-//   si_finetune.cpp  the whole-network trainer (mmla_si_loss_grad, mmla_si_finetune) over si_bwd.hip
+//   si_finetune.cpp  SI-NET's whole-network trainer over si_bwd.hip (mmla_si_loss_grad, mmla_si_finetune) and,
+//                    with si_base.hip, the base model's training from scratch (mmla_si_base_*)
 //   od_finetune.cpp  OD-NET's trainer (mmla_od_loss_grad, mmla_od_finetune) over conv.hip, od_bwd.hip, si_bwd.hip
 // All but mmla_ctx (the type include/mmla.h names) lives in namespace mmla, which is not exported.
 #pragma once
@@ -267,7 +268,7 @@ enum Slot {
   S_NR_PROF, S_COND_Q, S_COND_KEPT,       // profile indices of the gate; mmla_condition's outputs
   S_ROOM_P, S_ROOM_A,                     // mmla_room_pipeline_conditioned: the SI outputs' staging
   S_ENROL_VAD, S_ENROL_NW,                // mmla_si_enrol_embed: the temporary detectors, the window counts
-  S_FT,  // mmla_si_loss_grad / mmla_si_finetune: the blob's copy, its gradient and every activation
+  S_FT,  // mmla_si_loss_grad / mmla_si_finetune / mmla_si_base_*: the blob's copy, its gradient and every activation
   S_MIX, S_MIX_LEN,  // mmla_od_mix / mmla_od_pipeline_mixed: a micro-batch's mixed clips and their lengths
   S_ODFT   // mmla_od_loss_grad / mmla_od_finetune: the blob's copy, its gradient and every activation
 };

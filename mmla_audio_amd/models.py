@@ -217,6 +217,16 @@ class SpeakerIdModel(_Model):
         setattr(self.ctx, f'_owner_{self.kind}', self)
         self.W, self.n_classes, self.head = dict(W), int(n_classes), int(head)
 
+    def save(self, path):
+        """``model.save(path)`` for a softmax-headed model (a base model: ``res_model`` / ``train``): its
+        variables in the base layout (``tfbundle.save_speaker_base``), which ``load_model(path)`` and
+        ``transfer_learning(..., base_model_path=path)`` read back bit for bit.  A sigmoid-headed
+        (deployed) model is what ``transfer_learning`` writes itself."""
+        if self.head != _lib.HEAD_SOFTMAX:
+            raise ValueError('save() writes base models (softmax head); transfer_learning saves the deployed one')
+        os.makedirs(path, exist_ok=True)
+        tfbundle.save_speaker_base(path, self.W, self.n_classes)
+
     def predict_wavs(self, pcm, lens=None):
         """Fused WAV -> speaker: -> (probs [N,K], argmax [N] (-1 = 'silent'), silent [N])."""
         self._ensure_loaded()

@@ -314,6 +314,118 @@ def transfer_learning_on_experiment(root_dir, **kw):
     return transfer_learning(x, y, 1, 0, root_dir + '/timit/model', final_model_path, **kw)
 
 
+def res_model(input_shape=(256, 39), n_classes=630, seed=0, device=None):
+    """speaker_identification.py:115-219: the untrained base network, a ``SpeakerIdModel`` with a softmax
+    head on the Keras initial state (``weights.initial``: the initialisers' distributions with numpy's
+    draws, not TensorFlow's).  input_shape must be the (256, 39) of the feature functions."""
+    from . import models, weights
+    if tuple(input_shape) != (_lib.SI_FRAMES, _lib.SI_DIMS):
+        raise ValueError(f'input_shape {tuple(input_shape)}: the network is built for (256, 39)')
+    n_classes = int(n_classes)
+    if not 1 <= n_classes <= _lib.SI_BASE_MAX_CLASSES:
+        raise ValueError(f'{n_classes} classes outside [1, {_lib.SI_BASE_MAX_CLASSES}]')
+    return models.SpeakerIdModel(weights.initial(weights.SI, seed, n_classes), n_classes, _lib.HEAD_SOFTMAX,
+                                 device=device)
+
+
+HISTORY_KEYS = ('loss', 'categorical_accuracy', 'val_loss', 'val_categorical_accuracy')
+
+
+class History:
+    """What ``model.fit`` returns, as far as the reference reads it (:530-551): ``history`` is a dict of
+    the four Keras keys, one value per epoch run.  ``epochs_run`` and ``best_epoch`` (0-based, None if no
+    checkpoint was taken) say what the two callbacks did."""
+
+    def __init__(self, rows, epochs_run, best_epoch):
+        rows = np.asarray(rows, np.float32)[:epochs_run]
+        self.history = {k: [float(v) for v in rows[:, i]] for i, k in enumerate(HISTORY_KEYS)}
+        self.epoch = list(range(epochs_run))
+        self.epochs_run = int(epochs_run)
+        self.best_epoch = None if best_epoch < 0 else int(best_epoch)
+
+
+def _one_hot_labels(y, what):
+    y = np.asarray(y)
+    if y.ndim != 2 or len(y) == 0:
+        raise ValueError(f'{what} {y.shape}: expected one one-hot row per window')
+    bad = np.flatnonzero(~(((y == 0) | (y == 1)).all(axis=1) & (y.sum(axis=1) == 1)))
+    if bad.size:
+        raise ValueError(f'{what} row {int(bad[0])} is not one-hot')
+    return y.argmax(axis=1).astype(np.int32)
+
+
+def train(x_train, y_train, x_validate, y_validate, *, epochs=200, batch_size=32, lr=1e-4, patience=10,
+          checkpoint_path=None, checkpoint_period=10, seed=0, device=None):
+    """speaker_identification.py:221-250 on the device (``mmla_si_base_train``): ``res_model`` trained from
+    its initial state with RMSprop(lr), categorical cross-entropy, batch_size windows a step, for at most
+    `epochs` epochs under EarlyStopping(val_loss, patience) and ModelCheckpoint(val_categorical_accuracy,
+    save_best_only, mode 'max', period=checkpoint_period).  y is one-hot as the reference passes it; the
+    class count is y_train.shape[1].  -> (model, history): the model holds the LAST epoch's weights (no
+    restore_best_weights), is installed on the device and answers predict / predict_wavs at once;
+    history.history is the dict the reference plots, history.best_epoch the checkpointed epoch.  With
+    checkpoint_path the best weights are saved there in the base layout (``tfbundle.save_speaker_base``)
+    when a checkpoint was taken.  Everything random comes from `seed` through numpy: the initial state
+    (``weights.initial``), the order of every epoch and the dropout seed; TensorFlow's streams are not
+    reproduced."""
+    from . import models, tfbundle, weights
+    x_train = np.asarray(x_train)
+    labels = _one_hot_labels(y_train, 'y_train')
+    K = int(np.shape(y_train)[1])
+    if len(x_train) != len(labels):
+        raise ValueError(f'x_train {x_train.shape}: expected one window per row of y_train')
+    nv = 0 if x_validate is None else len(x_validate)
+    vx = vl = None
+    if nv:
+        vl = _one_hot_labels(y_validate, 'y_validate')
+        if np.shape(y_validate)[1] != K or len(vl) != nv:
+            raise ValueError(f'y_validate {np.shape(y_validate)}: expected [{nv},{K}]')
+        vx = np.asarray(x_validate).astype(np.float32)
+    epochs = int(epochs)
+    if epochs < 0 or batch_size < 1:
+        raise ValueError('epochs must be >= 0 and batch_size >= 1')
+    model = res_model(x_train.shape[1:], K, seed, device)
+    rng = np.random.default_rng([int(seed), 3])
+    drop_seed = int(rng.integers(0, 2 ** 63))
+    perm = np.empty((epochs, len(labels)), np.int32)
+    for e in range(epochs):
+        perm[e] = rng.permutation(len(labels))
+    period = int(checkpoint_period)
+    out, best, hist, ran, best_ep = model.ctx.si_base_train(
+        weights.pack(weights.SI, model.W, K), K, x_train.astype(np.float32), labels, vx, vl, perm, epochs,
+        batch_size, lr, drop_seed, patience, period)
+    model.set_weights(weights.unpack(weights.SI, out, K), K, _lib.HEAD_SOFTMAX)
+    if checkpoint_path is not None and best is not None:
+        os.makedirs(checkpoint_path, exist_ok=True)
+        tfbundle.save_speaker_base(checkpoint_path, weights.unpack(weights.SI, best, K), K)
+    return model, History(hist, ran, best_ep)
+
+
+def make_feature_timit(wav_files, speaker_ids, data_dir, device=None, chunk=256):
+    """speaker_identification.py:264-314 with data_dir in the place of Root_Dir + '/timit/data': per file
+    the MFCC + delta + delta-delta features of the whole recording, zero-padded or cut to 256 frames, and
+    the one-hot speaker rows of ``binarizer(dim=630)`` -> (x float64 [n,256,39], y [n,630]).  wav_files
+    and speaker_ids are sequences (or pandas columns, as the reference passes them); device: a device
+    index or a ``_lib.Context``.  Unlike
+    ``input_feature_gen`` there is no 'silent' rule here: a recording below 4000 samples gets its
+    features like any other, as in the reference.  Features run `chunk` files at a time on the device
+    (``input_feature_batch``'s call; a recording below that length goes through ``si_features_seq``)."""
+    wav_files = list(getattr(wav_files, 'values', wav_files))
+    speaker_ids = list(getattr(speaker_ids, 'values', speaker_ids))
+    if len(wav_files) != len(speaker_ids):
+        raise ValueError(f'{len(wav_files)} files, {len(speaker_ids)} speaker ids')
+    ctx = _lib.default_context(device) if device is None or isinstance(device, int) else device
+    xs = []
+    for i0 in range(0, len(wav_files), int(chunk)):
+        sigs = [_read(os.path.join(str(data_dir), str(f))) for f in wav_files[i0:i0 + int(chunk)]]
+        feat, silent = ctx.si_features(sigs)
+        for j in np.flatnonzero(silent):      # below the 'silent' length: the whole-signal path, window 0
+            feat[j] = ctx.si_features_seq(sigs[j])[0] if len(sigs[j]) else 0.0
+        xs.append(feat.astype(np.float64))
+    y = binarizer(speaker_ids, dim=630)
+    x = np.concatenate(xs) if xs else np.zeros((0, _lib.SI_FRAMES, _lib.SI_DIMS))
+    return x, np.asarray(y)
+
+
 def conversation_features(sig, device=None):
     """Whole-sequence MFCC + deltas cut into 256-frame windows -> float64 [S, 256, 39]
     (speaker_identification_post_processing.py:255-269; make_feature_experiment :341-353)."""

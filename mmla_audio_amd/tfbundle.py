@@ -287,6 +287,26 @@ def save_deployed(model_dir, W, n_classes):
     _write_bundle(model_dir, tensors)
 
 
+def save_speaker_base(model_dir, W, n_classes):
+    """Write an SI base model -- what the reference's ``train`` leaves behind through ``model.save`` /
+    ``ModelCheckpoint`` (speaker_identification.py:238-250, :529) -- as a variable bundle under
+    ``<model_dir>/variables/`` in the base-model layout ``layout`` documents, with the keys of the reference's
+    own ``timit/model`` index: every conv, BN and Dense variable under its ``layer_with_weights-k``, the
+    Bidirectional LSTM's six tensors as ``trainable_variables/82..87`` (their index among the trainable
+    variables in ``weights.si_spec`` order).  W: {canonical name: array} with an n_classes-way softmax head.
+    ``load_bundle`` / ``models.load_model`` return every tensor bit for bit.  As with ``save_deployed`` only
+    the model's variables are written -- no optimizer slots, metrics or object graph, which this package
+    never reads -- and parity of the key layout with a real TF save rests on that index alone."""
+    from . import weights
+    items = weights.si_spec(n_classes)
+    weights.check(weights.SI, W, n_classes)
+    trainable = _numbering(items)['trainable_variables']
+    tensors = {}
+    for name, _, role in items:
+        tensors[f'trainable_variables/{trainable.index(name)}' if role.startswith('lstm_') else name] = W[name]
+    _write_bundle(model_dir, tensors)
+
+
 def save_overlap(model_dir, W):
     """Write OD-NET -- what ``continue_train_model`` leaves behind -- as a variable bundle under
     ``<model_dir>/variables/`` in the base-model layout ``layout`` documents for ``timit2.0``: every conv, BN

@@ -182,6 +182,33 @@ def synthetic(kind, seed=0, n_classes=None, head_gain=None):
     return {k: np.asarray(v, dtype=np.float32) for k, v in W.items()}
 
 
+def initial(kind, seed=0, n_classes=None):
+    """The state a freshly built Keras model starts training from (``res_model``,
+    speaker_identification.py:115-219), for SI: Glorot-uniform kernels, zero biases, gamma 1, beta 0,
+    moving mean 0, moving variance 1, orthogonal recurrent kernels, LSTM bias 0 with the forget block 1
+    (``unit_forget_bias``).  The draws are numpy's (PCG64 seeded by ``seed``): the initialisers'
+    distributions are Keras's, TensorFlow's generator is not reproduced, so no seed gives TensorFlow's
+    numbers.  OD-NET is trained only further here (``continue_train_model``), never from scratch.
+    """
+    if kind != SI:
+        raise NotImplementedError('weights.initial: only the SI network is trained from scratch')
+    rng = np.random.default_rng(np.random.PCG64(0x696E6974 + 7919 * int(seed)))
+    fixed = {'bias': 0.0, 'bn_gamma': 1.0, 'bn_beta': 0.0, 'bn_mean': 0.0, 'bn_var': 1.0}
+    W = {}
+    for name, shape, role in spec(kind, n_classes):
+        if role in ('kernel', 'lstm_kernel'):
+            W[name] = _glorot(rng, shape)[0]
+        elif role == 'lstm_rec':
+            W[name] = _orthogonal(rng, shape)
+        elif role == 'lstm_bias':
+            b = np.zeros(shape)
+            b[LSTM_UNITS:2 * LSTM_UNITS] = 1.0
+            W[name] = b
+        else:
+            W[name] = np.full(shape, fixed[role])
+    return {k: np.asarray(v, dtype=np.float32) for k, v in W.items()}
+
+
 def check(kind, W, n_classes=None):
     """Raise ValueError unless W has exactly the spec's names and shapes."""
     items = spec(kind, n_classes)
