@@ -740,14 +740,34 @@ class Context:
             raise ValueError(f'{what} {x.shape} / labels {labels.shape}: expected [n,256,39] and [n]')
         return x, labels
 
+    @staticmethod
+    def _fit_args(perm, epochs, n, val_x, val_labels, prep, what='val_x', trim=False):
+        """What the fit wrappers prepare alike: perm as int32 [epochs, n] (trim: rows past epochs dropped), the
+        optional validation set through prep(val_x, val_labels, what).  -> (epochs, perm, vx, vl, nv, opt);
+        opt(a) is a's pointer, or None in a zero-epoch call, which must not read it."""
+        epochs = int(epochs)
+        perm = np.ascontiguousarray(perm, dtype=np.int32).reshape(-1, n) if epochs else np.zeros((0, n), np.int32)
+        if trim:
+            perm = np.ascontiguousarray(perm[:epochs])
+        if perm.shape != (epochs, n):
+            raise ValueError(f'perm {perm.shape}: expected [{epochs},{n}]')
+        nv = 0 if val_labels is None else len(val_labels)
+        vx = vl = None
+        if nv:
+            vx, vl = prep(val_x, val_labels, what)
+        return epochs, perm, vx, vl, nv, (_ptr if epochs else lambda a: None)
+
+    def _si_grad_args(self, packed, x, labels):
+        """-> (packed flat float32, x, labels, loss [2], grad like packed) of the two SI loss-grad wrappers"""
+        packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
+        x, labels = self._si_windows(x, labels, 'x')
+        return packed, x, labels, np.empty(2, np.float32), np.empty_like(packed)
+
     def si_loss_grad(self, packed, n_classes, x, labels):
         """The stage-2 loss of ONE batch and its gradient (mmla_si_loss_grad): packed = the SI blob of
         weights.pack with an n_classes-way head, x [n,256,39], labels [n] -> (loss float32 [2] = data
         term, L2 penalty; grad float32 [n_floats] in the packed order, 0 in the moving statistics)."""
-        packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
-        x, labels = self._si_windows(x, labels, 'x')
-        loss = np.empty(2, np.float32)
-        grad = np.empty_like(packed)
+        packed, x, labels, loss, grad = self._si_grad_args(packed, x, labels)
         self._check(self.lib.mmla_si_loss_grad(self.h, _ptr(packed), packed.size, int(n_classes), _ptr(x),
                                                _ptr(labels), x.shape[0], _ptr(loss), _ptr(grad), 0),
                     'mmla_si_loss_grad')
@@ -761,20 +781,12 @@ class Context:
         packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
         x, labels = self._si_windows(x, labels, 'x')
         n = x.shape[0]
-        epochs = int(epochs)
-        perm = np.ascontiguousarray(perm, dtype=np.int32).reshape(-1, n) if epochs else np.zeros((0, n), np.int32)
-        if perm.shape != (epochs, n):
-            raise ValueError(f'perm {perm.shape}: expected [{epochs},{n}]')
-        nv = 0 if val_labels is None else len(val_labels)
-        vx = vl = None
-        if nv:
-            vx, vl = self._si_windows(val_x, val_labels, 'val_x')
+        epochs, perm, vx, vl, nv, opt = self._fit_args(perm, epochs, n, val_x, val_labels, self._si_windows)
         out = np.empty_like(packed)
         hist = np.empty((epochs, 4), np.float32)
         self._check(self.lib.mmla_si_finetune(
             self.h, _ptr(packed), packed.size, int(n_classes), _ptr(x), _ptr(labels), n, _ptr(vx), _ptr(vl),
-            nv, epochs, int(batch), float(lr), _ptr(perm) if epochs else None, _ptr(out),
-            _ptr(hist) if epochs else None, 0), 'mmla_si_finetune')
+            nv, epochs, int(batch), float(lr), opt(perm), _ptr(out), opt(hist), 0), 'mmla_si_finetune')
         return out, hist
 
     def si_base_drop_mask(self, drop_seed, epoch, sample_ids, n=None):
@@ -799,15 +811,12 @@ class Context:
         epoch, sample_ids), the softmax head's loss on the logits.  -> (loss float32 [2] = data term, L2
         penalty; grad float32 [n_floats], 0 in the moving statistics) and, with moving=True, the blob with
         only its moving statistics advanced one step."""
-        packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
-        x, labels = self._si_windows(x, labels, 'x')
+        packed, x, labels, loss, grad = self._si_grad_args(packed, x, labels)
         ids = None
         if sample_ids is not None:
             ids = np.ascontiguousarray(sample_ids, dtype=np.int32).ravel()
             if ids.shape != labels.shape:
                 raise ValueError(f'sample_ids {ids.shape}: expected {labels.shape}')
-        loss = np.empty(2, np.float32)
-        grad = np.empty_like(packed)
         mov = np.empty_like(packed) if moving else None
         self._check(self.lib.mmla_si_base_loss_grad(
             self.h, _ptr(packed), packed.size, int(n_classes), _ptr(x), _ptr(labels), x.shape[0], _seed64(drop_seed),
@@ -824,14 +833,7 @@ class Context:
         packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
         x, labels = self._si_windows(x, labels, 'x')
         n = x.shape[0]
-        epochs = int(epochs)
-        perm = np.ascontiguousarray(perm, dtype=np.int32).reshape(-1, n) if epochs else np.zeros((0, n), np.int32)
-        if perm.shape != (epochs, n):
-            raise ValueError(f'perm {perm.shape}: expected [{epochs},{n}]')
-        nv = 0 if val_labels is None else len(val_labels)
-        vx = vl = None
-        if nv:
-            vx, vl = self._si_windows(val_x, val_labels, 'val_x')
+        epochs, perm, vx, vl, nv, opt = self._fit_args(perm, epochs, n, val_x, val_labels, self._si_windows)
         out = np.empty_like(packed)
         best = np.empty_like(packed)
         hist = np.empty((epochs, 4), np.float32)
@@ -839,9 +841,8 @@ class Context:
         best_ep = np.full(1, -1, np.int32)
         self._check(self.lib.mmla_si_base_train(
             self.h, _ptr(packed), packed.size, int(n_classes), _ptr(x), _ptr(labels), n, _ptr(vx), _ptr(vl), nv,
-            epochs, int(batch), float(lr), _ptr(perm) if epochs else None, _seed64(drop_seed), int(patience),
-            int(ckpt_period), _ptr(out), _ptr(best), _ptr(hist) if epochs else None, _ptr(ran), _ptr(best_ep), 0),
-            'mmla_si_base_train')
+            epochs, int(batch), float(lr), opt(perm), _seed64(drop_seed), int(patience), int(ckpt_period),
+            _ptr(out), _ptr(best), opt(hist), _ptr(ran), _ptr(best_ep), 0), 'mmla_si_base_train')
         return out, (best if best_ep[0] >= 0 else None), hist, int(ran[0]), int(best_ep[0])
 
     @staticmethod
@@ -884,31 +885,25 @@ class Context:
         packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
         img, labels = self._od_images(img, labels, 'img')
         n, h, w = img.shape[:3]
-        epochs = int(epochs)
+        epochs, perm, vi, vl, nv, opt = self._fit_args(perm, epochs, n, val_img, val_labels, self._od_images, 'val_img',
+                                                        trim=True)
         cw = np.ascontiguousarray(class_w, dtype=np.float32).reshape(2)
         lr = np.ascontiguousarray(lr, dtype=np.float32).ravel()[:epochs]
-        perm = np.ascontiguousarray(perm, dtype=np.int32).reshape(-1, n)[:epochs] if epochs else np.zeros((0, n), np.int32)
-        perm = np.ascontiguousarray(perm)
-        if perm.shape != (epochs, n) or lr.shape != (epochs,):
-            raise ValueError(f'perm {perm.shape} / lr {lr.shape}: expected [{epochs},{n}] and [{epochs}]')
+        if lr.shape != (epochs,):
+            raise ValueError(f'lr {lr.shape}: expected [{epochs}]')
         if drop_mask is not None:
             drop_mask = np.ascontiguousarray(np.asarray(drop_mask, dtype=np.uint8)[:epochs])
             if drop_mask.shape != (epochs, n, OD_DROP_UNITS):
                 raise ValueError(f'drop_mask {drop_mask.shape}: expected [{epochs},{n},{OD_DROP_UNITS}]')
-        nv = 0 if val_labels is None else len(val_labels)
-        vi = vl = None
-        if nv:
-            vi, vl = self._od_images(val_img, val_labels, 'val_img')
-            if vi.shape[1:] != img.shape[1:]:
-                raise ValueError(f'val_img {vi.shape}: expected [n,{h},{w},3]')
+        if nv and vi.shape[1:] != img.shape[1:]:
+            raise ValueError(f'val_img {vi.shape}: expected [n,{h},{w},3]')
         out = np.empty_like(packed)
         hist = np.empty((epochs, 5), np.float32)
         ran = np.zeros(1, np.int32)
         self._check(self.lib.mmla_od_finetune(
             self.h, _ptr(packed), packed.size, _ptr(img), _ptr(labels), n, _ptr(vi), _ptr(vl), nv, h, w, _ptr(cw),
-            epochs, int(batch), _ptr(lr) if epochs else None, _ptr(perm) if epochs else None,
-            _ptr(drop_mask) if epochs else None, int(patience), _ptr(out), _ptr(hist) if epochs else None,
-            _ptr(ran), 0), 'mmla_od_finetune')
+            epochs, int(batch), opt(lr), opt(perm), opt(drop_mask), int(patience), _ptr(out), opt(hist), _ptr(ran), 0),
+            'mmla_od_finetune')
         return out, hist, int(ran[0])
 
     def od_pipeline(self, pcm, lens=None):

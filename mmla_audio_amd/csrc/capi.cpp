@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <numeric>
 
+#include "fit_common.h"
 #include "internal.h"
 #include "resample.h"
 #include "si_train.h"
@@ -544,29 +545,15 @@ int mmla_si_head_fit(mmla_ctx* c, const float* emb, const int32_t* labels, int64
   if (!emb || !labels || !w0 || !b0 || !w || !b || (epochs > 0 && !perm) ||
       (n_val > 0 && (!val_emb || !val_labels)))
     return fail(c, MMLA_E_INVALID, "head_fit: null pointer");
-  const bool dev = flags & MMLA_DEVICE_PTR;
+  Stager st{c, (flags & MMLA_DEVICE_PTR) != 0};
   const int K = n_classes, R = n_restarts;
-  const size_t n_perm = (size_t)R * epochs * n_train;
-  if (!dev) {   // device-pointer calls: the caller guarantees labels and permutations
-    for (int64_t i = 0; i < n_train; ++i)
-      if (labels[i] < 0 || labels[i] >= K)
-        return fail(c, MMLA_E_INVALID, "labels[%lld] = %d outside [0, %d)", (long long)i, labels[i], K);
-    for (int64_t i = 0; i < n_val; ++i)
-      if (val_labels[i] < 0 || val_labels[i] >= K)
-        return fail(c, MMLA_E_INVALID, "val_labels[%lld] = %d outside [0, %d)", (long long)i,
-                    val_labels[i], K);
-    std::vector<uint8_t> seen(n_train);
-    for (size_t row = 0; row < (size_t)R * epochs; ++row) {
-      std::fill(seen.begin(), seen.end(), 0);
-      const int32_t* p = perm + row * n_train;
-      for (int64_t i = 0; i < n_train; ++i) {
-        if (p[i] < 0 || p[i] >= n_train || seen[p[i]])
-          return fail(c, MMLA_E_INVALID, "perm row %lld (restart %lld, epoch %lld) is not a permutation "
-                      "of 0..%lld", (long long)row, (long long)(row / std::max(epochs, 1)),
-                      (long long)(row % std::max(epochs, 1)), (long long)(n_train - 1));
-        seen[p[i]] = 1;
-      }
-    }
+  if (!st.dev) {   // device-pointer calls: the caller guarantees labels and permutations
+    CHK(check_labels(c, "labels", labels, n_train, K));
+    CHK(check_labels(c, "val_labels", val_labels, n_val, K));
+    const int64_t row = bad_perm_row(perm, (int64_t)R * epochs, n_train);
+    if (row >= 0)
+      return fail(c, MMLA_E_INVALID, "perm row %lld (restart %lld, epoch %lld) is not a permutation of 0..%lld",
+                  (long long)row, (long long)(row / epochs), (long long)(row % epochs), (long long)(n_train - 1));
   }
   HIPCHK(c, hipSetDevice(c->device));
   SiTrainArgs a{};
@@ -577,68 +564,27 @@ int mmla_si_head_fit(mmla_ctx* c, const float* emb, const int32_t* labels, int64
   a.batch = batch;
   a.lr = lr;
   const size_t nw = (size_t)R * MMLA_SI_EMBED * K, nb = (size_t)R * K, nh = (size_t)R * epochs * 4;
-  char* base = nullptr;
-  size_t off_w = 0, off_b = 0, off_h = 0;
-  if (dev) {
-    a.emb = emb;
-    a.labels = labels;
-    a.val_emb = val_emb;
-    a.val_labels = val_labels;
-    a.w0 = w0;
-    a.b0 = b0;
-    a.perm = perm;
-    a.w = w;
-    a.b = b;
-    a.history = history;
-  } else {
-    // every operand in one workspace slot, each at a 256-byte boundary
-    size_t total = 0;
-    auto take = [&](size_t bytes) {
-      const size_t at = total;
-      total += (bytes + 255) & ~(size_t)255;
-      return at;
-    };
-    const size_t o_e = take(n_train * MMLA_SI_EMBED * sizeof(float)), o_l = take(n_train * sizeof(int32_t));
-    const size_t o_ve = take(n_val * MMLA_SI_EMBED * sizeof(float)), o_vl = take(n_val * sizeof(int32_t));
-    const size_t o_w0 = take(nw * sizeof(float)), o_b0 = take(nb * sizeof(float));
-    const size_t o_p = take(n_perm * sizeof(int32_t));
-    off_w = take(nw * sizeof(float));
-    off_b = take(nb * sizeof(float));
-    off_h = take(nh * sizeof(float));
-    void* p = nullptr;
-    CHK(ws_get(c, S_TRAIN, total, &p));
-    base = static_cast<char*>(p);
-    auto up = [&](size_t at, const void* src, size_t bytes) -> hipError_t {
-      return bytes ? hipMemcpyAsync(base + at, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
-    };
-    HIPCHK(c, up(o_e, emb, n_train * MMLA_SI_EMBED * sizeof(float)));
-    HIPCHK(c, up(o_l, labels, n_train * sizeof(int32_t)));
-    HIPCHK(c, up(o_ve, val_emb, n_val * MMLA_SI_EMBED * sizeof(float)));
-    HIPCHK(c, up(o_vl, val_labels, n_val * sizeof(int32_t)));
-    HIPCHK(c, up(o_w0, w0, nw * sizeof(float)));
-    HIPCHK(c, up(o_b0, b0, nb * sizeof(float)));
-    HIPCHK(c, up(o_p, perm, n_perm * sizeof(int32_t)));
-    a.emb = reinterpret_cast<const float*>(base + o_e);
-    a.labels = reinterpret_cast<const int32_t*>(base + o_l);
-    a.val_emb = reinterpret_cast<const float*>(base + o_ve);
-    a.val_labels = reinterpret_cast<const int32_t*>(base + o_vl);
-    a.w0 = reinterpret_cast<const float*>(base + o_w0);
-    a.b0 = reinterpret_cast<const float*>(base + o_b0);
-    a.perm = reinterpret_cast<const int32_t*>(base + o_p);
-    a.w = reinterpret_cast<float*>(base + off_w);
-    a.b = reinterpret_cast<float*>(base + off_b);
-    a.history = history ? reinterpret_cast<float*>(base + off_h) : nullptr;
-  }
+  // host pointers: every operand in one workspace slot
+  CHK(carve_slot(c, S_TRAIN, [&](Carver& cv) -> int {
+    CHK(st.in(cv, emb, (size_t)n_train * MMLA_SI_EMBED, &a.emb));
+    CHK(st.in(cv, labels, (size_t)n_train, &a.labels));
+    CHK(st.in(cv, val_emb, (size_t)n_val * MMLA_SI_EMBED, &a.val_emb));
+    CHK(st.in(cv, val_labels, (size_t)n_val, &a.val_labels));
+    CHK(st.in(cv, w0, nw, &a.w0));
+    CHK(st.in(cv, b0, nb, &a.b0));
+    CHK(st.in(cv, perm, (size_t)R * epochs * n_train, &a.perm));
+    a.w = st.out(cv, w, nw);
+    a.b = st.out(cv, b, nb);
+    a.history = st.out(cv, history, nh);
+    return MMLA_OK;
+  }));
   // forward + gradient on the training set, forward on the validation set, per epoch and restart
   const double flops = (double)R * epochs * 2.0 * MMLA_SI_EMBED * K * (2.0 * n_train + n_val);
   LAUNCH(c, MMLA_STAGE_HEAD, flops, si_train_launch(a, R, c->stream));
-  if (!dev) {
-    HIPCHK(c, hipMemcpyAsync(w, base + off_w, nw * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b, base + off_b, nb * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (history && nh)
-      HIPCHK(c, hipMemcpyAsync(history, base + off_h, nh * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  }
-  return finish(c, dev);
+  CHK(st.back(w, a.w, nw));
+  CHK(st.back(b, a.b, nb));
+  CHK(st.back(history, a.history, nh));
+  return finish(c, st.dev);
 }
 
 }  // extern "C"

@@ -5,9 +5,13 @@
 //   net_runners.cpp  conv_spatial, lstm_run, run_od_net, run_si_net (which kernel runs which block)
 //   pipeline.cpp     staging, micro-batching, the range guard; feature / forward / pipeline entry points
 //   capi.cpp         the auxiliary entry points and the head trainer (mmla_si_head_fit)
-//   si_finetune.cpp  SI-NET's whole-network trainer over si_bwd.hip (mmla_si_loss_grad, mmla_si_finetune) and,
-//                    with si_base.hip, the base model's training from scratch (mmla_si_base_*)
-//   od_finetune.cpp  OD-NET's trainer (mmla_od_loss_grad, mmla_od_finetune) over conv.hip, od_bwd.hip, si_bwd.hip
+//   fit_common.h     what the trainers share, host code only: Carver / carve_slot, staged operands (Stager),
+//                    check_perm / check_labels, wire_lstm / mark_trainable and the fit driver (fit_check, fit)
+//   si_finetune.cpp  SI-NET's engine over si_bwd.hip and, with `base`, si_base.hip; one loss-grad body
+//                    (mmla_si_loss_grad, mmla_si_base_loss_grad) and one set of fit callables (mmla_si_finetune,
+//                    mmla_si_base_train) for the driver; mmla_si_base_drop_mask
+//   od_finetune.cpp  OD-NET's engine over conv.hip, od_bwd.hip, si_bwd.hip; mmla_od_loss_grad, and
+//                    mmla_od_finetune's callables for the driver
 // All but mmla_ctx (the type include/mmla.h names) lives in namespace mmla, which is not exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -263,14 +267,16 @@ enum Slot {
   S_OUT0, S_OUT1, S_OUT2, S_OUT3, S_IN,
   S_NR_S, S_NR_BITS, S_NR_FMAX, S_NR_FRAMES, S_NR_ITEMS, S_NR_Y, S_NR_ROWS,
   S_VAD_SPEECH, S_VAD_OUT, S_VAD_LENS, S_RS_TR, S_RS_WIN, S_LSTM,
-  S_TRAIN,  // mmla_si_head_fit: every host-pointer operand, carved from one slot
+  S_TRAIN,  // mmla_si_head_fit: every host-pointer operand, carved from one slot (carve_slot, fit_common.h)
   S_IMG2, S_GATE_Y0, S_GATE_Y1, S_SSIM,   // mmla_od_pipeline_gated / mmla_ssim_u8
   S_NR_PROF, S_COND_Q, S_COND_KEPT,       // profile indices of the gate; mmla_condition's outputs
   S_ROOM_P, S_ROOM_A,                     // mmla_room_pipeline_conditioned: the SI outputs' staging
   S_ENROL_VAD, S_ENROL_NW,                // mmla_si_enrol_embed: the temporary detectors, the window counts
-  S_FT,  // mmla_si_loss_grad / mmla_si_finetune / mmla_si_base_*: the blob's copy, its gradient and every activation
+  // mmla_si_loss_grad / mmla_si_finetune / mmla_si_base_*: the blob's copy, its gradient and every activation,
+  // then the call's staged host-pointer operands; carved anew by every call (carve_slot)
+  S_FT,
   S_MIX, S_MIX_LEN,  // mmla_od_mix / mmla_od_pipeline_mixed: a micro-batch's mixed clips and their lengths
-  S_ODFT   // mmla_od_loss_grad / mmla_od_finetune: the blob's copy, its gradient and every activation
+  S_ODFT   // mmla_od_loss_grad / mmla_od_finetune: likewise for the OD blob
 };
 
 // mmla_ctx::cap_buf: staged raw capture, host frames, per-clip entry (d0, prev), converted clips and

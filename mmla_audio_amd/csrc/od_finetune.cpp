@@ -4,12 +4,13 @@
 // data gradient is conv.hip's conv_launch (exact f32 MFMA); the weight gradients, BatchNorm in training
 // mode, the pools and the head are od_bwd.hip's; the BiLSTM is si_bwd.hip's with T = ceil(w / 8) steps.
 // A training step is a fixed sequence of launches on the context's stream; the only host synchronisation
-// of a fit is the read-back of one history row per epoch when early stopping is on.
+// of a fit is the read-back of one history row per epoch when early stopping is on.  The fit itself --
+// checks, staging, the epoch loop, early stopping -- is fit_common.h's driver; this file gives it the steps.
 #include <algorithm>
 #include <cmath>
-#include <vector>
 
 #include "conv.h"
+#include "fit_common.h"
 #include "internal.h"
 #include "od_bwd.h"
 #include "si_bwd.h"
@@ -120,18 +121,7 @@ void set_dims(Engine& e, int h, int w) {
   e.T = w;
 }
 
-// carve: first pass (base == nullptr) only measures
-struct Carver {
-  char* base;
-  size_t total = 0;
-  template <typename T>
-  T* take(size_t count) {
-    const size_t at = total;
-    total += (count * sizeof(T) + 255) & ~(size_t)255;
-    return base ? reinterpret_cast<T*>(base + at) : nullptr;
-  }
-};
-
+// the engine's buffers; the pass on a null base only measures (fit_common.h)
 void carve(Engine& e, Carver& cv, bool train) {
   const size_t B = e.cap, n = e.off.total, T = e.T;
   const size_t pix = (size_t)e.h * e.w;
@@ -181,14 +171,7 @@ void carve(Engine& e, Carver& cv, bool train) {
   l.dc = cv.take<float>(2 * B * SIB_LSTM_U);
   l.dxs = cv.take<float>(2 * B * T * SIB_LSTM_D);
   if (cv.base) {
-    for (int d = 0; d < 2; ++d) {
-      l.wk[d] = e.W + e.off.lk[d];
-      l.wr[d] = e.W + e.off.lr[d];
-      l.bias[d] = e.W + e.off.lb[d];
-      l.dwk[d] = e.G + e.off.lk[d];
-      l.dwr[d] = e.G + e.off.lr[d];
-      l.dbias[d] = e.G + e.off.lb[d];
-    }
+    wire_lstm(l, e.off, e.W, e.G);
     l.seq = e.seq;
     l.emb = e.emb;
     l.demb = e.demb;
@@ -352,12 +335,7 @@ int check_common(mmla_ctx* c, const char* who, int64_t n_floats, int32_t h, int3
   return MMLA_OK;
 }
 
-int check_labels(mmla_ctx* c, const char* what, const int32_t* l, int64_t n) {
-  for (int64_t i = 0; i < n; ++i)
-    if (l[i] < 0 || l[i] > 1)
-      return fail(c, MMLA_E_INVALID, "%s[%lld] = %d outside {0, 1}", what, (long long)i, l[i]);
-  return MMLA_OK;
-}
+constexpr const char* kLabelSet = "{0, 1}";
 
 int prepare(Engine& e, bool train) {
   hipStream_t s = e.c->stream;
@@ -368,13 +346,19 @@ int prepare(Engine& e, bool train) {
   if (!train) return MMLA_OK;
   HIPCHK(e.c, hipMemsetAsync(e.acc_g, 0, wbytes, s));   // a new optimiser: every accumulator from 0
   HIPCHK(e.c, hipMemsetAsync(e.acc_d, 0, wbytes, s));
-  HIPCHK(e.c, hipMemsetAsync(e.trainable, 1, e.off.total, s));
-  for (int i = 0; i < 9; ++i) {   // trainable = everything but moving_mean / moving_variance
-    const BlkOff& u = e.off.u[i];
-    HIPCHK(e.c, hipMemsetAsync(e.trainable + u.bn_in + 2 * u.cin, 0, 2 * (size_t)u.cin, s));
-    HIPCHK(e.c, hipMemsetAsync(e.trainable + u.bn_mid + 2 * u.cout, 0, 2 * (size_t)u.cout, s));
-  }
-  return MMLA_OK;
+  return mark_trainable(e.c, e.trainable, e.off);
+}
+
+// the engine of a checked call: the blob's size, the class weights, every block's dimensions
+Engine engine(mmla_ctx* c, int cap, int h, int w, const float* class_w) {
+  Engine e;
+  e.c = c;
+  e.cap = cap;
+  e.off = od_offsets();
+  e.cw[0] = class_w[0];
+  e.cw[1] = class_w[1];
+  set_dims(e, h, w);
+  return e;
 }
 
 }  // namespace
@@ -395,59 +379,34 @@ int mmla_od_loss_grad(mmla_ctx* c, const float* packed, int64_t n_floats, const 
   if (n < 1 || n > MMLA_OD_TRAIN_MAX_BATCH)
     return fail(c, MMLA_E_INVALID, "od_loss_grad: n %lld outside [1, %d]", (long long)n, MMLA_OD_TRAIN_MAX_BATCH);
   if (!packed || !img_u8 || !labels || !loss || !grad) return fail(c, MMLA_E_INVALID, "od_loss_grad: null pointer");
-  const bool dev = flags & MMLA_DEVICE_PTR;
-  if (!dev) CHK(check_labels(c, "labels", labels, n));
+  Stager st{c, (flags & MMLA_DEVICE_PTR) != 0};
+  if (!st.dev) CHK(check_labels(c, "labels", labels, n, 2, kLabelSet));
   HIPCHK(c, hipSetDevice(c->device));
-  Engine e;
-  e.c = c;
-  e.cap = (int)n;
-  e.off = od_offsets();
-  e.cw[0] = class_w[0];
-  e.cw[1] = class_w[1];
-  set_dims(e, h, w);
+  Engine e = engine(c, (int)n, h, w, class_w);
   const size_t img_bytes = (size_t)h * w * 3;
   float* lp = nullptr;
-  uint8_t *simg = nullptr, *smask = nullptr;
-  int32_t* sl = nullptr;
-  size_t total = 0;
-  for (int pass = 0; pass < 2; ++pass) {
-    void* p = nullptr;
-    if (pass) CHK(ws_get(c, S_ODFT, total, &p));
-    Carver cv{static_cast<char*>(p)};
+  const uint8_t *dimg = nullptr, *dmask = nullptr;
+  const int32_t* dl = nullptr;
+  CHK(carve_slot(c, S_ODFT, [&](Carver& cv) -> int {
     carve(e, cv, false);
     lp = cv.take<float>(1);
-    if (!dev) {
-      simg = cv.take<uint8_t>((size_t)n * img_bytes);
-      sl = cv.take<int32_t>(n);
-      smask = drop_mask ? cv.take<uint8_t>((size_t)n * ODB_HEAD_D) : nullptr;
-    }
-    total = cv.total;
-  }
+    CHK(st.in(cv, img_u8, (size_t)n * img_bytes, &dimg));
+    CHK(st.in(cv, labels, (size_t)n, &dl));
+    return st.in(cv, drop_mask, (size_t)n * ODB_HEAD_D, &dmask);
+  }));
   hipStream_t s = c->stream;
   const size_t wbytes = e.off.total * sizeof(float);
-  const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const hipMemcpyKind out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  const uint8_t *dimg = img_u8, *dmask = drop_mask;
-  const int32_t* dl = labels;
-  if (!dev) {
-    HIPCHK(c, hipMemcpyAsync(simg, img_u8, (size_t)n * img_bytes, in, s));
-    HIPCHK(c, hipMemcpyAsync(sl, labels, (size_t)n * sizeof(int32_t), in, s));
-    if (drop_mask) HIPCHK(c, hipMemcpyAsync(smask, drop_mask, (size_t)n * ODB_HEAD_D, in, s));
-    dimg = simg;
-    dl = sl;
-    dmask = smask;
-  }
-  HIPCHK(c, hipMemcpyAsync(e.W, packed, wbytes, in, s));
+  HIPCHK(c, hipMemcpyAsync(e.W, packed, wbytes, st.kind_in(), s));
   CHK(prepare(e, false));
   RUN(odb_gather(dimg, dl, dmask, nullptr, 0, (int)n, (int)n, (int)img_bytes, e.xb, e.lb, e.mb, s));
   CHK(forward(e, (int)n, true, e.st));
   CHK(backward(e, (int)n));
   RUN(odb_loss_out(e.st, (int)n, lp, s));
-  HIPCHK(c, hipMemcpyAsync(grad, e.G, wbytes, out, s));
-  HIPCHK(c, hipMemcpyAsync(loss, lp, sizeof(float), out, s));
+  HIPCHK(c, hipMemcpyAsync(grad, e.G, wbytes, st.kind_out(), s));
+  HIPCHK(c, hipMemcpyAsync(loss, lp, sizeof(float), st.kind_out(), s));
   // the forward advanced the copy's moving statistics and nothing else of it
-  if (moving_out) HIPCHK(c, hipMemcpyAsync(moving_out, e.W, wbytes, out, s));
-  return finish(c, dev);
+  if (moving_out) HIPCHK(c, hipMemcpyAsync(moving_out, e.W, wbytes, st.kind_out(), s));
+  return finish(c, st.dev);
 }
 
 int mmla_od_finetune(mmla_ctx* c, const float* packed, int64_t n_floats, const uint8_t* img_u8,
@@ -457,144 +416,62 @@ int mmla_od_finetune(mmla_ctx* c, const float* packed, int64_t n_floats, const u
                      float* packed_out, float* history, int32_t* epochs_run, uint32_t flags) {
   if (!c) return MMLA_E_INVALID;
   CHK(check_common(c, "od_finetune", n_floats, h, w, class_w));
-  if (batch < 1) return fail(c, MMLA_E_INVALID, "od_finetune: batch %d < 1", batch);
-  if (n_train < 1) return fail(c, MMLA_E_INVALID, "od_finetune: n_train %lld < 1", (long long)n_train);
-  if (n_val < 0 || epochs < 0 || patience < 0 || n_train > (1 << 24) || n_val > (1 << 24))
-    return fail(c, MMLA_E_INVALID, "od_finetune: bad sizes (n_val %lld, epochs %d, patience %d)", (long long)n_val,
-                epochs, patience);
-  if (std::min<int64_t>(batch, n_train) > MMLA_OD_TRAIN_MAX_BATCH)
-    return fail(c, MMLA_E_INVALID, "od_finetune: a batch of more than %d images", MMLA_OD_TRAIN_MAX_BATCH);
-  if (!packed || !img_u8 || !labels || !packed_out || !epochs_run ||
-      (epochs > 0 && (!perm || !history || !lr)) || (n_val > 0 && (!val_img || !val_labels)))
-    return fail(c, MMLA_E_INVALID, "od_finetune: null pointer");
+  FitCall a = fit_call("od_finetune", packed, n_floats, img_u8, labels, n_train, val_img, val_labels, n_val, epochs,
+                       batch, perm, packed_out, history, flags);
+  a.unit = "images";
+  a.slot = S_ODFT;
+  a.max_batch = MMLA_OD_TRAIN_MAX_BATCH;
+  a.val_chunk = 16;
+  a.hist_w = 5;   // ... and the epoch's lr
+  a.callbacks = FIT_STOP;
+  a.n_classes = 2;
+  a.label_set = kLabelSet;
+  a.row_bytes = (size_t)h * w * 3;
+  a.patience = patience;
+  a.epochs_run = epochs_run;
+  // rows after an early stop
+  a.nan_fill = [](float* hist, size_t n, hipStream_t s) { return odb_fill(hist, (int64_t)n, __builtin_nanf(""), s); };
+  CHK(fit_check(c, a));
+  if (epochs > 0 && !lr) return fail(c, MMLA_E_INVALID, "od_finetune: null pointer");
   for (int ep = 0; ep < epochs; ++ep)
     if (!std::isfinite(lr[ep]) || lr[ep] < 0.0f)
       return fail(c, MMLA_E_INVALID, "od_finetune: lr[%d] = %g is negative or not finite", ep, lr[ep]);
-  const bool dev = flags & MMLA_DEVICE_PTR;
-  if (!dev) {
-    CHK(check_labels(c, "labels", labels, n_train));
-    CHK(check_labels(c, "val_labels", val_labels, n_val));
-    std::vector<uint8_t> seen(n_train);
-    for (int ep = 0; ep < epochs; ++ep) {
-      std::fill(seen.begin(), seen.end(), 0);
-      const int32_t* p = perm + (size_t)ep * n_train;
-      for (int64_t i = 0; i < n_train; ++i) {
-        if (p[i] < 0 || p[i] >= n_train || seen[p[i]])
-          return fail(c, MMLA_E_INVALID, "od_finetune: perm row %d is not a permutation of 0..%lld", ep,
-                      (long long)(n_train - 1));
-        seen[p[i]] = 1;
-      }
-    }
-  }
-  HIPCHK(c, hipSetDevice(c->device));
+  Engine e = engine(c, a.cap(), h, w, class_w);
   hipStream_t s = c->stream;
-  Engine e;
-  e.c = c;
-  e.off = od_offsets();
-  e.cw[0] = class_w[0];
-  e.cw[1] = class_w[1];
-  set_dims(e, h, w);
-  const size_t wbytes = e.off.total * sizeof(float);
-  const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const hipMemcpyKind out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (epochs == 0) {   // the input blob, unchanged
-    if (!dev) {
-      if (packed_out != packed) std::memcpy(packed_out, packed, wbytes);
-      *epochs_run = 0;
-      return MMLA_OK;
-    }
-    if (packed_out != packed) HIPCHK(c, hipMemcpyAsync(packed_out, packed, wbytes, in, s));
-    HIPCHK(c, hipMemsetAsync(epochs_run, 0, sizeof(int32_t), s));
-    return finish(c, dev);
-  }
-  e.cap = (int)std::max<int64_t>(std::min<int64_t>(batch, n_train), std::min<int64_t>(n_val, 16));
-  const size_t img_bytes = (size_t)h * w * 3;
-  const uint8_t *dimg = img_u8, *dvimg = val_img, *dmask = drop_mask;
-  const int32_t *dl = labels, *dvl = val_labels, *dperm = perm;
-  float* dhist = history;
-  size_t total = 0;
-  uint8_t *simg = nullptr, *svimg = nullptr, *smask = nullptr;
-  int32_t *sl = nullptr, *svl = nullptr, *sperm = nullptr;
-  float *shist = nullptr, *dlr = nullptr;
-  for (int pass = 0; pass < 2; ++pass) {
-    void* p = nullptr;
-    if (pass) CHK(ws_get(c, S_ODFT, total, &p));
-    Carver cv{static_cast<char*>(p)};
-    carve(e, cv, true);
-    dlr = cv.take<float>(epochs);
-    if (!dev) {
-      simg = cv.take<uint8_t>((size_t)n_train * img_bytes);
-      sl = cv.take<int32_t>(n_train);
-      svimg = cv.take<uint8_t>((size_t)n_val * img_bytes);
-      svl = cv.take<int32_t>(n_val);
-      sperm = cv.take<int32_t>((size_t)epochs * n_train);
-      smask = drop_mask ? cv.take<uint8_t>((size_t)epochs * n_train * ODB_HEAD_D) : nullptr;
-      shist = cv.take<float>((size_t)epochs * 5);
-    }
-    total = cv.total;
-  }
-  HIPCHK(c, hipMemcpyAsync(dlr, lr, (size_t)epochs * sizeof(float), hipMemcpyHostToDevice, s));
-  if (!dev) {
-    HIPCHK(c, hipMemcpyAsync(simg, img_u8, (size_t)n_train * img_bytes, in, s));
-    HIPCHK(c, hipMemcpyAsync(sl, labels, (size_t)n_train * sizeof(int32_t), in, s));
-    if (n_val > 0) {
-      HIPCHK(c, hipMemcpyAsync(svimg, val_img, (size_t)n_val * img_bytes, in, s));
-      HIPCHK(c, hipMemcpyAsync(svl, val_labels, (size_t)n_val * sizeof(int32_t), in, s));
-    }
-    HIPCHK(c, hipMemcpyAsync(sperm, perm, (size_t)epochs * n_train * sizeof(int32_t), in, s));
-    if (drop_mask) HIPCHK(c, hipMemcpyAsync(smask, drop_mask, (size_t)epochs * n_train * ODB_HEAD_D, in, s));
-    dimg = simg;
-    dl = sl;
-    dvimg = svimg;
-    dvl = svl;
-    dperm = sperm;
-    dmask = smask;
-    dhist = shist;
-  }
-  HIPCHK(c, hipMemcpyAsync(e.W, packed, wbytes, in, s));
-  CHK(prepare(e, true));
-  RUN(odb_fill(dhist, (int64_t)epochs * 5, __builtin_nanf(""), s));   // rows after an early stop
-  const bool stopping = patience > 0 && n_val > 0;
-  float best = INFINITY;
-  int wait = 0, ran = 0;
-  for (int ep = 0; ep < epochs; ++ep) {
-    const int32_t* order = dperm + (size_t)ep * n_train;
-    const uint8_t* mask = dmask ? dmask + (size_t)ep * n_train * ODB_HEAD_D : nullptr;
-    for (int64_t b0 = 0; b0 < n_train; b0 += batch) {
-      const int nb = (int)std::min<int64_t>(batch, n_train - b0);
-      RUN(odb_gather(dimg, dl, mask, order, (int)b0, nb, (int)n_train, (int)img_bytes, e.xb, e.lb, e.mb, s));
-      CHK(forward(e, nb, true, e.st));
-      CHK(backward(e, nb));
-      RUN(sib_fold_batch(e.st, nb, s));
-      RUN(odb_adadelta(e.W, e.acc_g, e.acc_d, e.G, e.trainable, (int64_t)e.off.total, dlr, ep, s));
-    }
-    for (int64_t v0 = 0; v0 < n_val; v0 += e.cap) {
-      const int nb = (int)std::min<int64_t>(e.cap, n_val - v0);
-      RUN(odb_gather(dvimg, dvl, nullptr, nullptr, (int)v0, nb, (int)n_val, (int)img_bytes, e.xb, e.lb, e.mb, s));
-      CHK(forward(e, nb, false, e.st + 5));
-    }
-    RUN(odb_end_epoch(e.st, (int)n_train, (int)n_val, dlr, ep, dhist + (size_t)ep * 5, s));
-    ran = ep + 1;
-    if (!stopping) continue;
-    // EarlyStopping(monitor='val_loss', patience): one row read back per epoch
-    float row[5];
-    HIPCHK(c, hipMemcpyAsync(row, dhist + (size_t)ep * 5, sizeof(row), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (row[2] < best) {
-      best = row[2];
-      wait = 0;
-    } else if (++wait >= patience) {
-      break;
-    }
-  }
-  HIPCHK(c, hipMemcpyAsync(packed_out, e.W, wbytes, out, s));
-  if (dev) {
-    HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(epochs_run), ran, 1, s));
-  } else {
-    HIPCHK(c, hipMemcpyAsync(history, dhist, (size_t)epochs * 5 * sizeof(float), out, s));
-    *epochs_run = ran;
-  }
-  return finish(c, dev);
+  const int img_bytes = (int)a.row_bytes, n = (int)n_train, nv = (int)n_val;
+  const float* dlr = nullptr;
+  const uint8_t* dmask = nullptr;   // [epochs, n_train, 512], indexed by epoch and sample
+  return fit(
+      c, a,
+      [&](Carver& cv, Stager& st, FitBufs& d) -> int {
+        carve(e, cv, true);
+        d.blob = e.W;
+        CHK(st.up(cv, lr, (size_t)epochs, &dlr));   // a host array in either mode
+        CHK(d.stage_in(a, cv, st));
+        CHK(st.in(cv, drop_mask, (size_t)epochs * n_train * ODB_HEAD_D, &dmask));
+        d.stage_out(a, cv, st);
+        return MMLA_OK;
+      },
+      [&]() -> int { return prepare(e, true); },
+      [&](const FitBufs& d, int ep, const int32_t* order, int b0, int nb) -> int {
+        const uint8_t* mask = dmask ? dmask + (size_t)ep * n_train * ODB_HEAD_D : nullptr;
+        RUN(odb_gather(static_cast<const uint8_t*>(d.x), d.labels, mask, order, b0, nb, n, img_bytes, e.xb, e.lb, e.mb,
+                       s));
+        CHK(forward(e, nb, true, e.st));
+        CHK(backward(e, nb));
+        RUN(sib_fold_batch(e.st, nb, s));
+        RUN(odb_adadelta(e.W, e.acc_g, e.acc_d, e.G, e.trainable, (int64_t)e.off.total, dlr, ep, s));
+        return MMLA_OK;
+      },
+      [&](const FitBufs& d, int v0, int nb) -> int {
+        RUN(odb_gather(static_cast<const uint8_t*>(d.val_x), d.val_labels, nullptr, nullptr, v0, nb, nv, img_bytes,
+                       e.xb, e.lb, e.mb, s));
+        return forward(e, nb, false, e.st + 5);
+      },
+      [&](int ep, float* row) -> int {
+        RUN(odb_end_epoch(e.st, n, nv, dlr, ep, row, s));
+        return MMLA_OK;
+      });
 }
 
 }  // extern "C"

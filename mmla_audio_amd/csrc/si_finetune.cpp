@@ -4,12 +4,12 @@
 // Which kernel of si_bwd.hip runs which layer, forward and backward, over a copy of the packed SI blob
 // in workspace slot S_FT; the context's loaded model is not touched.  A training step is a fixed
 // sequence of launches on the context's stream with no host synchronisation: the loss bookkeeping
-// lives in device memory and the history is read once at the end of the fit.
+// lives in device memory and the history is read once at the end of the fit.  The fit itself -- checks,
+// staging, the epoch loop, the callbacks -- is fit_common.h's driver; this file gives it the steps.
 #include <algorithm>
 #include <cmath>
-#include <cstring>
-#include <vector>
 
+#include "fit_common.h"
 #include "internal.h"
 #include "si_base.h"
 #include "si_bwd.h"
@@ -102,18 +102,7 @@ struct Engine {
 };
 constexpr int kBnSites = 19;   // bn_in, bn_mid of the nine units, then the final one
 
-// carve: first pass (base == nullptr) only measures
-struct Carver {
-  char* base;
-  size_t total = 0;
-  template <typename T>
-  T* take(size_t count) {
-    const size_t at = total;
-    total += (count * sizeof(T) + 255) & ~(size_t)255;
-    return base ? reinterpret_cast<T*>(base + at) : nullptr;
-  }
-};
-
+// the engine's buffers; the pass on a null base only measures (fit_common.h)
 void carve(Engine& e, Carver& cv, bool train) {
   const size_t B = e.cap, n = e.off.total;
   e.W = cv.take<float>(n);
@@ -162,14 +151,7 @@ void carve(Engine& e, Carver& cv, bool train) {
     e.dbnoise = cv.take<float>(SBB_MAX_C);
   }
   if (cv.base) {
-    for (int d = 0; d < 2; ++d) {
-      l.wk[d] = e.W + e.off.lk[d];
-      l.wr[d] = e.W + e.off.lr[d];
-      l.bias[d] = e.W + e.off.lb[d];
-      l.dwk[d] = e.G + e.off.lk[d];
-      l.dwr[d] = e.G + e.off.lr[d];
-      l.dbias[d] = e.G + e.off.lb[d];
-    }
+    wire_lstm(l, e.off, e.W, e.G);
     l.seq = e.seq;
     l.T = SIB_LSTM_T;
     l.emb = e.emb;
@@ -338,42 +320,128 @@ int check_common(mmla_ctx* c, const char* who, int64_t n_floats, int32_t K,
   return MMLA_OK;
 }
 
-// e.mask: trainable = everything but moving_mean / moving_variance
-int mark_trainable(Engine& e) {
-  hipStream_t s = e.c->stream;
-  HIPCHK(e.c, hipMemsetAsync(e.mask, 1, e.off.total, s));
-  auto frozen = [&](size_t bn, int ch) { return hipMemsetAsync(e.mask + bn + 2 * ch, 0, 2 * (size_t)ch, s); };
-  for (int i = 0; i < 9; ++i) {
-    HIPCHK(e.c, frozen(e.off.u[i].bn_in, e.off.u[i].cin));
-    HIPCHK(e.c, frozen(e.off.u[i].bn_mid, e.off.u[i].cout));
+// sample ids are rows of the training set: none negative (host pointers)
+int check_ids(mmla_ctx* c, const char* who, const int32_t* ids, int64_t n) {
+  for (int64_t i = 0; ids && i < n; ++i)
+    if (ids[i] < 0) return fail(c, MMLA_E_INVALID, "%s: sample_ids[%lld] = %d < 0", who, (long long)i, ids[i]);
+  return MMLA_OK;
+}
+
+// loss and gradient of the B windows in xb / lb: the data term's sums -> st, R -> st + 2, the gradient -> G
+int train_pass(Engine& e, int B) {
+  CHK(forward(e, B, e.st, true, (float)B));
+  CHK(l2_term(e));
+  return backward(e, B);
+}
+
+// mmla_si_loss_grad and, with `base`, mmla_si_base_loss_grad
+int loss_grad(mmla_ctx* c, const char* who, bool base, int k_max, const float* packed, int64_t n_floats, int32_t K,
+              const float* x, const int32_t* labels, int64_t n, int64_t drop_seed, int32_t epoch,
+              const int32_t* sample_ids, float* loss, float* grad, float* moving_out, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  CHK(check_common(c, who, n_floats, K, k_max));
+  if (n < 1 || n > kMaxPass) return fail(c, MMLA_E_INVALID, "%s: n %lld outside [1, %d]", who, (long long)n, kMaxPass);
+  if (epoch < 0) return fail(c, MMLA_E_INVALID, "%s: epoch %d < 0", who, epoch);
+  if (!packed || !x || !labels || !loss || !grad) return fail(c, MMLA_E_INVALID, "%s: null pointer", who);
+  Stager st{c, (flags & MMLA_DEVICE_PTR) != 0};
+  if (!st.dev) {
+    CHK(check_labels(c, "labels", labels, n, K));
+    CHK(check_ids(c, who, sample_ids, n));
   }
-  HIPCHK(e.c, frozen(e.off.fbn, 128));
-  return MMLA_OK;
-}
-
-// perm [epochs, n]: every row a permutation of 0..n-1
-int check_perm(mmla_ctx* c, const char* who, const int32_t* perm, int epochs, int64_t n) {
-  std::vector<uint8_t> seen(n);
-  for (int ep = 0; ep < epochs; ++ep) {
-    std::fill(seen.begin(), seen.end(), 0);
-    const int32_t* p = perm + (size_t)ep * n;
-    for (int64_t i = 0; i < n; ++i) {
-      if (p[i] < 0 || p[i] >= n || seen[p[i]])
-        return fail(c, MMLA_E_INVALID, "%s: perm row %d is not a permutation of 0..%lld", who, ep,
-                    (long long)(n - 1));
-      seen[p[i]] = 1;
-    }
+  HIPCHK(c, hipSetDevice(c->device));
+  Engine e;
+  e.c = c;
+  e.K = K;
+  e.cap = (int)n;
+  e.base = base;
+  e.off = si_offsets(K);
+  float* lp = nullptr;
+  int32_t* ids = nullptr;
+  CHK(carve_slot(c, S_FT, [&](Carver& cv) -> int {
+    carve(e, cv, false);
+    lp = cv.take<float>(2);
+    if (base) ids = cv.take<int32_t>(n);
+    return MMLA_OK;
+  }));
+  hipStream_t s = c->stream;
+  const size_t wbytes = e.off.total * sizeof(float), xbytes = (size_t)n * SI_T * SI_D * sizeof(float);
+  HIPCHK(c, hipMemcpyAsync(e.W, packed, wbytes, st.kind_in(), s));
+  HIPCHK(c, hipMemcpyAsync(e.xb, x, xbytes, st.kind_in(), s));
+  HIPCHK(c, hipMemcpyAsync(e.lb, labels, (size_t)n * sizeof(int32_t), st.kind_in(), s));
+  if (base) {
+    if (sample_ids) HIPCHK(c, hipMemcpyAsync(ids, sample_ids, (size_t)n * sizeof(int32_t), st.kind_in(), s));
+    HIPCHK(c, sbb_ids(sample_ids ? ids : nullptr, nullptr, 0, (int)n, (int)n, e.sid, s));
+    e.drop = SbbDrop{(uint64_t)drop_seed, (uint32_t)epoch, e.sid};
   }
-  return MMLA_OK;
+  HIPCHK(c, hipMemsetAsync(e.G, 0, wbytes, s));   // the moving-statistics slots stay 0
+  HIPCHK(c, hipMemsetAsync(e.st, 0, SIB_ST * sizeof(double), s));
+  CHK(train_pass(e, (int)n));
+  HIPCHK(c, sib_loss_pair(e.st, (int)n, lp, s));
+  HIPCHK(c, hipMemcpyAsync(grad, e.G, wbytes, st.kind_out(), s));
+  HIPCHK(c, hipMemcpyAsync(loss, lp, 2 * sizeof(float), st.kind_out(), s));
+  // a base model's forward advanced the copy's moving statistics and nothing else of it
+  if (moving_out) HIPCHK(c, hipMemcpyAsync(moving_out, e.W, wbytes, st.kind_out(), s));
+  return finish(c, st.dev);
 }
 
-int check_labels(mmla_ctx* c, const char* what, const int32_t* l, int64_t n, int K) {
-  for (int64_t i = 0; i < n; ++i)
-    if (l[i] < 0 || l[i] >= K)
-      return fail(c, MMLA_E_INVALID, "%s[%lld] = %d outside [0, %d)", what, (long long)i, l[i], K);
-  return MMLA_OK;
+// mmla_si_finetune and, with `base`, mmla_si_base_train: what fit_common.h's driver runs per step
+int si_fit(mmla_ctx* c, FitCall a, bool base, int k_max, float lr, int64_t drop_seed) {
+  if (!c) return MMLA_E_INVALID;
+  CHK(check_common(c, a.who, (int64_t)a.n_floats, a.n_classes, k_max));
+  a.unit = "windows";
+  a.slot = S_FT;
+  a.max_batch = kMaxPass;
+  a.val_chunk = 64;
+  a.hist_w = 4;
+  a.row_bytes = (size_t)SI_T * SI_D * sizeof(float);
+  CHK(fit_check(c, a));
+  if (base && (!(lr >= 0.0f) || !std::isfinite(lr)))
+    return fail(c, MMLA_E_INVALID, "%s: lr %g is negative or not finite", a.who, lr);
+  Engine e;
+  e.c = c;
+  e.K = a.n_classes;
+  e.base = base;
+  e.off = si_offsets(e.K);
+  e.cap = a.cap();
+  hipStream_t s = c->stream;
+  const size_t wbytes = e.off.total * sizeof(float);
+  const int row = SI_T * SI_D, n = (int)a.n_train, nv = (int)a.n_val;
+  return fit(
+      c, a,
+      [&](Carver& cv, Stager& st, FitBufs& d) -> int {
+        carve(e, cv, true);
+        d.blob = e.W;
+        CHK(d.stage_in(a, cv, st));
+        d.stage_out(a, cv, st);
+        return MMLA_OK;
+      },
+      [&]() -> int {
+        HIPCHK(c, hipMemsetAsync(e.G, 0, wbytes, s));     // the moving-statistics slots stay 0
+        HIPCHK(c, hipMemsetAsync(e.rms, 0, wbytes, s));   // a new optimiser: every accumulator from 0
+        HIPCHK(c, hipMemsetAsync(e.st, 0, SIB_ST * sizeof(double), s));
+        CHK(mark_trainable(c, e.mask, e.off));
+        return freeze_bn(c, e.mask, e.off.fbn, 128);
+      },
+      [&](const FitBufs& d, int ep, const int32_t* order, int b0, int nb) -> int {
+        HIPCHK(c, sib_gather(static_cast<const float*>(d.x), d.labels, order, b0, nb, n, row, e.xb, e.lb, s));
+        if (base) {
+          HIPCHK(c, sbb_ids(nullptr, order, b0, nb, n, e.sid, s));
+          e.drop = SbbDrop{(uint64_t)drop_seed, (uint32_t)ep, e.sid};
+        }
+        CHK(train_pass(e, nb));
+        HIPCHK(c, sib_fold_batch(e.st, nb, s));
+        HIPCHK(c, sib_rmsprop(e.W, e.rms, e.G, e.mask, (int64_t)e.off.total, lr, s));
+        return b0 + nb == n ? l2_term(e) : MMLA_OK;   // R of the epoch's last weights, for its history row
+      },
+      [&](const FitBufs& d, int v0, int nb) -> int {
+        HIPCHK(c, sib_gather(static_cast<const float*>(d.val_x), d.val_labels, nullptr, v0, nb, nv, row, e.xb, e.lb, s));
+        return forward(e, nb, e.st + 5, false, 1.0f);
+      },
+      [&](int, float* hrow) -> int {
+        HIPCHK(c, sib_end_epoch(e.st, n, nv, hrow, s));
+        return MMLA_OK;
+      });
 }
-
 }  // namespace
 }  // namespace mmla
 
@@ -386,151 +454,18 @@ extern "C" {
 
 int mmla_si_loss_grad(mmla_ctx* c, const float* packed, int64_t n_floats, int32_t n_classes, const float* x,
                       const int32_t* labels, int64_t n, float* loss, float* grad, uint32_t flags) {
-  if (!c) return MMLA_E_INVALID;
-  CHK(check_common(c, "si_loss_grad", n_floats, n_classes));
-  if (n < 1 || n > kMaxPass)
-    return fail(c, MMLA_E_INVALID, "si_loss_grad: n %lld outside [1, %d]", (long long)n, kMaxPass);
-  if (!packed || !x || !labels || !loss || !grad) return fail(c, MMLA_E_INVALID, "si_loss_grad: null pointer");
-  const bool dev = flags & MMLA_DEVICE_PTR;
-  if (!dev) CHK(check_labels(c, "labels", labels, n, n_classes));
-  HIPCHK(c, hipSetDevice(c->device));
-  Engine e;
-  e.c = c;
-  e.K = n_classes;
-  e.cap = (int)n;
-  e.off = si_offsets(n_classes);
-  Carver cv{nullptr};
-  carve(e, cv, false);
-  float* lp = cv.take<float>(2);
-  void* p = nullptr;
-  CHK(ws_get(c, S_FT, cv.total, &p));
-  cv = Carver{static_cast<char*>(p)};
-  carve(e, cv, false);
-  lp = cv.take<float>(2);
-  hipStream_t s = c->stream;
-  const size_t wbytes = e.off.total * sizeof(float), xbytes = (size_t)n * SI_T * SI_D * sizeof(float);
-  const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  HIPCHK(c, hipMemcpyAsync(e.W, packed, wbytes, in, s));
-  HIPCHK(c, hipMemcpyAsync(e.xb, x, xbytes, in, s));
-  HIPCHK(c, hipMemcpyAsync(e.lb, labels, (size_t)n * sizeof(int32_t), in, s));
-  HIPCHK(c, hipMemsetAsync(e.G, 0, wbytes, s));   // the moving-statistics slots stay 0
-  HIPCHK(c, hipMemsetAsync(e.st, 0, SIB_ST * sizeof(double), s));
-  CHK(forward(e, (int)n, e.st, true, (float)n));
-  CHK(l2_term(e));
-  CHK(backward(e, (int)n));
-  RUN(sib_loss_pair(e.st, (int)n, lp, s));
-  const hipMemcpyKind out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  HIPCHK(c, hipMemcpyAsync(grad, e.G, wbytes, out, s));
-  HIPCHK(c, hipMemcpyAsync(loss, lp, 2 * sizeof(float), out, s));
-  return finish(c, dev);
+  return loss_grad(c, "si_loss_grad", false, MMLA_SI_TRAIN_MAX_CLASSES, packed, n_floats, n_classes, x, labels, n, 0,
+                   0, nullptr, loss, grad, nullptr, flags);
 }
 
 int mmla_si_finetune(mmla_ctx* c, const float* packed, int64_t n_floats, int32_t n_classes, const float* x,
                      const int32_t* labels, int64_t n_train, const float* val_x, const int32_t* val_labels,
                      int64_t n_val, int32_t epochs, int32_t batch, float lr, const int32_t* perm,
                      float* packed_out, float* history, uint32_t flags) {
-  if (!c) return MMLA_E_INVALID;
-  CHK(check_common(c, "si_finetune", n_floats, n_classes));
-  if (batch < 1) return fail(c, MMLA_E_INVALID, "si_finetune: batch %d < 1", batch);
-  if (n_train < 1) return fail(c, MMLA_E_INVALID, "si_finetune: n_train %lld < 1", (long long)n_train);
-  if (n_val < 0 || epochs < 0 || n_train > (1 << 24) || n_val > (1 << 24))
-    return fail(c, MMLA_E_INVALID, "si_finetune: bad sizes (n_val %lld, epochs %d)", (long long)n_val, epochs);
-  if (std::min<int64_t>(batch, n_train) > kMaxPass)
-    return fail(c, MMLA_E_INVALID, "si_finetune: a batch of more than %d windows", kMaxPass);
-  if (!packed || !x || !labels || !packed_out || (epochs > 0 && (!perm || !history)) ||
-      (n_val > 0 && (!val_x || !val_labels)))
-    return fail(c, MMLA_E_INVALID, "si_finetune: null pointer");
-  const bool dev = flags & MMLA_DEVICE_PTR;
-  const int K = n_classes;
-  if (!dev) {
-    CHK(check_labels(c, "labels", labels, n_train, K));
-    CHK(check_labels(c, "val_labels", val_labels, n_val, K));
-    CHK(check_perm(c, "si_finetune", perm, epochs, n_train));
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  Engine e;
-  e.c = c;
-  e.K = K;
-  e.off = si_offsets(K);
-  const size_t wbytes = e.off.total * sizeof(float);
-  const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const hipMemcpyKind out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (epochs == 0) {   // the input blob, unchanged
-    if (packed_out == packed) return MMLA_OK;
-    if (!dev) {
-      std::memcpy(packed_out, packed, wbytes);
-      return MMLA_OK;
-    }
-    HIPCHK(c, hipMemcpyAsync(packed_out, packed, wbytes, in, s));
-    return finish(c, dev);
-  }
-  e.cap = (int)std::max<int64_t>(std::min<int64_t>(batch, n_train), std::min<int64_t>(n_val, 64));
-  const size_t row = (size_t)SI_T * SI_D;
-  const float *dx = x, *dvx = val_x;
-  const int32_t *dl = labels, *dvl = val_labels, *dperm = perm;
-  float* dhist = history;
-  // measure, allocate, carve
-  size_t total = 0;
-  float *sx = nullptr, *svx = nullptr, *shist = nullptr;
-  int32_t *sl = nullptr, *svl = nullptr, *sperm = nullptr;
-  for (int pass = 0; pass < 2; ++pass) {
-    void* p = nullptr;
-    if (pass) CHK(ws_get(c, S_FT, total, &p));
-    Carver cv{static_cast<char*>(p)};
-    carve(e, cv, true);
-    if (!dev) {
-      sx = cv.take<float>((size_t)n_train * row);
-      sl = cv.take<int32_t>(n_train);
-      svx = cv.take<float>((size_t)n_val * row);
-      svl = cv.take<int32_t>(n_val);
-      sperm = cv.take<int32_t>((size_t)epochs * n_train);
-      shist = cv.take<float>((size_t)epochs * 4);
-    }
-    total = cv.total;
-  }
-  if (!dev) {
-    HIPCHK(c, hipMemcpyAsync(sx, x, (size_t)n_train * row * sizeof(float), in, s));
-    HIPCHK(c, hipMemcpyAsync(sl, labels, (size_t)n_train * sizeof(int32_t), in, s));
-    if (n_val > 0) {
-      HIPCHK(c, hipMemcpyAsync(svx, val_x, (size_t)n_val * row * sizeof(float), in, s));
-      HIPCHK(c, hipMemcpyAsync(svl, val_labels, (size_t)n_val * sizeof(int32_t), in, s));
-    }
-    HIPCHK(c, hipMemcpyAsync(sperm, perm, (size_t)epochs * n_train * sizeof(int32_t), in, s));
-    dx = sx;
-    dl = sl;
-    dvx = svx;
-    dvl = svl;
-    dperm = sperm;
-    dhist = shist;
-  }
-  HIPCHK(c, hipMemcpyAsync(e.W, packed, wbytes, in, s));
-  HIPCHK(c, hipMemsetAsync(e.G, 0, wbytes, s));     // the moving-statistics slots stay 0
-  HIPCHK(c, hipMemsetAsync(e.rms, 0, wbytes, s));   // a new optimiser: every accumulator from 0
-  HIPCHK(c, hipMemsetAsync(e.st, 0, SIB_ST * sizeof(double), s));
-  CHK(mark_trainable(e));
-  for (int ep = 0; ep < epochs; ++ep) {
-    const int32_t* order = dperm + (size_t)ep * n_train;
-    for (int64_t b0 = 0; b0 < n_train; b0 += batch) {
-      const int nb = (int)std::min<int64_t>(batch, n_train - b0);
-      RUN(sib_gather(dx, dl, order, (int)b0, nb, (int)n_train, (int)row, e.xb, e.lb, s));
-      CHK(forward(e, nb, e.st, true, (float)nb));
-      CHK(l2_term(e));
-      CHK(backward(e, nb));
-      RUN(sib_fold_batch(e.st, nb, s));
-      RUN(sib_rmsprop(e.W, e.rms, e.G, e.mask, (int64_t)e.off.total, lr, s));
-    }
-    CHK(l2_term(e));
-    for (int64_t v0 = 0; v0 < n_val; v0 += e.cap) {
-      const int nb = (int)std::min<int64_t>(e.cap, n_val - v0);
-      RUN(sib_gather(dvx, dvl, nullptr, (int)v0, nb, (int)n_val, (int)row, e.xb, e.lb, s));
-      CHK(forward(e, nb, e.st + 5, false, 1.0f));
-    }
-    RUN(sib_end_epoch(e.st, (int)n_train, (int)n_val, dhist + (size_t)ep * 4, s));
-  }
-  HIPCHK(c, hipMemcpyAsync(packed_out, e.W, wbytes, out, s));
-  if (!dev) HIPCHK(c, hipMemcpyAsync(history, dhist, (size_t)epochs * 4 * sizeof(float), out, s));
-  return finish(c, dev);
+  FitCall a = fit_call("si_finetune", packed, n_floats, x, labels, n_train, val_x, val_labels, n_val, epochs, batch,
+                       perm, packed_out, history, flags);
+  a.n_classes = n_classes;
+  return si_fit(c, a, false, MMLA_SI_TRAIN_MAX_CLASSES, lr, 0);
 }
 
 int mmla_si_base_drop_mask(mmla_ctx* c, int64_t drop_seed, int32_t epoch, const int32_t* sample_ids, int64_t n,
@@ -539,101 +474,34 @@ int mmla_si_base_drop_mask(mmla_ctx* c, int64_t drop_seed, int32_t epoch, const 
   if (n < 1 || n > (1 << 20)) return fail(c, MMLA_E_INVALID, "si_base_drop_mask: n %lld outside [1, 2^20]", (long long)n);
   if (epoch < 0) return fail(c, MMLA_E_INVALID, "si_base_drop_mask: epoch %d < 0", epoch);
   if (!mask_a || !mask_b) return fail(c, MMLA_E_INVALID, "si_base_drop_mask: null pointer");
-  const bool dev = flags & MMLA_DEVICE_PTR;
-  if (!dev && sample_ids)
-    for (int64_t i = 0; i < n; ++i)
-      if (sample_ids[i] < 0)
-        return fail(c, MMLA_E_INVALID, "si_base_drop_mask: sample_ids[%lld] = %d < 0", (long long)i, sample_ids[i]);
+  Stager st{c, (flags & MMLA_DEVICE_PTR) != 0};
+  if (!st.dev) CHK(check_ids(c, "si_base_drop_mask", sample_ids, n));
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
-  int32_t *sid = nullptr, *ids = nullptr;
-  uint8_t *da = mask_a, *db = mask_b;
-  size_t total = 0;
-  for (int pass = 0; pass < 2; ++pass) {
-    void* p = nullptr;
-    if (pass) CHK(ws_get(c, S_FT, total, &p));
-    Carver cv{static_cast<char*>(p)};
+  int32_t* sid = nullptr;
+  const int32_t* dids = nullptr;
+  uint8_t *da = nullptr, *db = nullptr;
+  CHK(carve_slot(c, S_FT, [&](Carver& cv) -> int {
     sid = cv.take<int32_t>(n);
-    if (!dev) {
-      ids = cv.take<int32_t>(n);
-      da = cv.take<uint8_t>((size_t)n * SBB_MAP);
-      db = cv.take<uint8_t>((size_t)n * SBB_EMB);
-    }
-    total = cv.total;
-  }
-  const int32_t* dids = sample_ids;
-  if (!dev && sample_ids) {
-    HIPCHK(c, hipMemcpyAsync(ids, sample_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    dids = ids;
-  }
+    CHK(st.in(cv, sample_ids, (size_t)n, &dids));
+    if (!st.dev && !sample_ids) cv.take<int32_t>(n);   // the ids' place, used or not
+    da = st.out(cv, mask_a, (size_t)n * SBB_MAP);
+    db = st.out(cv, mask_b, (size_t)n * SBB_EMB);
+    return MMLA_OK;
+  }));
   RUN(sbb_ids(dids, nullptr, 0, (int)n, (int)n, sid, s));
   RUN(sbb_drop_mask(SbbDrop{(uint64_t)drop_seed, (uint32_t)epoch, sid}, (int)n, da, db, s));
-  if (!dev) {
-    HIPCHK(c, hipMemcpyAsync(mask_a, da, (size_t)n * SBB_MAP, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(mask_b, db, (size_t)n * SBB_EMB, hipMemcpyDeviceToHost, s));
-  }
-  return finish(c, dev);
+  CHK(st.back(mask_a, da, (size_t)n * SBB_MAP));
+  CHK(st.back(mask_b, db, (size_t)n * SBB_EMB));
+  return finish(c, st.dev);
 }
 
 int mmla_si_base_loss_grad(mmla_ctx* c, const float* packed, int64_t n_floats, int32_t n_classes, const float* x,
                            const int32_t* labels, int64_t n, int64_t drop_seed, int32_t epoch,
                            const int32_t* sample_ids, float* loss, float* grad, float* moving_out,
                            uint32_t flags) {
-  if (!c) return MMLA_E_INVALID;
-  CHK(check_common(c, "si_base_loss_grad", n_floats, n_classes, MMLA_SI_BASE_MAX_CLASSES));
-  if (n < 1 || n > kMaxPass)
-    return fail(c, MMLA_E_INVALID, "si_base_loss_grad: n %lld outside [1, %d]", (long long)n, kMaxPass);
-  if (epoch < 0) return fail(c, MMLA_E_INVALID, "si_base_loss_grad: epoch %d < 0", epoch);
-  if (!packed || !x || !labels || !loss || !grad)
-    return fail(c, MMLA_E_INVALID, "si_base_loss_grad: null pointer");
-  const bool dev = flags & MMLA_DEVICE_PTR;
-  if (!dev) {
-    CHK(check_labels(c, "labels", labels, n, n_classes));
-    if (sample_ids)
-      for (int64_t i = 0; i < n; ++i)
-        if (sample_ids[i] < 0)
-          return fail(c, MMLA_E_INVALID, "si_base_loss_grad: sample_ids[%lld] = %d < 0", (long long)i,
-                      sample_ids[i]);
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  Engine e;
-  e.c = c;
-  e.K = n_classes;
-  e.cap = (int)n;
-  e.base = true;
-  e.off = si_offsets(n_classes);
-  float* lp = nullptr;
-  int32_t* ids = nullptr;
-  size_t total = 0;
-  for (int pass = 0; pass < 2; ++pass) {
-    void* p = nullptr;
-    if (pass) CHK(ws_get(c, S_FT, total, &p));
-    Carver cv{static_cast<char*>(p)};
-    carve(e, cv, false);
-    lp = cv.take<float>(2);
-    ids = cv.take<int32_t>(n);
-    total = cv.total;
-  }
-  hipStream_t s = c->stream;
-  const size_t wbytes = e.off.total * sizeof(float), xbytes = (size_t)n * SI_T * SI_D * sizeof(float);
-  const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const hipMemcpyKind out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  HIPCHK(c, hipMemcpyAsync(e.W, packed, wbytes, in, s));
-  HIPCHK(c, hipMemcpyAsync(e.xb, x, xbytes, in, s));
-  HIPCHK(c, hipMemcpyAsync(e.lb, labels, (size_t)n * sizeof(int32_t), in, s));
-  if (sample_ids) HIPCHK(c, hipMemcpyAsync(ids, sample_ids, (size_t)n * sizeof(int32_t), in, s));
-  RUN(sbb_ids(sample_ids ? ids : nullptr, nullptr, 0, (int)n, (int)n, e.sid, s));
-  e.drop = SbbDrop{(uint64_t)drop_seed, (uint32_t)epoch, e.sid};
-  HIPCHK(c, hipMemsetAsync(e.G, 0, wbytes, s));   // the moving-statistics slots stay 0
-  HIPCHK(c, hipMemsetAsync(e.st, 0, SIB_ST * sizeof(double), s));
-  CHK(forward(e, (int)n, e.st, true, (float)n));
-  CHK(l2_term(e));
-  CHK(backward(e, (int)n));
-  RUN(sib_loss_pair(e.st, (int)n, lp, s));
-  HIPCHK(c, hipMemcpyAsync(grad, e.G, wbytes, out, s));
-  HIPCHK(c, hipMemcpyAsync(loss, lp, 2 * sizeof(float), out, s));
-  if (moving_out) HIPCHK(c, hipMemcpyAsync(moving_out, e.W, wbytes, out, s));   // only the forward wrote W
-  return finish(c, dev);
+  return loss_grad(c, "si_base_loss_grad", true, MMLA_SI_BASE_MAX_CLASSES, packed, n_floats, n_classes, x, labels, n,
+                   drop_seed, epoch, sample_ids, loss, grad, moving_out, flags);
 }
 
 int mmla_si_base_train(mmla_ctx* c, const float* packed, int64_t n_floats, int32_t n_classes, const float* x,
@@ -642,156 +510,18 @@ int mmla_si_base_train(mmla_ctx* c, const float* packed, int64_t n_floats, int32
                        int64_t drop_seed, int32_t patience, int32_t ckpt_period, float* packed_out,
                        float* best_out, float* history, int32_t* epochs_run, int32_t* best_epoch,
                        uint32_t flags) {
-  if (!c) return MMLA_E_INVALID;
-  CHK(check_common(c, "si_base_train", n_floats, n_classes, MMLA_SI_BASE_MAX_CLASSES));
-  if (batch < 1) return fail(c, MMLA_E_INVALID, "si_base_train: batch %d < 1", batch);
-  if (n_train < 1) return fail(c, MMLA_E_INVALID, "si_base_train: n_train %lld < 1", (long long)n_train);
-  if (n_val < 0 || epochs < 0 || patience < 0 || ckpt_period < 0 || n_train > (1 << 24) || n_val > (1 << 24))
-    return fail(c, MMLA_E_INVALID, "si_base_train: bad sizes (n_val %lld, epochs %d, patience %d, ckpt_period %d)",
-                (long long)n_val, epochs, patience, ckpt_period);
-  if (std::min<int64_t>(batch, n_train) > kMaxPass)
-    return fail(c, MMLA_E_INVALID, "si_base_train: a batch of more than %d windows", kMaxPass);
-  if (!(lr >= 0.0f) || !std::isfinite(lr))
-    return fail(c, MMLA_E_INVALID, "si_base_train: lr %g is negative or not finite", lr);
-  const bool ckpt = ckpt_period > 0 && n_val > 0;
-  if (!packed || !x || !labels || !packed_out || !epochs_run || !best_epoch ||
-      (epochs > 0 && (!perm || !history)) || (n_val > 0 && (!val_x || !val_labels)) ||
-      (epochs > 0 && ckpt && !best_out))
-    return fail(c, MMLA_E_INVALID, "si_base_train: null pointer");
-  const bool dev = flags & MMLA_DEVICE_PTR;
-  const int K = n_classes;
-  if (!dev) {
-    CHK(check_labels(c, "labels", labels, n_train, K));
-    CHK(check_labels(c, "val_labels", val_labels, n_val, K));
-    CHK(check_perm(c, "si_base_train", perm, epochs, n_train));
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  Engine e;
-  e.c = c;
-  e.K = K;
-  e.base = true;
-  e.off = si_offsets(K);
-  const size_t wbytes = e.off.total * sizeof(float);
-  const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const hipMemcpyKind out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  int ran = 0, best_ep = -1;
-  auto report = [&]() -> int {   // epochs_run, best_epoch: host or device words like every other output
-    if (!dev) {
-      *epochs_run = ran;
-      *best_epoch = best_ep;
-      return MMLA_OK;
-    }
-    HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(epochs_run), ran, 1, s));
-    HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(best_epoch), best_ep, 1, s));
-    return MMLA_OK;
-  };
-  if (epochs == 0) {   // the input blob, unchanged
-    if (!dev) {
-      if (packed_out != packed) std::memcpy(packed_out, packed, wbytes);
-      return report();
-    }
-    if (packed_out != packed) HIPCHK(c, hipMemcpyAsync(packed_out, packed, wbytes, in, s));
-    CHK(report());
-    return finish(c, dev);
-  }
-  e.cap = (int)std::max<int64_t>(std::min<int64_t>(batch, n_train), std::min<int64_t>(n_val, 64));
-  const size_t row = (size_t)SI_T * SI_D;
-  const float *dx = x, *dvx = val_x;
-  const int32_t *dl = labels, *dvl = val_labels, *dperm = perm;
-  float *dhist = history, *dbest = best_out;
-  size_t total = 0;
-  float *sx = nullptr, *svx = nullptr, *shist = nullptr, *sbest = nullptr;
-  int32_t *sl = nullptr, *svl = nullptr, *sperm = nullptr;
-  for (int pass = 0; pass < 2; ++pass) {
-    void* p = nullptr;
-    if (pass) CHK(ws_get(c, S_FT, total, &p));
-    Carver cv{static_cast<char*>(p)};
-    carve(e, cv, true);
-    if (!dev) {
-      sx = cv.take<float>((size_t)n_train * row);
-      sl = cv.take<int32_t>(n_train);
-      svx = cv.take<float>((size_t)n_val * row);
-      svl = cv.take<int32_t>(n_val);
-      sperm = cv.take<int32_t>((size_t)epochs * n_train);
-      shist = cv.take<float>((size_t)epochs * 4);
-      sbest = ckpt ? cv.take<float>(e.off.total) : nullptr;
-    }
-    total = cv.total;
-  }
-  if (!dev) {
-    HIPCHK(c, hipMemcpyAsync(sx, x, (size_t)n_train * row * sizeof(float), in, s));
-    HIPCHK(c, hipMemcpyAsync(sl, labels, (size_t)n_train * sizeof(int32_t), in, s));
-    if (n_val > 0) {
-      HIPCHK(c, hipMemcpyAsync(svx, val_x, (size_t)n_val * row * sizeof(float), in, s));
-      HIPCHK(c, hipMemcpyAsync(svl, val_labels, (size_t)n_val * sizeof(int32_t), in, s));
-    }
-    HIPCHK(c, hipMemcpyAsync(sperm, perm, (size_t)epochs * n_train * sizeof(int32_t), in, s));
-    dx = sx;
-    dl = sl;
-    dvx = svx;
-    dvl = svl;
-    dperm = sperm;
-    dhist = shist;
-    dbest = sbest;
-  }
-  HIPCHK(c, hipMemcpyAsync(e.W, packed, wbytes, in, s));
-  HIPCHK(c, hipMemsetAsync(e.G, 0, wbytes, s));     // the moving-statistics slots stay 0
-  HIPCHK(c, hipMemsetAsync(e.rms, 0, wbytes, s));   // a new optimiser: every accumulator from 0
-  HIPCHK(c, hipMemsetAsync(e.st, 0, SIB_ST * sizeof(double), s));
-  CHK(mark_trainable(e));
-  HIPCHK(c, hipMemsetAsync(dhist, 0xff, (size_t)epochs * 4 * sizeof(float), s));   // NaN: rows after an early stop
-  const bool stopping = patience > 0 && n_val > 0;
-  float best_loss = INFINITY, best_acc = -INFINITY;
-  int wait = 0;
-  for (int ep = 0; ep < epochs; ++ep) {
-    const int32_t* order = dperm + (size_t)ep * n_train;
-    for (int64_t b0 = 0; b0 < n_train; b0 += batch) {
-      const int nb = (int)std::min<int64_t>(batch, n_train - b0);
-      RUN(sib_gather(dx, dl, order, (int)b0, nb, (int)n_train, (int)row, e.xb, e.lb, s));
-      RUN(sbb_ids(nullptr, order, (int)b0, nb, (int)n_train, e.sid, s));
-      e.drop = SbbDrop{(uint64_t)drop_seed, (uint32_t)ep, e.sid};
-      CHK(forward(e, nb, e.st, true, (float)nb));
-      CHK(l2_term(e));
-      CHK(backward(e, nb));
-      RUN(sib_fold_batch(e.st, nb, s));
-      RUN(sib_rmsprop(e.W, e.rms, e.G, e.mask, (int64_t)e.off.total, lr, s));
-    }
-    CHK(l2_term(e));
-    for (int64_t v0 = 0; v0 < n_val; v0 += e.cap) {
-      const int nb = (int)std::min<int64_t>(e.cap, n_val - v0);
-      RUN(sib_gather(dvx, dvl, nullptr, (int)v0, nb, (int)n_val, (int)row, e.xb, e.lb, s));
-      CHK(forward(e, nb, e.st + 5, false, 1.0f));
-    }
-    RUN(sib_end_epoch(e.st, (int)n_train, (int)n_val, dhist + (size_t)ep * 4, s));
-    ran = ep + 1;
-    if (!stopping && !ckpt) continue;
-    // the two Keras callbacks: one history row read back per epoch
-    float hrow[4];
-    HIPCHK(c, hipMemcpyAsync(hrow, dhist + (size_t)ep * 4, sizeof(hrow), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    // ModelCheckpoint(val_categorical_accuracy, save_best_only, mode 'max', period)
-    if (ckpt && (ep + 1) % ckpt_period == 0 && hrow[3] > best_acc) {
-      best_acc = hrow[3];
-      best_ep = ep;
-      HIPCHK(c, hipMemcpyAsync(dbest, e.W, wbytes, hipMemcpyDeviceToDevice, s));
-    }
-    // EarlyStopping(val_loss, patience)
-    if (!stopping) continue;
-    if (hrow[2] < best_loss) {
-      best_loss = hrow[2];
-      wait = 0;
-    } else if (++wait >= patience) {
-      break;
-    }
-  }
-  HIPCHK(c, hipMemcpyAsync(packed_out, e.W, wbytes, out, s));
-  if (!dev) {
-    HIPCHK(c, hipMemcpyAsync(history, dhist, (size_t)epochs * 4 * sizeof(float), out, s));
-    if (best_ep >= 0) HIPCHK(c, hipMemcpyAsync(best_out, dbest, wbytes, out, s));
-  }
-  CHK(report());
-  return finish(c, dev);
+  FitCall a = fit_call("si_base_train", packed, n_floats, x, labels, n_train, val_x, val_labels, n_val, epochs, batch,
+                       perm, packed_out, history, flags);
+  a.n_classes = n_classes;
+  a.callbacks = FIT_STOP | FIT_CKPT;
+  a.patience = patience;
+  a.ckpt_period = ckpt_period;
+  a.best_out = best_out;
+  a.epochs_run = epochs_run;
+  a.best_epoch = best_epoch;
+  // NaN: rows after an early stop
+  a.nan_fill = [](float* h, size_t n, hipStream_t s) { return hipMemsetAsync(h, 0xff, n * sizeof(float), s); };
+  return si_fit(c, a, true, MMLA_SI_BASE_MAX_CLASSES, lr, drop_seed);
 }
 
 }  // extern "C"
