@@ -99,8 +99,9 @@ int mmla_synchronize(mmla_ctx* ctx);
  * Arithmetic of the spatial convolutions (98 % of OD-NET FLOPs) and the BiLSTM:
  *   MMLA_PREC_F16X3 (default) error-compensated 3xFP16 on f16 MFMA: operands split hi + 2^-11 lo,
  *                   hi*hi + hi*lo + lo*hi accumulated in f32 (~22-bit products, f32 accumulation);
- *                   needs |activations| < 65504 in the fused res_blocks, < 4094 in the halo-tiled
- *                   convs (split x 2^4) and < 1023 in the LSTM (x 2^6).  Each weight tensor is split
+ *                   needs |activation| < 4094 (65504 / 2^4) at every conv operand -- the fused
+ *                   res_blocks and the halo-tiled convs alike split x 2^4 and compare the scaled
+ *                   value with 65504 -- and < 1023.5 at the LSTM input (x 2^6).  Each weight tensor is split
  *                   at its own power-of-two scale (2^8 for max |w| in [1/16, 255.9), else the one
  *                   putting max |w| in [2^13, 2^14)), so any finite checkpoint stays on this path;
  *                   a tensor holding inf / NaN makes that model run exact f32 (decided at
@@ -108,6 +109,13 @@ int mmla_synchronize(mmla_ctx* ctx);
  *                   a value outside its range.  Host-pointer calls then re-run the micro-batch in exact f32
  *                   (counted by mmla_range_check); device-pointer calls report MMLA_E_RANGE from
  *                   the next mmla_range_check / mmla_synchronize.
+ *                   A NaN or an inf in a caller's float input (an image of mmla_od_forward, the
+ *                   features of mmla_si_forward / mmla_si_embed) is out of range like any other
+ *                   value: the kernel that reads the input flags it.  A host-pointer call then
+ *                   returns what exact f32 gives -- NaN for that clip, as the float64 reference
+ *                   network does, and the other clips' exact-f32 results --; a device-pointer call
+ *                   reports MMLA_E_RANGE.  MMLA_PREC_F32 returns NaN for such a clip as well: its
+ *                   ReLU and max-pools keep NaN.
  *   MMLA_PREC_F32   exact f32 MFMA (v_mfma_f32_32x32x2_f32), 1/5.3 of the throughput.
  * The front-ends (OD f32, SI f64), the OD stem Conv2D(1x1), the OD Dense(2) head and the softmax /
  * sigmoid are the same in both modes; under MMLA_PREC_F16X3 the strided 1x1 shortcuts (OD blocks 1,
@@ -866,7 +874,11 @@ int mmla_profile_enable(mmla_ctx* ctx, int on);
 
 /* Layer-wise parity tap (tests): run OD-NET on host float NHWC x[n,128,151,3] up to `stage`
  * (0 = stem conv, 1..9 = after res_block 1..9 in NHWC, 10 = mean over H [n,19,128],
- * 11 = BiLSTM output [n,512]) and copy that tensor to host `out` (capacity out_floats). */
+ * 11 = BiLSTM output [n,512]) and copy that tensor to host `out` (capacity out_floats).
+ * Unguarded: it shows what the selected arithmetic computes.  Env MMLA_DEBUG_TRACE_GUARD=1 at
+ * mmla_create makes it a host-pointer micro-batch under the range guard (mmla_set_precision): an
+ * operand out of range in a kernel up to `stage` re-runs the trace in exact f32 and counts in
+ * mmla_range_check. */
 int mmla_debug_od_trace(mmla_ctx* ctx, const float* x, int64_t n, int stage, float* out,
                         int64_t out_floats);
 /* Debug (tests, tools): device address and size of internal workspace slot `slot` (0 and 0 when the

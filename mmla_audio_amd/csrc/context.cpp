@@ -194,6 +194,7 @@ static const EnvSwitch kEnvSwitches[] = {
     {"MMLA_NO_LSTM_SPLIT", &mmla_ctx::lstm_split, nullptr},
     {"MMLA_LSTM_SPLIT_MAX", nullptr, &mmla_ctx::lstm_split_max},
     {"MMLA_DEBUG_LSTM_SPIN", nullptr, &mmla_ctx::lstm_spin},
+    {"MMLA_DEBUG_TRACE_GUARD", nullptr, &mmla_ctx::debug_trace_guard},
     {"MMLA_NO_SIPAD", &mmla_ctx::si_pad_feat, nullptr},
     {"MMLA_NO_ODU", &mmla_ctx::odu, nullptr},
     {"MMLA_NO_ODW", &mmla_ctx::odw, nullptr},

@@ -29,7 +29,7 @@ MMLA_DEV float prologue(float v, float sc, float sh) {
   } else {
     v = fmaf(v, sc, sh);
     if constexpr (PRO == PRO_BN_ELU) return v > 0.0f ? v : expm1f(v);
-    return fmaxf(v, 0.0f);
+    return v > 0.0f ? v : v == v ? 0.0f : v;   // ReLU that keeps NaN (np.maximum; fmaxf drops it)
   }
 }
 
@@ -196,8 +196,10 @@ __global__ void __launch_bounds__(NT) conv_kernel(ConvArgs a) {
 #pragma unroll
           for (int dx = 0; dx < 2; ++dx) {
             const int hh = 2 * ho + dy, ww = 2 * wo + dx;
-            if (hh < a.hp && ww < a.wp)
-              m = fmaxf(m, a.res[(((int64_t)n * a.hp + hh) * a.wp + ww) * a.cout + co]);
+            if (hh < a.hp && ww < a.wp) {   // a max that keeps NaN, as the ReLU above
+              const float r = a.res[(((int64_t)n * a.hp + hh) * a.wp + ww) * a.cout + co];
+              m = r > m || r != r ? r : m;
+            }
           }
         v += m;
       }

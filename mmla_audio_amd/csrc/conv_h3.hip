@@ -341,7 +341,13 @@ __global__ void __launch_bounds__(NT, (conv_minw<KH, BN, TW, EPI, SHP::FIXED>())
           v.w = pro_fn<PRO>(v.w, sc.w, sh.w);
         }
       }
-      rbad |= !(fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))) < ACT_RANGE);
+      // raw operands (PRO_NONE) may be a caller's input (SI-NET's features enter through the stem conv):
+      // each value is compared on its own, because the quad's fmaxf drops one NaN among four
+      if constexpr (PRO == PRO_NONE)
+        rbad |= !(fabsf(v.x) < ACT_RANGE) || !(fabsf(v.y) < ACT_RANGE) || !(fabsf(v.z) < ACT_RANGE) ||
+                !(fabsf(v.w) < ACT_RANGE);
+      else
+        rbad |= !(fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))) < ACT_RANGE);
       v.x *= ACT_SCALE;
       v.y *= ACT_SCALE;
       v.z *= ACT_SCALE;

@@ -62,6 +62,16 @@ MMLA_DEV float amax4(float a, float b, float c, float d) {
 }
 MMLA_DEV float amax4(float r, float4 v) { return fmaxf(r, amax4(v.x, v.y, v.z, v.w)); }
 
+// A caller's float input (image pixel, feature cell) is the only way a NaN or an inf enters the 3xFP16
+// path: finite in-range operands and finite weights give finite sums, and an overflow gives inf, which
+// the folds above catch.  They do not catch NaN (fmaxf returns its other argument, elu16's median turns
+// NaN into 0), so every kernel that reads such an input tests it once, here: x * 0 is NaN for NaN and
+// +-inf and 0 otherwise.  true: the micro-batch must be flagged (range_flag) like an operand out of range
+MMLA_DEV bool nonfinite3(float a, float b, float c) {
+  const float s = fmaf(a, 0.0f, fmaf(b, 0.0f, c * 0.0f));
+  return s != s;
+}
+
 // A split weight tensor (conv_h3_split_weights order) through a wave-uniform buffer descriptor: a
 // fragment load is voffset = the lane's 32-bit offset, soffset = the uniform (tap, k-step) offset, so
 // no load costs 64-bit address VALU

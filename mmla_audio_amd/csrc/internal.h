@@ -131,6 +131,7 @@ struct mmla_ctx {
   int64_t od_mb = 0, si_mb = 0;            // user caps (0 = sized from free memory)
   int64_t od_mb_cap = mmla::kOdMicrobatch, si_mb_cap = mmla::kSiMicrobatch;   // default caps of the automatic size
   int debug_fail_allocs = 0;   // test hook (env MMLA_DEBUG_FAIL_ALLOC at create): fail this many workspace allocations
+  int debug_trace_guard = 0;   // test hook (env MMLA_DEBUG_TRACE_GUARD at create): mmla_debug_od_trace under the range guard
   int precision = MMLA_PREC_F16X3;
   // SI res units as fused launches of siu.hip's one template, siu_chain_kernel<..., POOL, NU, FIN, ...>
   // (net_runners.cpp si_choose); env MMLA_NO_SIU=1 at create: two conv_h3 launches per unit (A/B)

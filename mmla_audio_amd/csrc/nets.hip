@@ -84,7 +84,10 @@ __global__ void maxpool_t2_kernel(const float* __restrict__ x, int n, int t, int
   const int ti = (int)(r % to);
   const int64_t ni = r / to;
   float m = x[(ni * t + 2 * ti) * c + ci];
-  if (2 * ti + 1 < t) m = fmaxf(m, x[(ni * t + 2 * ti + 1) * c + ci]);
+  if (2 * ti + 1 < t) {   // a max that keeps NaN (the exact-f32 path returns what the oracle does)
+    const float u = x[(ni * t + 2 * ti + 1) * c + ci];
+    m = u > m || u != u ? u : m;
+  }
   y[i] = m;
 }
 
@@ -101,7 +104,10 @@ __global__ void bn_relu_avgpool4_kernel(const float* __restrict__ x, int n, int 
   const int64_t ni = r / to;
   float s = 0.0f;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) s += fmaxf(fmaf(x[(ni * t + 4 * ti + j) * c + ci], sc[ci], sh[ci]), 0.0f);
+  for (int j = 0; j < 4; ++j) {   // ReLU that keeps NaN (np.maximum; fmaxf drops it), the same bits otherwise
+    const float v = fmaf(x[(ni * t + 4 * ti + j) * c + ci], sc[ci], sh[ci]);
+    s += v > 0.0f ? v : v == v ? 0.0f : v;
+  }
   y[i] = s / 4.0f;
 }
 

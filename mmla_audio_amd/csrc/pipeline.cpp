@@ -1354,14 +1354,22 @@ int mmla_debug_od_trace(mmla_ctx* c, const float* x, int64_t n, int stage, float
   if (!c || !x || !out || n < 1 || stage < 0 || stage > 11) return MMLA_E_INVALID;
   if (!c->od_loaded) return fail(c, MMLA_E_NOWEIGHTS, "OD weights not loaded");
   HIPCHK(c, hipSetDevice(c->device));
-  const float *dx, *tap = nullptr;
-  int64_t tn = 0;
+  const float* dx;
   CHK(in_ptr(c, x, n * OD_IMG, false, S_IN, &dx));
-  CHK(run_od_net(c, nullptr, dx, n, nullptr, nullptr, OdGate(), stage, &tap, &tn));
-  if (tn > out_floats) return fail(c, MMLA_E_SHAPE, "trace stage %d needs %lld floats", stage, (long long)tn);
-  HIPCHK(c, hipMemcpyAsync(out, tap, tn * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return MMLA_OK;
+  auto body = [&]() -> int {
+    const float* tap = nullptr;
+    int64_t tn = 0;
+    CHK(run_od_net(c, nullptr, dx, n, nullptr, nullptr, OdGate(), stage, &tap, &tn));
+    if (tn > out_floats) return fail(c, MMLA_E_SHAPE, "trace stage %d needs %lld floats", stage, (long long)tn);
+    HIPCHK(c, hipMemcpyAsync(out, tap, tn * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MMLA_OK;
+  };
+  // the trace shows what the selected arithmetic computes, unguarded.  MMLA_DEBUG_TRACE_GUARD=1 at
+  // mmla_create: one host-pointer micro-batch under the range guard, like mmla_od_forward's -- an
+  // operand out of range in a kernel up to `stage` re-runs the trace in exact f32 and counts in
+  // mmla_range_check, so a test can tell which block's guard fired (the blocks behind `stage` do not run)
+  return c->debug_trace_guard ? guarded(c, false, c->od_f32_only, body) : body();
 }
 
 }  // extern "C"

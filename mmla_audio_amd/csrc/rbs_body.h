@@ -302,7 +302,13 @@ __global__ void __launch_bounds__(NT, (SG<H, W, CIN, POOL>::MINB)) RBS_KERNEL(Re
   // zero unless `in` (the 3x3 conv's padding rows; padding columns are zeroed once, see below)
   auto stage4 = [&](int o, bool in, float4 v, auto MASK_) {
     constexpr bool MASK = decltype(MASK_)::value;
-    if constexpr (STEM) v = img_px(v);
+    if constexpr (STEM) {
+      // a float image is a caller's input: a NaN / inf pixel flags the launch here (f16x3.h nonfinite3;
+      // every pixel of the image is staged by some strip, the shortcut re-reads staged pixels).  u8
+      // pixels are finite: the test is behind the wave-uniform im8
+      if (!im8 && (!MASK || in) && nonfinite3(v.x, v.y, v.z)) rmax = SPLIT_MAX;
+      v = img_px(v);
+    }
     float u[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {

@@ -197,6 +197,8 @@ __global__ void __launch_bounds__(NT, (Geo<CIN, C, POOL>::MINB)) resblk_kernel(R
       const int ih = h0 - 2 + py, iw = w0 - 1 + pxx;
       if (p < G::XNP && ih >= 0 && ih < a.h && iw >= 0 && iw < a.w) {
         im[k] = image_px(a, ((int64_t)clip * a.h + ih) * a.w + iw);
+        // a float image is a caller's input: a NaN / inf pixel flags the launch (f16x3.h nonfinite3)
+        if (!a.img8) rbad |= nonfinite3(im[k].x, im[k].y, im[k].z);
         im[k].w = 1.0f;
       }
     }
