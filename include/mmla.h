@@ -464,6 +464,73 @@ int mmla_od_finetune(mmla_ctx* ctx, const float* packed, int64_t n_floats, const
                      const uint8_t* drop_mask, int32_t patience, float* packed_out, float* history,
                      int32_t* epochs_run, uint32_t flags);
 
+/*
+ * Training OD-NET from scratch: OverlapDetector.train_model (overlap_detector.py:392-451) with its class
+ * balancing augment_images (:198-220) and its tf.keras.metrics.AUC() (:403).  The fit is mmla_od_finetune's
+ * statement above in every respect -- graph, BatchNorm rules, loss, Adadelta, validation mode, argument
+ * checks, the epochs == 0 identity, no host synchronisation unless a callback is live -- on the same engine
+ * and the same driver, with three differences:
+ *   dropout   no host mask: drop_seed keys Philox4x32-10 (Salmon et al., SC'11) on the device, the generator
+ *             of mmla_si_base_train at a site of its own.  Key = the two halves of drop_seed, counter =
+ *             (element / 4, sample id, epoch, 2), word = element % 4 over the 512 embedding elements; an
+ *             element is kept iff its word >= 0x40000000.  The sample id is the row of the training set, not
+ *             the slot in the batch.  mmla_od_drop_mask writes the same bits as bytes: fed to
+ *             mmla_od_finetune they give the same fit, bit for bit.
+ *   callbacks EarlyStopping(val_loss, patience) as above and ModelCheckpoint(val_categorical_accuracy,
+ *             save_best_only, mode 'max', period = ckpt_period) as mmla_si_base_train states it: best_out
+ *             [n_floats] (needed when ckpt_period > 0 and n_val > 0; written only when best_epoch >= 0),
+ *             best_epoch [1] (-1 if none).  restore_best_weights is not mirrored (the script never sets it).
+ *   history   [epochs, 7] = loss, acc, val_loss, val_acc, lr, auc, val_auc.  auc: the counts accumulate over
+ *             the batches of the epoch from the training-mode softmax outputs (each batch with the weights
+ *             before its update), as Keras accumulates a metric during fit; val_auc over the validation
+ *             passes, NaN when n_val == 0.  Rows after an early stop are NaN.
+ *
+ * AUC (mmla_od_auc, and the two history columns): tf.keras.metrics.AUC() at its defaults, stated from Keras
+ * 2.6's published source (parity with TF itself is unpinned).  200 float32 thresholds: float32(0 - 1e-7),
+ * float32((i + 1) / 199.0) for i = 0..197 with the quotient in double, float32(1 + 1e-7).  multi_label =
+ * False: all 2 n entries of probs [n, 2] are binary predictions against the entries of the one-hot label
+ * rows; a prediction is positive iff p > thr, strictly.  Per threshold TP, FP, TN, FN are integers (one
+ * thread per threshold walks the rows: no atomics); recall = TP / (TP + FN), fpr = FP / (FP + TN), 0 where
+ * a denominator is 0; auc = sum_{t=0}^{198} (fpr[t] - fpr[t+1]) (recall[t] + recall[t+1]) / 2.  Deliberate
+ * deviation: the formula is evaluated in double from the integer counts and rounded to float32 once, where
+ * Keras sums in float32 -- a difference of at most about 200 x 2^-24.
+ *
+ * mmla_od_augment: the pyramid blur.  out[k] [h, w, 3] = img[src[k]] after levels[k] rounds of cv.pyrDown
+ * then cv.pyrUp, cropped once at the end with [:, :-1]; level 0 is a copy.  Stated from OpenCV's published
+ * uint8 pyramid code; OpenCV is not available here: parity with OpenCV unpinned.  Each channel alone, exact
+ * integer arithmetic, k = (1, 4, 6, 4, 1):
+ *   pyrDown [H, W] -> [(H+1)/2, (W+1)/2]: d[y,x] = (sum_{i,j=-2..2} k[i] k[j] s[r(2y+i), r(2x+j)] + 128) >> 8,
+ *           r = BORDER_REFLECT_101 (-1 -> 1, -2 -> 2, N -> N-2, N+1 -> N-3)
+ *   pyrUp   [H, W] -> [2H, 2W]: along a row e[2x] = s[x-1] + 6 s[x] + s[x+1], e[2x+1] = 4 (s[x] + s[x+1]), then
+ *           the same rule down the columns of e, result (v + 32) >> 6; s[-1] = s[1], s[N] = s[N-1] on both axes
+ *   levels  the first pyrUp of a w-wide image is w + 1 wide; that column stays in the working image through
+ *           every further level (later pyrDowns read it) and is cropped once, after the last
+ * h even in [8, 128], w odd in [9, 151] (other sizes would change the reference's output shape); n in
+ * [1, 2^24], m in [0, 2^24]; a level in [0, MMLA_OD_AUG_MAX_LEVELS].
+ *
+ * mmla_od_drop_mask: mask [n, 512] bytes (1 kept), sample_ids [n] nullable (= 0..n-1), n in [1, 2^20].
+ * mmla_od_auc: probs [n, 2], labels [n] in {0, 1}, n in [1, 2^24] -> auc_out [1].
+ * Host or device pointers (flags) throughout; class_w and lr are host pointers as above.
+ * MMLA_E_INVALID, before any device work: what mmla_od_finetune rejects, ckpt_period < 0, epoch < 0, a size or
+ * count outside the ranges above, a null pointer, and in host-pointer calls a src outside [0, n), a level
+ * outside its range, a label outside {0, 1} or a sample id < 0 (device pointers: src and levels are clamped
+ * into range, a label selects a lane by its lowest bit, a sample id is only a counter word, so a broken
+ * contract gives a wrong result, not an access outside a buffer).
+ */
+#define MMLA_OD_AUG_MAX_LEVELS 8
+int mmla_od_augment(mmla_ctx* ctx, const uint8_t* img, int64_t n, int32_t h, int32_t w, const int32_t* src,
+                    const int32_t* levels, int64_t m, uint8_t* out, uint32_t flags);
+int mmla_od_auc(mmla_ctx* ctx, const float* probs, const int32_t* labels, int64_t n, float* auc_out,
+                uint32_t flags);
+int mmla_od_drop_mask(mmla_ctx* ctx, int64_t drop_seed, int32_t epoch, const int32_t* sample_ids, int64_t n,
+                      uint8_t* mask, uint32_t flags);
+int mmla_od_train(mmla_ctx* ctx, const float* packed, int64_t n_floats, const uint8_t* img_u8,
+                  const int32_t* labels, int64_t n_train, const uint8_t* val_img, const int32_t* val_labels,
+                  int64_t n_val, int32_t h, int32_t w, const float* class_w, int32_t epochs, int32_t batch,
+                  const float* lr, const int32_t* perm, int64_t drop_seed, int32_t patience,
+                  int32_t ckpt_period, float* packed_out, float* best_out, float* history,
+                  int32_t* epochs_run, int32_t* best_epoch, uint32_t flags);
+
 /* Fused WAV->class pipelines (no PNG, no host round trip): probs [n,K] f32 (nullable),
  * argmax [n] i32 (nullable; -1 for 'silent' clips), silent [n] u8 (nullable).  'silent' = fewer
  * than 4000 samples (lens[c], or clip_len without lens): OD record_on_pc.py:141-154 logs it and

@@ -28,6 +28,7 @@ SI_FRAMES, SI_DIMS, SI_SILENT_LEN = 256, 39, 4000
 SI_EMBED, SI_TRAIN_MAX_CLASSES = 512, 32
 SI_BASE_MAX_CLASSES = 1024
 OD_TRAIN_MAX_BATCH, OD_DROP_UNITS = 64, 512
+OD_AUG_MAX_LEVELS = 8
 ENROL_MAX_SAMPLES = 1966080
 MIX_MAX_LAYERS = 8
 
@@ -118,6 +119,16 @@ SIGNATURES = {
     # lr, perm, drop_mask, patience, packed_out, history, epochs_run
     'mmla_od_finetune': [_P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _I32,
                          _P, _P, _P, _U32],
+    # ctx, img, n, h, w, src, levels, m, out
+    'mmla_od_augment': [_P, _P, _I64, _I32, _I32, _P, _P, _I64, _P, _U32],
+    # ctx, probs, labels, n, auc_out
+    'mmla_od_auc': [_P, _P, _P, _I64, _P, _U32],
+    # ctx, drop_seed, epoch, sample_ids, n, mask
+    'mmla_od_drop_mask': [_P, _I64, _I32, _P, _I64, _P, _U32],
+    # ctx, packed, n_floats, img_u8, labels, n_train, val_img, val_labels, n_val, h, w, class_w, epochs, batch,
+    # lr, perm, drop_seed, patience, ckpt_period, packed_out, best_out, history, epochs_run, best_epoch
+    'mmla_od_train': [_P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I32, _I32, _P, _I32, _I32, _P, _P, _I64, _I32,
+                      _I32, _P, _P, _P, _P, _P, _U32],
     'mmla_od_pipeline': [_P, _P, _I64, _I64, _P, _I32, _P, _P, _P, _U32],
     'mmla_si_pipeline': [_P, _P, _I64, _I64, _P, _I32, _P, _P, _P, _U32],
     'mmla_ssim_u8': [_P, _P, _P, _I64, _I32, _I32, _I32, _P, _U32],
@@ -906,6 +917,75 @@ class Context:
             'mmla_od_finetune')
         return out, hist, int(ran[0])
 
+    def od_train(self, packed, img, labels, val_img, val_labels, class_w, lr, perm, epochs, batch=16, drop_seed=0,
+                 patience=0, ckpt_period=0):
+        """OverlapDetector.train_model's fit on the device (mmla_od_train): od_finetune's arguments with the
+        dropout keep-bits generated on the device from drop_seed and ModelCheckpoint(val_acc, 'max',
+        ckpt_period).  -> (packed_out, best float32 [n_floats] or None, history [epochs,7] = loss, acc,
+        val_loss, val_acc, lr, auc, val_auc (NaN rows after an early stop), epochs_run, best_epoch or -1)."""
+        packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
+        img, labels = self._od_images(img, labels, 'img')
+        n, h, w = img.shape[:3]
+        epochs, perm, vi, vl, nv, opt = self._fit_args(perm, epochs, n, val_img, val_labels, self._od_images, 'val_img',
+                                                        trim=True)
+        cw = np.ascontiguousarray(class_w, dtype=np.float32).reshape(2)
+        lr = np.ascontiguousarray(lr, dtype=np.float32).ravel()[:epochs]
+        if lr.shape != (epochs,):
+            raise ValueError(f'lr {lr.shape}: expected [{epochs}]')
+        if nv and vi.shape[1:] != img.shape[1:]:
+            raise ValueError(f'val_img {vi.shape}: expected [n,{h},{w},3]')
+        out = np.empty_like(packed)
+        best = np.empty_like(packed)
+        hist = np.empty((epochs, 7), np.float32)
+        ran = np.zeros(1, np.int32)
+        best_ep = np.full(1, -1, np.int32)
+        self._check(self.lib.mmla_od_train(
+            self.h, _ptr(packed), packed.size, _ptr(img), _ptr(labels), n, _ptr(vi), _ptr(vl), nv, h, w, _ptr(cw),
+            epochs, int(batch), opt(lr), opt(perm), _seed64(drop_seed), int(patience), int(ckpt_period), _ptr(out),
+            _ptr(best), opt(hist), _ptr(ran), _ptr(best_ep), 0), 'mmla_od_train')
+        return out, (best if best_ep[0] >= 0 else None), hist, int(ran[0]), int(best_ep[0])
+
+    def od_drop_mask(self, drop_seed, epoch, sample_ids, n=None):
+        """The dropout keep-bits of an mmla_od_train fit as bytes (mmla_od_drop_mask): sample_ids [n] (None:
+        0..n-1) -> uint8 [n,512] on the embedding; 1 = kept."""
+        ids = None
+        if sample_ids is not None:
+            ids = np.ascontiguousarray(sample_ids, dtype=np.int32).ravel()
+            n = ids.size
+        n = int(n)
+        mask = np.empty((max(n, 0), OD_DROP_UNITS), np.uint8)
+        self._check(self.lib.mmla_od_drop_mask(self.h, _seed64(drop_seed), int(epoch), _ptr(ids), n, _ptr(mask), 0),
+                    'mmla_od_drop_mask')
+        return mask
+
+    def od_augment(self, img, src, levels):
+        """The pyramid blur of augment_images (mmla_od_augment): img uint8 [n,h,w,3] (h even in [8,128], w odd
+        in [9,151]), src [m] rows of img, levels [m] in [0, 8] -> uint8 [m,h,w,3]; out[k] = img[src[k]] after
+        levels[k] rounds of pyrDown + pyrUp, cropped once."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        if img.ndim != 4 or img.shape[3] != 3:
+            raise ValueError(f'img {img.shape}: expected [n,h,w,3]')
+        src = np.ascontiguousarray(src, dtype=np.int32).ravel()
+        levels = np.ascontiguousarray(levels, dtype=np.int32).ravel()
+        if src.shape != levels.shape:
+            raise ValueError(f'src {src.shape} / levels {levels.shape}: expected one level per source row')
+        n, h, w = img.shape[:3]
+        out = np.empty((src.size, h, w, 3), np.uint8)
+        self._check(self.lib.mmla_od_augment(self.h, _ptr(img), n, h, w, _ptr(src), _ptr(levels), src.size, _ptr(out),
+                                             0), 'mmla_od_augment')
+        return out
+
+    def od_auc(self, probs, labels):
+        """tf.keras.metrics.AUC() at its defaults (mmla_od_auc) of probs float32 [n,2] against labels [n] in
+        {0,1} -> float32 scalar."""
+        probs = np.ascontiguousarray(probs, dtype=np.float32)
+        labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+        if probs.ndim != 2 or probs.shape != (labels.size, 2):
+            raise ValueError(f'probs {probs.shape} / labels {labels.shape}: expected [n,2] and [n]')
+        out = np.empty(1, np.float32)
+        self._check(self.lib.mmla_od_auc(self.h, _ptr(probs), _ptr(labels), labels.size, _ptr(out), 0), 'mmla_od_auc')
+        return out[0]
+
     def od_pipeline(self, pcm, lens=None):
         """-> (probs [n,2], argmax [n] (-1 = 'silent'), silent [n] bool)."""
         a, ln, L = self._pcm(pcm, lens)
@@ -1395,6 +1475,34 @@ class Context:
             self.h, packed, n_floats, img, labels, n_train, val_img or None, val_labels or None, n_val, h, w,
             _ptr(cw), epochs, batch, _ptr(lr), perm, drop_mask or None, patience, packed_out, history,
             epochs_run, MMLA_DEVICE_PTR), 'mmla_od_finetune(dev)')
+
+    def od_train_dev(self, packed, n_floats, img, labels, n_train, val_img, val_labels, n_val, h, w, class_w,
+                     epochs, batch, lr, perm, drop_seed, patience, ckpt_period, packed_out, best_out, history,
+                     epochs_run, best_epoch):
+        """mmla_od_train on device buffers (class_w, lr: host float32 arrays; epochs_run, best_epoch: device
+        int32 words): the caller guarantees labels in {0, 1} and that every perm row is a permutation;
+        asynchronous on the context's stream unless a callback is on (patience or ckpt_period > 0 with
+        n_val > 0)"""
+        cw = np.ascontiguousarray(class_w, dtype=np.float32).reshape(2)
+        lr = np.ascontiguousarray(lr, dtype=np.float32).ravel()
+        self._check(self.lib.mmla_od_train(
+            self.h, packed, n_floats, img, labels, n_train, val_img or None, val_labels or None, n_val, h, w,
+            _ptr(cw), epochs, batch, _ptr(lr), perm or None, _seed64(drop_seed), patience, ckpt_period, packed_out,
+            best_out or None, history or None, epochs_run, best_epoch, MMLA_DEVICE_PTR), 'mmla_od_train(dev)')
+
+    def od_drop_mask_dev(self, drop_seed, epoch, sample_ids, n, mask):
+        """mmla_od_drop_mask on device buffers (sample_ids 0: 0..n-1)"""
+        self._check(self.lib.mmla_od_drop_mask(self.h, _seed64(drop_seed), epoch, sample_ids or None, n, mask,
+                                               MMLA_DEVICE_PTR), 'mmla_od_drop_mask(dev)')
+
+    def od_augment_dev(self, img, n, h, w, src, levels, m, out):
+        """mmla_od_augment on device buffers (src and levels are clamped into range)"""
+        self._check(self.lib.mmla_od_augment(self.h, img, n, h, w, src or None, levels or None, m, out or None,
+                                             MMLA_DEVICE_PTR), 'mmla_od_augment(dev)')
+
+    def od_auc_dev(self, probs, labels, n, auc_out):
+        """mmla_od_auc on device buffers (a label selects its class by its lowest bit)"""
+        self._check(self.lib.mmla_od_auc(self.h, probs, labels, n, auc_out, MMLA_DEVICE_PTR), 'mmla_od_auc(dev)')
 
 
 _default = {}

@@ -10,8 +10,9 @@
 //   si_finetune.cpp  SI-NET's engine over si_bwd.hip and, with `base`, si_base.hip; one loss-grad body
 //                    (mmla_si_loss_grad, mmla_si_base_loss_grad) and one set of fit callables (mmla_si_finetune,
 //                    mmla_si_base_train) for the driver; mmla_si_base_drop_mask
-//   od_finetune.cpp  OD-NET's engine over conv.hip, od_bwd.hip, si_bwd.hip; mmla_od_loss_grad, and
-//                    mmla_od_finetune's callables for the driver
+//   od_finetune.cpp  OD-NET's engine over conv.hip, od_bwd.hip, si_bwd.hip; mmla_od_loss_grad, and one set of
+//                    fit callables (mmla_od_finetune, mmla_od_train) for the driver; mmla_od_drop_mask,
+//                    mmla_od_auc, mmla_od_augment (od_aug.hip)
 // All but mmla_ctx (the type include/mmla.h names) lives in namespace mmla, which is not exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -277,7 +278,8 @@ enum Slot {
   // then the call's staged host-pointer operands; carved anew by every call (carve_slot)
   S_FT,
   S_MIX, S_MIX_LEN,  // mmla_od_mix / mmla_od_pipeline_mixed: a micro-batch's mixed clips and their lengths
-  S_ODFT   // mmla_od_loss_grad / mmla_od_finetune: likewise for the OD blob
+  S_ODFT   // mmla_od_loss_grad / mmla_od_finetune / mmla_od_train: likewise for the OD blob; the staged
+           // operands of mmla_od_drop_mask, mmla_od_auc and mmla_od_augment
 };
 
 // mmla_ctx::cap_buf: staged raw capture, host frames, per-clip entry (d0, prev), converted clips and

@@ -88,6 +88,7 @@ struct OdbHead {
   double* acc;             // [2]: += sum of the samples' losses, += hits
   int B;
   float bsz;
+  float* probs;            // [B, 2] the softmax outputs (nullable)
 };
 hipError_t odb_head_loss(const OdbHead& a, hipStream_t stream);
 // gw [512, 2], gb [2], demb [B, 512]
@@ -103,3 +104,31 @@ hipError_t odb_end_epoch(double* st, int n_train, int n_val, const float* lrs, i
 // loss[0] = st[0] / n
 hipError_t odb_loss_out(const double* st, int n, float* loss, hipStream_t stream);
 hipError_t odb_fill(float* p, int64_t n, float v, hipStream_t stream);
+
+// ---- training from scratch (OverlapDetector.train_model): device keep-bits and the AUC metric --------------
+
+// mask [n, 512] bytes: element d of the sample with id sid[s] is kept (1) iff word d % 4 of Philox4x32-10
+// (philox.h), key = the halves of seed, counter = (d / 4, sid[s], epoch, 2), is >= 0x40000000 (rate 0.25)
+hipError_t odb_drop_mask(uint64_t seed, uint32_t epoch, const int32_t* sid, int n, uint8_t* mask,
+                         hipStream_t stream);
+
+// tf.keras.metrics.AUC() at its defaults: 200 thresholds, float32(-1e-7), float32((i + 1) / 199.0) (the
+// quotient in double), float32(1 + 1e-7); a prediction is positive iff p > thr
+constexpr int ODB_AUC_T = 200;
+constexpr int ODB_AUC_SLABS = 256;                     // most slabs of one count
+constexpr int ODB_AUC_COUNTS = 2 * ODB_AUC_T;          // words of one slab's counts: TP, FP per threshold
+struct OdbAucThr {
+  float t[ODB_AUC_T];
+};
+OdbAucThr odb_auc_thresholds();
+// slabs of a count over n samples: min(ODB_AUC_SLABS, ceil(n / 4096))
+int odb_auc_slabs(int64_t n);
+// counts [slabs, 200, 2] (uint32): over the 2 n entries of probs [n, 2] against the one-hot rows of labels
+// (bit 0), TP and FP per threshold; add != 0: added to what counts holds, else written.  Integer counts
+// and no atomics: one thread per threshold walks its slab's rows
+hipError_t odb_auc_count(const float* probs, const int32_t* labels, int64_t n, const OdbAucThr& thr, int add,
+                         uint32_t* counts, hipStream_t stream);
+// out[0] = float32 of sum_t (fpr[t] - fpr[t + 1]) (recall[t] + recall[t + 1]) / 2 in double from the slabs'
+// integer sums; the 2 n entries hold n positives and n negatives, so FN = n - TP, TN = n - FP.  n == 0: NaN.
+// clear != 0: counts zeroed afterwards
+hipError_t odb_auc_final(uint32_t* counts, int slabs, int64_t n, int clear, float* out, hipStream_t stream);

@@ -12,6 +12,9 @@
 //                      recomputed from x on the way, as conv.hip's prologue computes it
 //   BN + ELU backward, max-pool backward by the stored winner, the stride-2 shortcut's data gradient, the
 //   mean over H, the head (dropout mask, LeakyReLU, Dense(2), softmax, weighted loss), Adadelta
+//   training from scratch (mmla_od_train): the keep-bits of a batch from Philox4x32-10 (philox.h, site 2) as
+//   mask bytes, and tf.keras.metrics.AUC(): integer TP / FP counts per threshold, one thread per threshold,
+//   then the trapezoid sum in double
 //
 // Determinism: no floating-point atomics.  Every sum over pixels is split into slabs whose count depends
 // on the shape alone; a workgroup reduces its slab in a fixed order (serial per thread, then an LDS tree,
@@ -21,6 +24,8 @@
 // of two lanes by its lowest bit, mask bytes are read as zero / non-zero.
 #include "od_bwd.h"
 
+#include "philox.h"
+
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -28,6 +33,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr float BN_EPS = 1e-3f;
 constexpr float LEAKY = 0.3f;                  // float32(0.3)
 constexpr float KEEP_SCALE = 1.0f / 0.75f;     // float32(1 / (1 - rate))
+constexpr uint32_t DROP_RATE = 0x40000000u;    // the rate 0.25 as a 32-bit fraction
 constexpr int C = ODB_MAX_C;
 
 inline dim3 grid1(int64_t n, int nt) { return dim3((unsigned)((n + nt - 1) / nt)); }
@@ -387,6 +393,10 @@ __global__ void __launch_bounds__(ODB_MAX_BATCH) head_loss_kernel(OdbHead a) {
     const bool inside = pc >= lo && pc <= hi;
     l = wc * (float)(-log((double)fminf(fmaxf(pc, lo), hi)));
     h = (q1 > q0 ? 1 : 0) == c ? 1 : 0;
+    if (a.probs) {
+      a.probs[2 * s] = p0;
+      a.probs[2 * s + 1] = p1;
+    }
     if (a.dz) {
       a.dz[2 * s] = inside ? wc * (q0 - (c == 0 ? 1.0f : 0.0f)) / a.bsz : 0.0f;
       a.dz[2 * s + 1] = inside ? wc * (q1 - (c == 1 ? 1.0f : 0.0f)) / a.bsz : 0.0f;
@@ -461,6 +471,66 @@ __global__ void loss_out_kernel(const double* st, int n, float* loss) { loss[0] 
 __global__ void fill_kernel(float* p, int64_t n, float v) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
+}
+
+// ---- keep-bits and the AUC metric of a fit from scratch ----------------------------------------------------
+
+// thread = (sample, four elements): one Philox block
+__global__ void drop_mask_kernel(uint64_t seed, uint32_t epoch, const int32_t* __restrict__ sid, int n,
+                                 uint8_t* __restrict__ mask) {
+  constexpr int Q = ODB_HEAD_D / 4;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)n * Q) return;
+  const int s = (int)(i / Q), q = (int)(i % Q);
+  const U4 r = philox_drop_words(seed, epoch, (uint32_t)sid[s], (uint32_t)q, 2u);
+  uint8_t* out = mask + (size_t)s * ODB_HEAD_D + 4 * q;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out[k] = r.v[k] >= DROP_RATE ? 1 : 0;
+}
+
+constexpr int AUC_NT = 256;
+
+// workgroup = one slab of rows, thread = one threshold
+__global__ void __launch_bounds__(AUC_NT) auc_count_kernel(const float* __restrict__ probs,
+                                                           const int32_t* __restrict__ labels, int64_t n,
+                                                           int64_t slab_len, OdbAucThr thr, int add,
+                                                           uint32_t* __restrict__ counts) {
+  const int t = threadIdx.x;
+  if (t >= ODB_AUC_T) return;
+  const float th = thr.t[t];
+  const int64_t r0 = (int64_t)blockIdx.x * slab_len, r1 = min(n, r0 + slab_len);
+  uint32_t tp = 0, fp = 0;
+  for (int64_t r = r0; r < r1; ++r) {
+    const int c = labels[r] & 1;
+    const bool pos0 = probs[2 * r] > th, pos1 = probs[2 * r + 1] > th;
+    tp += (c ? pos1 : pos0) ? 1u : 0u;   // the entry whose one-hot label is 1
+    fp += (c ? pos0 : pos1) ? 1u : 0u;
+  }
+  uint32_t* out = counts + ((size_t)blockIdx.x * ODB_AUC_T + t) * 2;
+  out[0] = add ? out[0] + tp : tp;
+  out[1] = add ? out[1] + fp : fp;
+}
+
+__global__ void __launch_bounds__(AUC_NT) auc_final_kernel(uint32_t* counts, int slabs, int64_t n, int clear,
+                                                           float* __restrict__ out) {
+  __shared__ double rec[ODB_AUC_T], fpr[ODB_AUC_T];
+  const int t = threadIdx.x;
+  if (t < ODB_AUC_T) {
+    uint64_t tp = 0, fp = 0;
+    for (int q = 0; q < slabs; ++q) {
+      uint32_t* at = counts + ((size_t)q * ODB_AUC_T + t) * 2;
+      tp += at[0];
+      fp += at[1];
+      if (clear) at[0] = at[1] = 0u;
+    }
+    rec[t] = n > 0 ? (double)tp / (double)n : 0.0;
+    fpr[t] = n > 0 ? (double)fp / (double)n : 0.0;
+  }
+  __syncthreads();
+  if (t != 0) return;
+  double auc = 0.0;
+  for (int q = 0; q + 1 < ODB_AUC_T; ++q) auc += (fpr[q] - fpr[q + 1]) * (rec[q] + rec[q + 1]) / 2.0;
+  out[0] = n > 0 ? (float)auc : __builtin_nanf("");
 }
 
 inline bool bn_width_ok(int c) { return c == 16 || c == 32 || c == 64 || c == 128; }
@@ -660,5 +730,40 @@ hipError_t odb_loss_out(const double* st, int n, float* loss, hipStream_t stream
 hipError_t odb_fill(float* p, int64_t n, float v, hipStream_t stream) {
   if (n < 1) return hipSuccess;
   ODB_LAUNCH(fill_kernel, grid1(n, 256), dim3(256), p, n, v);
+  return hipSuccess;
+}
+
+hipError_t odb_drop_mask(uint64_t seed, uint32_t epoch, const int32_t* sid, int n, uint8_t* mask,
+                         hipStream_t stream) {
+  if (n < 1) return hipErrorInvalidValue;
+  ODB_LAUNCH(drop_mask_kernel, grid1((int64_t)n * (ODB_HEAD_D / 4), 256), dim3(256), seed, epoch, sid, n, mask);
+  return hipSuccess;
+}
+
+OdbAucThr odb_auc_thresholds() {
+  OdbAucThr thr;
+  thr.t[0] = (float)(0.0 - 1e-7);
+  for (int i = 0; i < ODB_AUC_T - 2; ++i) thr.t[i + 1] = (float)((double)(i + 1) / 199.0);
+  thr.t[ODB_AUC_T - 1] = (float)(1.0 + 1e-7);
+  return thr;
+}
+
+int odb_auc_slabs(int64_t n) {
+  const int64_t s = (n + 4095) / 4096;
+  return (int)(s < 1 ? 1 : s > ODB_AUC_SLABS ? ODB_AUC_SLABS : s);
+}
+
+hipError_t odb_auc_count(const float* probs, const int32_t* labels, int64_t n, const OdbAucThr& thr, int add,
+                         uint32_t* counts, hipStream_t stream) {
+  if (n < 1) return hipErrorInvalidValue;
+  const int S = odb_auc_slabs(n);
+  const int64_t len = (n + S - 1) / S;   // ceil: slabs * len >= n, and every slab starts inside the rows
+  ODB_LAUNCH(auc_count_kernel, dim3(S), dim3(AUC_NT), probs, labels, n, len, thr, add, counts);
+  return hipSuccess;
+}
+
+hipError_t odb_auc_final(uint32_t* counts, int slabs, int64_t n, int clear, float* out, hipStream_t stream) {
+  if (slabs < 1 || slabs > ODB_AUC_SLABS) return hipErrorInvalidValue;
+  ODB_LAUNCH(auc_final_kernel, dim3(1), dim3(AUC_NT), counts, slabs, n, clear, out);
   return hipSuccess;
 }

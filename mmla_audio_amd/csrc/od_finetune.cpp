@@ -1,4 +1,6 @@
-// libmmla: adapting OD-NET to a room -- mmla_od_loss_grad and mmla_od_finetune (include/mmla.h).
+// libmmla: training OD-NET -- adapting it to a room (mmla_od_loss_grad, mmla_od_finetune) and training it from
+// scratch (mmla_od_train on the same engine and fit body, with mmla_od_drop_mask, mmla_od_auc and
+// mmla_od_augment, the entries of od_aug.hip and of od_bwd.hip's keep-bit and AUC kernels) (include/mmla.h).
 // Which kernel runs which layer, forward and backward, over a copy of the packed OD blob in workspace
 // slot S_ODFT; the context's loaded model is not touched.  Every forward convolution and every stride-1
 // data gradient is conv.hip's conv_launch (exact f32 MFMA); the weight gradients, BatchNorm in training
@@ -12,7 +14,9 @@
 #include "conv.h"
 #include "fit_common.h"
 #include "internal.h"
+#include "od_aug.h"
 #include "od_bwd.h"
+#include "si_base.h"
 #include "si_bwd.h"
 
 namespace mmla {
@@ -91,6 +95,12 @@ struct Engine {
   float *xb = nullptr, *net0 = nullptr, *seq = nullptr, *emb = nullptr, *dzh = nullptr, *demb = nullptr;
   int32_t* lb = nullptr;
   uint8_t* mb = nullptr;
+  // mmla_od_train: the batch's sample ids, its softmax outputs, the epoch's AUC counts (training, validation)
+  bool auc = false;
+  OdbAucThr thr{};
+  int32_t* sid = nullptr;
+  float* probs = nullptr;
+  uint32_t* auc_n = nullptr;
   BlkAct ba[9];
   float* gbuf[3] = {nullptr, nullptr, nullptr};
   SibLstm lstm{};
@@ -170,6 +180,9 @@ void carve(Engine& e, Carver& cv, bool train) {
   l.dh = cv.take<float>(2 * B * SIB_LSTM_U);
   l.dc = cv.take<float>(2 * B * SIB_LSTM_U);
   l.dxs = cv.take<float>(2 * B * T * SIB_LSTM_D);
+  e.sid = cv.take<int32_t>(B);
+  e.probs = cv.take<float>(B * 2);
+  e.auc_n = cv.take<uint32_t>(2 * ODB_AUC_COUNTS);
   if (cv.base) {
     wire_lstm(l, e.off, e.W, e.G);
     l.seq = e.seq;
@@ -267,8 +280,10 @@ int forward(Engine& e, int B, bool train, double* acc) {
   e.lstm.B = B;
   RUN(sib_lstm_fwd(e.lstm, s));
   OdbHead h{e.emb, train ? e.mb : nullptr, W + e.off.dw, W + e.off.db, e.lb, {e.cw[0], e.cw[1]},
-            train ? e.dzh : nullptr, acc, B, (float)B};
+            train ? e.dzh : nullptr, acc, B, (float)B, e.auc ? e.probs : nullptr};
   RUN(odb_head_loss(h, s));
+  // Keras accumulates a metric over the batches of an epoch: the training-mode outputs, then the validation's
+  if (e.auc) RUN(odb_auc_count(e.probs, e.lb, B, e.thr, 1, e.auc_n + (train ? 0 : ODB_AUC_COUNTS), s));
   return MMLA_OK;
 }
 
@@ -277,7 +292,7 @@ int backward(Engine& e, int B) {
   hipStream_t s = e.c->stream;
   const float* W = e.W;
   float* G = e.G;
-  OdbHead h{e.emb, e.mb, W + e.off.dw, W + e.off.db, e.lb, {e.cw[0], e.cw[1]}, e.dzh, nullptr, B, (float)B};
+  OdbHead h{e.emb, e.mb, W + e.off.dw, W + e.off.db, e.lb, {e.cw[0], e.cw[1]}, e.dzh, nullptr, B, (float)B, nullptr};
   RUN(odb_head_bwd(h, G + e.off.dw, G + e.off.db, e.demb, s));
   RUN(sib_lstm_bwd(e.lstm, s));
   float *cur = e.gbuf[0], *f1 = e.gbuf[1], *f2 = e.gbuf[2];
@@ -343,6 +358,7 @@ int prepare(Engine& e, bool train) {
   HIPCHK(e.c, hipMemsetAsync(e.G, 0, wbytes, s));   // the moving-statistics slots stay 0
   HIPCHK(e.c, hipMemsetAsync(e.zero, 0, C * sizeof(float), s));
   HIPCHK(e.c, hipMemsetAsync(e.st, 0, SIB_ST * sizeof(double), s));
+  if (e.auc) HIPCHK(e.c, hipMemsetAsync(e.auc_n, 0, 2 * ODB_AUC_COUNTS * sizeof(uint32_t), s));
   if (!train) return MMLA_OK;
   HIPCHK(e.c, hipMemsetAsync(e.acc_g, 0, wbytes, s));   // a new optimiser: every accumulator from 0
   HIPCHK(e.c, hipMemsetAsync(e.acc_d, 0, wbytes, s));
@@ -359,6 +375,77 @@ Engine engine(mmla_ctx* c, int cap, int h, int w, const float* class_w) {
   e.cw[1] = class_w[1];
   set_dims(e, h, w);
   return e;
+}
+
+// mmla_od_finetune and, with `scratch`, mmla_od_train: what fit_common.h's driver runs per step.  scratch: the
+// keep-bits of every batch are generated on the device from drop_seed (site 2, by training-set row), and the
+// AUC of the epoch's training-mode and validation outputs is counted into history columns 5 and 6
+int od_fit(mmla_ctx* c, FitCall a, int32_t h, int32_t w, const float* class_w, const float* lr,
+           const uint8_t* drop_mask, bool scratch, int64_t drop_seed) {
+  if (!c) return MMLA_E_INVALID;
+  const char* who = a.who;
+  CHK(check_common(c, who, (int64_t)a.n_floats, h, w, class_w));
+  const int32_t epochs = a.epochs;
+  const int64_t n_train = a.n_train;
+  a.unit = "images";
+  a.slot = S_ODFT;
+  a.max_batch = MMLA_OD_TRAIN_MAX_BATCH;
+  a.val_chunk = 16;
+  a.n_classes = 2;
+  a.label_set = kLabelSet;
+  a.row_bytes = (size_t)h * w * 3;
+  // rows after an early stop
+  a.nan_fill = [](float* hist, size_t n, hipStream_t s) { return odb_fill(hist, (int64_t)n, __builtin_nanf(""), s); };
+  CHK(fit_check(c, a));
+  if (epochs > 0 && !lr) return fail(c, MMLA_E_INVALID, "%s: null pointer", who);
+  for (int ep = 0; ep < epochs; ++ep)
+    if (!std::isfinite(lr[ep]) || lr[ep] < 0.0f)
+      return fail(c, MMLA_E_INVALID, "%s: lr[%d] = %g is negative or not finite", who, ep, lr[ep]);
+  Engine e = engine(c, a.cap(), h, w, class_w);
+  e.auc = scratch;
+  if (scratch) e.thr = odb_auc_thresholds();
+  hipStream_t s = c->stream;
+  const int img_bytes = (int)a.row_bytes, n = (int)n_train, nv = (int)a.n_val;
+  const float* dlr = nullptr;
+  const uint8_t* dmask = nullptr;   // [epochs, n_train, 512], indexed by epoch and sample
+  return fit(
+      c, a,
+      [&](Carver& cv, Stager& st, FitBufs& d) -> int {
+        carve(e, cv, true);
+        d.blob = e.W;
+        CHK(st.up(cv, lr, (size_t)epochs, &dlr));   // a host array in either mode
+        CHK(d.stage_in(a, cv, st));
+        CHK(st.in(cv, drop_mask, (size_t)epochs * n_train * ODB_HEAD_D, &dmask));
+        d.stage_out(a, cv, st);
+        return MMLA_OK;
+      },
+      [&]() -> int { return prepare(e, true); },
+      [&](const FitBufs& d, int ep, const int32_t* order, int b0, int nb) -> int {
+        const uint8_t* mask = dmask ? dmask + (size_t)ep * n_train * ODB_HEAD_D : nullptr;
+        RUN(odb_gather(static_cast<const uint8_t*>(d.x), d.labels, mask, order, b0, nb, n, img_bytes, e.xb, e.lb, e.mb,
+                       s));
+        if (scratch) {   // the batch's keep-bits over the all-ones the gather left
+          RUN(sbb_ids(nullptr, order, b0, nb, n, e.sid, s));
+          RUN(odb_drop_mask((uint64_t)drop_seed, (uint32_t)ep, e.sid, nb, e.mb, s));
+        }
+        CHK(forward(e, nb, true, e.st));
+        CHK(backward(e, nb));
+        RUN(sib_fold_batch(e.st, nb, s));
+        RUN(odb_adadelta(e.W, e.acc_g, e.acc_d, e.G, e.trainable, (int64_t)e.off.total, dlr, ep, s));
+        return MMLA_OK;
+      },
+      [&](const FitBufs& d, int v0, int nb) -> int {
+        RUN(odb_gather(static_cast<const uint8_t*>(d.val_x), d.val_labels, nullptr, nullptr, v0, nb, nv, img_bytes,
+                       e.xb, e.lb, e.mb, s));
+        return forward(e, nb, false, e.st + 5);
+      },
+      [&](int ep, float* row) -> int {
+        RUN(odb_end_epoch(e.st, n, nv, dlr, ep, row, s));
+        if (!scratch) return MMLA_OK;
+        RUN(odb_auc_final(e.auc_n, 1, n, 1, row + 5, s));
+        RUN(odb_auc_final(e.auc_n + ODB_AUC_COUNTS, 1, nv, 1, row + 6, s));   // NaN when n_val == 0
+        return MMLA_OK;
+      });
 }
 
 }  // namespace
@@ -414,64 +501,123 @@ int mmla_od_finetune(mmla_ctx* c, const float* packed, int64_t n_floats, const u
                      int64_t n_val, int32_t h, int32_t w, const float* class_w, int32_t epochs, int32_t batch,
                      const float* lr, const int32_t* perm, const uint8_t* drop_mask, int32_t patience,
                      float* packed_out, float* history, int32_t* epochs_run, uint32_t flags) {
-  if (!c) return MMLA_E_INVALID;
-  CHK(check_common(c, "od_finetune", n_floats, h, w, class_w));
   FitCall a = fit_call("od_finetune", packed, n_floats, img_u8, labels, n_train, val_img, val_labels, n_val, epochs,
                        batch, perm, packed_out, history, flags);
-  a.unit = "images";
-  a.slot = S_ODFT;
-  a.max_batch = MMLA_OD_TRAIN_MAX_BATCH;
-  a.val_chunk = 16;
   a.hist_w = 5;   // ... and the epoch's lr
   a.callbacks = FIT_STOP;
-  a.n_classes = 2;
-  a.label_set = kLabelSet;
-  a.row_bytes = (size_t)h * w * 3;
   a.patience = patience;
   a.epochs_run = epochs_run;
-  // rows after an early stop
-  a.nan_fill = [](float* hist, size_t n, hipStream_t s) { return odb_fill(hist, (int64_t)n, __builtin_nanf(""), s); };
-  CHK(fit_check(c, a));
-  if (epochs > 0 && !lr) return fail(c, MMLA_E_INVALID, "od_finetune: null pointer");
-  for (int ep = 0; ep < epochs; ++ep)
-    if (!std::isfinite(lr[ep]) || lr[ep] < 0.0f)
-      return fail(c, MMLA_E_INVALID, "od_finetune: lr[%d] = %g is negative or not finite", ep, lr[ep]);
-  Engine e = engine(c, a.cap(), h, w, class_w);
+  return od_fit(c, a, h, w, class_w, lr, drop_mask, false, 0);
+}
+
+int mmla_od_train(mmla_ctx* c, const float* packed, int64_t n_floats, const uint8_t* img_u8, const int32_t* labels,
+                  int64_t n_train, const uint8_t* val_img, const int32_t* val_labels, int64_t n_val, int32_t h,
+                  int32_t w, const float* class_w, int32_t epochs, int32_t batch, const float* lr,
+                  const int32_t* perm, int64_t drop_seed, int32_t patience, int32_t ckpt_period, float* packed_out,
+                  float* best_out, float* history, int32_t* epochs_run, int32_t* best_epoch, uint32_t flags) {
+  FitCall a = fit_call("od_train", packed, n_floats, img_u8, labels, n_train, val_img, val_labels, n_val, epochs,
+                       batch, perm, packed_out, history, flags);
+  a.hist_w = 7;   // ... the epoch's lr, auc, val_auc
+  a.callbacks = FIT_STOP | FIT_CKPT;
+  a.patience = patience;
+  a.ckpt_period = ckpt_period;
+  a.best_out = best_out;
+  a.epochs_run = epochs_run;
+  a.best_epoch = best_epoch;
+  return od_fit(c, a, h, w, class_w, lr, nullptr, true, drop_seed);
+}
+
+int mmla_od_drop_mask(mmla_ctx* c, int64_t drop_seed, int32_t epoch, const int32_t* sample_ids, int64_t n,
+                      uint8_t* mask, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  if (n < 1 || n > (1 << 20)) return fail(c, MMLA_E_INVALID, "od_drop_mask: n %lld outside [1, 2^20]", (long long)n);
+  if (epoch < 0) return fail(c, MMLA_E_INVALID, "od_drop_mask: epoch %d < 0", epoch);
+  if (!mask) return fail(c, MMLA_E_INVALID, "od_drop_mask: null pointer");
+  Stager st{c, (flags & MMLA_DEVICE_PTR) != 0};
+  if (!st.dev && sample_ids)
+    for (int64_t i = 0; i < n; ++i)
+      if (sample_ids[i] < 0)
+        return fail(c, MMLA_E_INVALID, "od_drop_mask: sample_ids[%lld] = %d < 0", (long long)i, sample_ids[i]);
+  HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
-  const int img_bytes = (int)a.row_bytes, n = (int)n_train, nv = (int)n_val;
-  const float* dlr = nullptr;
-  const uint8_t* dmask = nullptr;   // [epochs, n_train, 512], indexed by epoch and sample
-  return fit(
-      c, a,
-      [&](Carver& cv, Stager& st, FitBufs& d) -> int {
-        carve(e, cv, true);
-        d.blob = e.W;
-        CHK(st.up(cv, lr, (size_t)epochs, &dlr));   // a host array in either mode
-        CHK(d.stage_in(a, cv, st));
-        CHK(st.in(cv, drop_mask, (size_t)epochs * n_train * ODB_HEAD_D, &dmask));
-        d.stage_out(a, cv, st);
-        return MMLA_OK;
-      },
-      [&]() -> int { return prepare(e, true); },
-      [&](const FitBufs& d, int ep, const int32_t* order, int b0, int nb) -> int {
-        const uint8_t* mask = dmask ? dmask + (size_t)ep * n_train * ODB_HEAD_D : nullptr;
-        RUN(odb_gather(static_cast<const uint8_t*>(d.x), d.labels, mask, order, b0, nb, n, img_bytes, e.xb, e.lb, e.mb,
-                       s));
-        CHK(forward(e, nb, true, e.st));
-        CHK(backward(e, nb));
-        RUN(sib_fold_batch(e.st, nb, s));
-        RUN(odb_adadelta(e.W, e.acc_g, e.acc_d, e.G, e.trainable, (int64_t)e.off.total, dlr, ep, s));
-        return MMLA_OK;
-      },
-      [&](const FitBufs& d, int v0, int nb) -> int {
-        RUN(odb_gather(static_cast<const uint8_t*>(d.val_x), d.val_labels, nullptr, nullptr, v0, nb, nv, img_bytes,
-                       e.xb, e.lb, e.mb, s));
-        return forward(e, nb, false, e.st + 5);
-      },
-      [&](int ep, float* row) -> int {
-        RUN(odb_end_epoch(e.st, n, nv, dlr, ep, row, s));
-        return MMLA_OK;
-      });
+  int32_t* sid = nullptr;
+  const int32_t* dids = nullptr;
+  uint8_t* dm = nullptr;
+  CHK(carve_slot(c, S_ODFT, [&](Carver& cv) -> int {
+    sid = cv.take<int32_t>(n);
+    CHK(st.in(cv, sample_ids, (size_t)n, &dids));
+    dm = st.out(cv, mask, (size_t)n * ODB_HEAD_D);
+    return MMLA_OK;
+  }));
+  RUN(sbb_ids(dids, nullptr, 0, (int)n, (int)n, sid, s));
+  RUN(odb_drop_mask((uint64_t)drop_seed, (uint32_t)epoch, sid, (int)n, dm, s));
+  CHK(st.back(mask, dm, (size_t)n * ODB_HEAD_D));
+  return finish(c, st.dev);
+}
+
+int mmla_od_auc(mmla_ctx* c, const float* probs, const int32_t* labels, int64_t n, float* auc_out, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  if (n < 1 || n > (1 << 24)) return fail(c, MMLA_E_INVALID, "od_auc: n %lld outside [1, 2^24]", (long long)n);
+  if (!probs || !labels || !auc_out) return fail(c, MMLA_E_INVALID, "od_auc: null pointer");
+  Stager st{c, (flags & MMLA_DEVICE_PTR) != 0};
+  if (!st.dev) CHK(check_labels(c, "labels", labels, n, 2, kLabelSet));
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const int S = odb_auc_slabs(n);
+  const float* dp = nullptr;
+  const int32_t* dl = nullptr;
+  uint32_t* counts = nullptr;
+  float* da = nullptr;
+  CHK(carve_slot(c, S_ODFT, [&](Carver& cv) -> int {
+    counts = cv.take<uint32_t>((size_t)S * ODB_AUC_COUNTS);
+    CHK(st.in(cv, probs, (size_t)n * 2, &dp));
+    CHK(st.in(cv, labels, (size_t)n, &dl));
+    da = st.out(cv, auc_out, 1);
+    return MMLA_OK;
+  }));
+  RUN(odb_auc_count(dp, dl, n, odb_auc_thresholds(), 0, counts, s));
+  RUN(odb_auc_final(counts, S, n, 0, da, s));
+  CHK(st.back(auc_out, da, 1));
+  return finish(c, st.dev);
+}
+
+int mmla_od_augment(mmla_ctx* c, const uint8_t* img, int64_t n, int32_t h, int32_t w, const int32_t* src,
+                    const int32_t* levels, int64_t m, uint8_t* out, uint32_t flags) {
+  if (!c) return MMLA_E_INVALID;
+  if (h < ODA_MIN_H || h > ODA_MAX_H || h % 2)
+    return fail(c, MMLA_E_INVALID, "od_augment: h %d is not an even size in [%d, %d]", h, ODA_MIN_H, ODA_MAX_H);
+  if (w < ODA_MIN_W || w > ODA_MAX_W || w % 2 == 0)
+    return fail(c, MMLA_E_INVALID, "od_augment: w %d is not an odd size in [%d, %d]", w, ODA_MIN_W, ODA_MAX_W);
+  if (n < 1 || n > (1 << 24)) return fail(c, MMLA_E_INVALID, "od_augment: n %lld outside [1, 2^24]", (long long)n);
+  if (m < 0 || m > (1 << 24)) return fail(c, MMLA_E_INVALID, "od_augment: m %lld outside [0, 2^24]", (long long)m);
+  if (!img || (m > 0 && (!src || !levels || !out))) return fail(c, MMLA_E_INVALID, "od_augment: null pointer");
+  Stager st{c, (flags & MMLA_DEVICE_PTR) != 0};
+  if (!st.dev)
+    for (int64_t k = 0; k < m; ++k) {
+      if (src[k] < 0 || src[k] >= n)
+        return fail(c, MMLA_E_INVALID, "od_augment: src[%lld] = %d outside [0, %lld)", (long long)k, src[k],
+                    (long long)n);
+      if (levels[k] < 0 || levels[k] > MMLA_OD_AUG_MAX_LEVELS)
+        return fail(c, MMLA_E_INVALID, "od_augment: levels[%lld] = %d outside [0, %d]", (long long)k, levels[k],
+                    MMLA_OD_AUG_MAX_LEVELS);
+    }
+  if (m == 0) return MMLA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const size_t img_bytes = (size_t)h * w * 3;
+  const uint8_t* di = nullptr;
+  const int32_t *ds = nullptr, *dl = nullptr;
+  uint8_t* dout = nullptr;
+  CHK(carve_slot(c, S_ODFT, [&](Carver& cv) -> int {
+    CHK(st.in(cv, img, (size_t)n * img_bytes, &di));
+    CHK(st.in(cv, src, (size_t)m, &ds));
+    CHK(st.in(cv, levels, (size_t)m, &dl));
+    dout = st.out(cv, out, (size_t)m * img_bytes);
+    return MMLA_OK;
+  }));
+  RUN(oda_augment(di, n, h, w, ds, dl, m, dout, s));
+  CHK(st.back(out, dout, (size_t)m * img_bytes));
+  return finish(c, st.dev);
 }
 
 }  // extern "C"

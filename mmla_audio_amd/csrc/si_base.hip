@@ -10,7 +10,7 @@
 // that same serial addition, so all of them see the same bits and no launch exists only to finalise.  S
 // depends on the shape alone: the same inputs give the same bits, and no atomics are used.
 //
-// Dropout: no mask array.  A keep-bit is a word of Philox4x32-10 (Salmon et al., SC'11) keyed by the
+// Dropout: no mask array.  A keep-bit is a word of Philox4x32-10 (philox.h) keyed by the
 // fit's seed and counted by (element / 4, sample id, epoch, site), recomputed wherever it is needed: in
 // the forward and backward of the avg-pool (site 0) and in the head (site 1).  sbb_drop_mask writes the
 // same bits out as bytes for the tests.
@@ -22,6 +22,8 @@
 
 #include <algorithm>
 
+#include "philox.h"
+
 namespace {
 
 constexpr float BN_EPS = 1e-3f;
@@ -30,31 +32,9 @@ constexpr float SCALE_A = 1.0f / 0.75f, SCALE_B = 1.0f / 0.8f;   // float32(1 / 
 
 inline dim3 grid1(int64_t n, int nt) { return dim3((unsigned)((n + nt - 1) / nt)); }
 
-// ---- Philox4x32-10 ------------------------------------------------------------------------------------
-
-struct U4 {
-  uint32_t v[4];
-};
-
-__device__ inline U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                   uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return U4{{c0, c1, c2, c3}};
-}
-
 // the four words of elements 4 q .. 4 q + 3 of one sample at one site
 __device__ inline U4 drop_words(const SbbDrop& d, int sample, uint32_t q, uint32_t site) {
-  return philox4x32_10(q, (uint32_t)d.sid[sample], d.epoch, site, (uint32_t)d.seed, (uint32_t)(d.seed >> 32));
+  return philox_drop_words(d.seed, d.epoch, (uint32_t)d.sid[sample], q, site);
 }
 
 __global__ void ids_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ order, int i0, int nb,

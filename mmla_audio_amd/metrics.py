@@ -56,6 +56,17 @@ def structural_similarity(im1, im2, *, win_size=None, gradient=False, data_range
     return np.float64(_lib.default_context().ssim_u8(a, b))
 
 
+def auc(probs, labels):
+    """``tf.keras.metrics.AUC()`` at its defaults, as ``OverlapDetector.train_model`` compiles it
+    (overlap_detector.py:403), through ``mmla_od_auc``: probs float32 [n, 2] against labels [n] in {0, 1} (or
+    their one-hot rows [n, 2]) -> float.  include/mmla.h states the thresholds and the one deliberate
+    deviation (the final sum in double)."""
+    labels = np.asarray(labels)
+    if labels.ndim == 2:
+        labels = labels.argmax(axis=1)
+    return float(_lib.default_context().od_auc(probs, labels))
+
+
 def compare_images(img1_path, img2_path, threshold=0.3):
     """``compare_images`` of record_on_pi.py:39-48: True ('silent') when the two PNG files' similarity
     is below the threshold.  The files are read as 3 channels (``cv2.imread`` drops alpha too, and its

@@ -1,12 +1,14 @@
-"""Adapting OD-NET to new labelled feature images on the GPU: the part of the reference's
-``OverlapDetection/scripts/overlap_detector.py`` that fits a trained detector further
-(``OverlapDetector.continue_train_model``, :480-509) -- Adadelta under the cosine learning-rate schedule,
-the class-weighted cross-entropy, early stopping -- through ``mmla_od_finetune`` (include/mmla.h, which
-states what is computed; parity with TensorFlow itself is unpinned).
+"""Training OD-NET on labelled feature images on the GPU: the fits of the reference's
+``OverlapDetection/scripts/overlap_detector.py``.  ``OverlapDetector.continue_train_model`` (:480-509) fits a
+trained detector further -- Adadelta under the cosine learning-rate schedule, the class-weighted
+cross-entropy, early stopping -- through ``mmla_od_finetune``; ``train_model`` (:392-451) trains one from the
+Keras initial state through ``mmla_od_train``, which adds keep-bits generated on the device, ModelCheckpoint
+and the AUC metric, after the pyramid-blur class balancing of ``augment_images`` (:143-220,
+``mmla_od_augment``).  include/mmla.h states what is computed; parity with TensorFlow and OpenCV themselves
+is unpinned.
 
-Not here: training from scratch (``train_model``, the initialisers), the pyramid-blur ``augment_images``,
-the xlsx / PNG dataset loaders, the ``AUC`` metric, ``restore_best_weights`` and the three-class variant of
-``evaluation``.
+Not here: the xlsx / PNG dataset loaders, ``StratifiedKFold``, ``restore_best_weights`` (the reference never
+sets it), the three-class variant of ``evaluation`` and multi-GPU training.
 """
 import math
 
@@ -63,3 +65,129 @@ def continue_train(W, images, labels, plan, epochs, batch_size, weighted=True, p
                                      cosine_lr(epochs), plan['perm'], plan['drop_mask'], epochs, batch_size,
                                      patience)
     return weights.unpack(weights.OD, out), hist, ran
+
+
+# ---- training from scratch: augment_images (:143-220), train_model (:392-451) -----------------------------
+
+HISTORY_KEYS = ('loss', 'categorical_accuracy', 'val_loss', 'val_categorical_accuracy', 'lr', 'auc', 'val_auc')
+
+
+class History:
+    """What ``model.fit`` returns, as far as the reference reads it: ``history`` is a dict of the Keras keys
+    (``HISTORY_KEYS``), one value per epoch run.  ``epochs_run`` and ``best_epoch`` (0-based, None if no
+    checkpoint was taken) say what the two callbacks did."""
+
+    def __init__(self, rows, epochs_run, best_epoch):
+        rows = np.asarray(rows, np.float32)[:epochs_run]
+        self.history = {k: [float(v) for v in rows[:, i]] for i, k in enumerate(HISTORY_KEYS)}
+        self.epoch = list(range(epochs_run))
+        self.epochs_run = int(epochs_run)
+        self.best_epoch = None if best_epoch < 0 else int(best_epoch)
+
+
+def _class_labels(y, what):
+    """labels [n] of integers, or one-hot rows [n, 2] as ``labels_loader`` returns them -> int32 [n]"""
+    y = np.asarray(y)
+    if y.ndim == 2:
+        if y.shape[1] != 2 or not (((y == 0) | (y == 1)).all() and (y.sum(axis=1) == 1).all()):
+            raise ValueError(f'{what} {y.shape}: expected one-hot rows of two classes')
+        return y.argmax(axis=1).astype(np.int32)
+    if y.ndim != 1 or not np.issubdtype(y.dtype, np.integer):
+        raise ValueError(f'{what} {y.shape} {y.dtype}: expected integer labels [n] or one-hot rows [n,2]')
+    return y.astype(np.int32)
+
+
+def augment_plan(labels, n_classes=None):
+    """The class balancing of ``augment_images`` (:158-166, :199-204) as indices: count[k] images per class,
+    base = max(count), ratio[k] = base / count[k] - 1, and for i in range(round(ratio[k])) -- Python's round,
+    half to even -- every image of class k gets a copy blurred i + 1 times.  -> (src, levels, new_labels),
+    int32 each: the originals in input order at level 0, then the copies by class, by i, by image.  n_classes
+    None: max(labels) + 1."""
+    labels = np.asarray(labels)
+    if labels.ndim != 1 or not np.issubdtype(labels.dtype, np.integer) or (labels.size and labels.min() < 0):
+        raise ValueError(f'labels {labels.shape} {labels.dtype}: expected non-negative integers [n]')
+    K = int(labels.max()) + 1 if n_classes is None and labels.size else int(n_classes or 0)
+    if labels.size and labels.max() >= K:
+        raise ValueError(f'label {int(labels.max())} outside the {K} classes')
+    count = [int((labels == k).sum()) for k in range(K)]
+    for k in range(K):
+        if count[k] == 0:
+            raise ValueError(f'class {k} has no images: its ratio base / count is undefined')
+    base = max(count) if K else 0
+    src, levels = [np.arange(len(labels))], [np.zeros(len(labels), np.int64)]
+    for k in range(K):
+        copies = round(base / count[k] - 1)
+        if copies > _lib.OD_AUG_MAX_LEVELS:
+            raise ValueError(f'class {k}: {copies} copies per image, more than the {_lib.OD_AUG_MAX_LEVELS} '
+                             f'levels built')
+        members = np.flatnonzero(labels == k)
+        for i in range(copies):
+            src.append(members)
+            levels.append(np.full(len(members), i + 1))
+    src = np.concatenate(src).astype(np.int32)
+    return src, np.concatenate(levels).astype(np.int32), labels[src].astype(np.int32)
+
+
+def augment_images(images, labels, ctx=None):
+    """``augment_images`` on arrays: images uint8 [n,h,w,3], labels [n] -> (images_aug [m,h,w,3], labels_aug
+    [m]) in ``augment_plan``'s order, the blurred copies through ``mmla_od_augment``."""
+    ctx = ctx if isinstance(ctx, _lib.Context) else _lib.default_context(ctx)
+    images = np.asarray(images)
+    if images.dtype != np.uint8 or images.ndim != 4 or images.shape[0] != len(labels):
+        raise ValueError(f'images {images.shape} {images.dtype}: expected uint8 [n,h,w,3], one per label')
+    src, levels, new_labels = augment_plan(labels)
+    return ctx.od_augment(images, src, levels), new_labels
+
+
+def train_model(x_train, y_train, x_val, y_val, *, epochs, batch_size, weighted=False, augmented=False, seed=0,
+                patience=10, checkpoint_path=None, save_path=None, device=None):
+    """``OverlapDetector.train_model`` on the device (``mmla_od_train``): ``__ResBLSTM`` from its Keras initial
+    state (``weights.initial_od(seed)``) under Adadelta with the cosine schedule, EarlyStopping(val_loss,
+    patience) and ModelCheckpoint(val_categorical_accuracy, save_best_only, 'max', period=1).  Images uint8
+    [n,h,w,3]; labels integers or one-hot rows.  augmented: the training set is balanced first
+    (``augment_images``); weighted: the loss's class weights are ``cal_weighted_penalty`` of the (possibly
+    augmented) training labels, else [1, 1].  x_val None or empty: no validation set, no callbacks.
+    -> (OverlapDetectionModel, History): the model holds the LAST epoch's weights (no restore_best_weights)
+    and is installed on the device.  The best checkpoint's weights go to checkpoint_path when one was taken,
+    the final model to save_path (``tfbundle.save_overlap``).  Everything random comes from `seed` through
+    numpy: the initial state, the order of every epoch (``fit_plan``'s generator) and the dropout seed;
+    TensorFlow's streams are not reproduced."""
+    import os
+
+    from . import models, tfbundle
+    ctx = device if isinstance(device, _lib.Context) else _lib.default_context(device)
+    x_train = np.asarray(x_train)
+    labels = _class_labels(y_train, 'y_train')
+    if x_train.dtype != np.uint8 or x_train.ndim != 4 or len(x_train) != len(labels):
+        raise ValueError(f'x_train {x_train.shape} {x_train.dtype}: expected uint8 [n,h,w,3], one per label')
+    nv = 0 if x_val is None else len(x_val)
+    vx = vl = None
+    if nv:
+        vx, vl = np.asarray(x_val), _class_labels(y_val, 'y_val')
+        if vx.dtype != np.uint8 or vx.shape[1:] != x_train.shape[1:] or len(vl) != nv:
+            raise ValueError(f'x_val {vx.shape} {vx.dtype}: expected uint8 [n,{x_train.shape[1]},'
+                             f'{x_train.shape[2]},3], one per label')
+    epochs = int(epochs)
+    if epochs < 0 or batch_size < 1:
+        raise ValueError('epochs must be >= 0 and batch_size >= 1')
+    if augmented:
+        src, levels, labels = augment_plan(labels, 2)
+        x_train = ctx.od_augment(x_train, src, levels)
+    cw = cal_weighted_penalty(np.eye(2)[labels]) if weighted else np.ones(2)
+    n = len(labels)
+    rng_p = np.random.default_rng([int(seed), 1])       # fit_plan's generator of the epochs' orders
+    perm = np.stack([rng_p.permutation(n) for _ in range(epochs)]).astype(np.int32) if epochs else \
+        np.zeros((0, n), np.int32)
+    drop_seed = int(np.random.default_rng([int(seed), 2]).integers(0, 2 ** 63))
+    W0 = weights.initial_od(seed)
+    out, best, hist, ran, best_ep = ctx.od_train(weights.pack(weights.OD, W0), x_train, labels, vx, vl, cw,
+                                                 cosine_lr(epochs), perm, epochs, batch_size, drop_seed, patience,
+                                                 1)
+    model = models.OverlapDetectionModel(weights.unpack(weights.OD, out), device=ctx)
+    if checkpoint_path is not None and best is not None:
+        os.makedirs(checkpoint_path, exist_ok=True)
+        tfbundle.save_overlap(checkpoint_path, weights.unpack(weights.OD, best))
+    if save_path is not None:
+        os.makedirs(save_path, exist_ok=True)
+        tfbundle.save_overlap(save_path, model.W)
+    return model, History(hist, ran, best_ep)

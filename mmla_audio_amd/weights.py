@@ -188,14 +188,25 @@ def initial(kind, seed=0, n_classes=None):
     moving mean 0, moving variance 1, orthogonal recurrent kernels, LSTM bias 0 with the forget block 1
     (``unit_forget_bias``).  The draws are numpy's (PCG64 seeded by ``seed``): the initialisers'
     distributions are Keras's, TensorFlow's generator is not reproduced, so no seed gives TensorFlow's
-    numbers.  OD-NET is trained only further here (``continue_train_model``), never from scratch.
+    numbers.  OD-NET's initial state has a name of its own, ``initial_od``.
     """
     if kind != SI:
         raise NotImplementedError('weights.initial: only the SI network is trained from scratch')
-    rng = np.random.default_rng(np.random.PCG64(0x696E6974 + 7919 * int(seed)))
+    return _initial(spec(kind, n_classes), 0x696E6974 + 7919 * int(seed))
+
+
+def initial_od(seed=0):
+    """The Keras initial state of ``__ResBLSTM`` (overlap_detector.py:362-390), what ``train_model`` starts
+    from: the same initialisers as ``initial`` over ``od_spec()``, with numpy's draws from a stream of its
+    own."""
+    return _initial(od_spec(), 0x696E6F64 + 7919 * int(seed))
+
+
+def _initial(items, stream):
+    rng = np.random.default_rng(np.random.PCG64(stream))
     fixed = {'bias': 0.0, 'bn_gamma': 1.0, 'bn_beta': 0.0, 'bn_mean': 0.0, 'bn_var': 1.0}
     W = {}
-    for name, shape, role in spec(kind, n_classes):
+    for name, shape, role in items:
         if role in ('kernel', 'lstm_kernel'):
             W[name] = _glorot(rng, shape)[0]
         elif role == 'lstm_rec':
