@@ -71,6 +71,8 @@ constexpr size_t kGuardBytes = 4u << 20;
 constexpr int kGuardByte = 0xA5;
 
 int ws_get(mmla_ctx* c, int slot, size_t bytes, void** out) {
+  const bool kept = slot_kept(slot);
+  if (kept && bytes < 256) bytes = 256;
   if ((int)c->ws.size() <= slot) {
     c->ws.resize(slot + 1, nullptr);
     c->ws_size.resize(slot + 1, 0);
@@ -88,7 +90,7 @@ int ws_get(mmla_ctx* c, int slot, size_t bytes, void** out) {
       c->ws_size[slot] = 0;
     }
     void* p = nullptr;
-    if (c->debug_fail_allocs > 0) {
+    if (c->debug_fail_allocs > 0 && !kept) {   // the hook: a workspace allocation inside a micro-batch
       --c->debug_fail_allocs;
       return fail(c, MMLA_E_OOM, "workspace slot %d: injected allocation failure (MMLA_DEBUG_FAIL_ALLOC)", slot);
     }
@@ -114,10 +116,10 @@ int ws_get(mmla_ctx* c, int slot, size_t bytes, void** out) {
   return MMLA_OK;
 }
 
-int ws_release(mmla_ctx* c) {
+int ws_release(mmla_ctx* c, bool kept_too) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (size_t i = 0; i < c->ws.size(); ++i)
-    if (c->ws[i]) {
+    if (c->ws[i] && (kept_too || !slot_kept((int)i))) {
       HIPCHK(c, hipFree(static_cast<char*>(c->ws[i]) - c->ws_guard[i]));
       c->ws[i] = nullptr;
       c->ws_size[i] = 0;
@@ -159,7 +161,7 @@ constexpr double kSiBytesPerClip = 4.0 * 256 * 32 * 4 + 256 * 39 * 4 + 8 * 128 *
                                    1024 * 4 + 64;
 
 // clips per micro-batch: the user's cap, else what the device's free memory holds (the slots this
-// context already owns count as free), capped at the default
+// context already owns and a retry would free, so not the kept ones, count as free), capped at the default
 int64_t microbatch(mmla_ctx* c, bool od) {
   const int64_t user = od ? c->od_mb : c->si_mb;
   if (user > 0) return user;
@@ -170,7 +172,8 @@ int64_t microbatch(mmla_ctx* c, bool od) {
     return cap;
   }
   double held = 0;
-  for (size_t b : c->ws_size) held += (double)b;
+  for (size_t i = 0; i < c->ws_size.size(); ++i)
+    if (!slot_kept((int)i)) held += (double)c->ws_size[i];
   int64_t fit = (int64_t)(((double)fr + held) * 0.9 / (od ? kOdBytesPerClip : kSiBytesPerClip));
   fit = fit / kMinMicrobatch * kMinMicrobatch;
   return std::max(kMinMicrobatch, std::min(cap, fit));
@@ -233,8 +236,8 @@ int mmla_create(int device, mmla_ctx** out) {
     return MMLA_E_HIP;
   }
   c->stream = c->own_stream;
-  if (hipMalloc(&c->range_dev, 4 * sizeof(int)) != hipSuccess ||
-      hipMemset(c->range_dev, 0, 4 * sizeof(int)) != hipSuccess ||
+  if (hipMalloc(&c->range_dev, RW_COUNT * sizeof(int)) != hipSuccess ||
+      hipMemset(c->range_dev, 0, RW_COUNT * sizeof(int)) != hipSuccess ||
       hipHostMalloc(&c->range_host, 2 * sizeof(int), hipHostMallocDefault) != hipSuccess) {
     mmla_destroy(c);
     return MMLA_E_HIP;
@@ -290,8 +293,6 @@ int mmla_destroy(mmla_ctx* c) {
   if (c->range_dev) (void)hipFree(c->range_dev);
   if (c->vad_state) (void)hipFree(c->vad_state);
   if (c->cap_state) (void)hipFree(c->cap_state);
-  for (void* p : c->cap_buf)
-    if (p) (void)hipFree(p);
   if (c->range_host) (void)hipHostFree(c->range_host);
   if (c->range_map) (void)hipHostFree(c->range_map);
   if (c->pin_out) (void)hipHostFree(c->pin_out);
@@ -329,16 +330,16 @@ int mmla_range_check(mmla_ctx* c, int64_t* f32_reruns) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (f32_reruns) *f32_reruns = c->range_reruns;
   int flag = 0, timeout = 0;
-  HIPCHK(c, hipMemcpy(&flag, c->range_dev, sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(&timeout, c->range_dev + 3, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(&flag, c->range_dev + RW_DEV_RANGE, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(&timeout, c->range_dev + RW_DEV_TIMEOUT, sizeof(int), hipMemcpyDeviceToHost));
   if (timeout) {
-    HIPCHK(c, hipMemset(c->range_dev + 3, 0, sizeof(int)));
+    HIPCHK(c, hipMemset(c->range_dev + RW_DEV_TIMEOUT, 0, sizeof(int)));
     return fail(c, MMLA_E_HIP,
                 "a device-pointer call since the last check ran the split BiLSTM and one of its "
                 "workgroups timed out waiting for the others: its probabilities are NaN; re-run it");
   }
   if (flag) {
-    HIPCHK(c, hipMemset(c->range_dev, 0, sizeof(int)));
+    HIPCHK(c, hipMemset(c->range_dev + RW_DEV_RANGE, 0, sizeof(int)));
     return fail(c, MMLA_E_RANGE,
                 "a device-pointer call since the last check split an operand outside the fp16 "
                 "range (|x| >= 65504): its results are not valid; re-run it with MMLA_PREC_F32");
@@ -366,14 +367,7 @@ int mmla_get_microbatch(mmla_ctx* c, int64_t* od_clips, int64_t* si_clips) {
 int mmla_release_workspace(mmla_ctx* c) {
   if (!c) return MMLA_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
-  CHK(ws_release(c));   // (the stream has drained)
-  for (int i = 0; i < kCapBufs; ++i)   // the capture conversion's and the mix's buffers; the states stay
-    if (c->cap_buf[i]) {
-      HIPCHK(c, hipFree(c->cap_buf[i]));
-      c->cap_buf[i] = nullptr;
-      c->cap_bytes[i] = 0;
-    }
-  return MMLA_OK;
+  return ws_release(c, true);   // the kept slots too; the capture and detector states stay
 }
 
 int mmla_set_precision(mmla_ctx* c, int mode) {

@@ -2,8 +2,10 @@
 // workspace slots and the error / launch macros.
 //   context.cpp      context, profiler, workspace; create / destroy / setters / profile entry points
 //   weights.cpp      take_*, mmla_load_weights
-//   net_runners.cpp  conv_spatial, lstm_run, run_od_net, run_si_net (which kernel runs which block)
-//   pipeline.cpp     staging, micro-batching, the range guard; feature / forward / pipeline entry points
+//   net_runners.cpp  conv_spatial, lstm_run, run_od_net, run_si_net (which kernel runs which block), each in
+//                    the arithmetic of its Arith argument
+//   pipeline.cpp     staging, micro-batching, the range guard (it builds each pass's Arith); feature /
+//                    forward / pipeline entry points
 //   capi.cpp         the auxiliary entry points and the head trainer (mmla_si_head_fit)
 //   fit_common.h     what the trainers share, host code only: Carver / carve_slot, staged operands (Stager),
 //                    check_perm / check_labels, wire_lstm / mark_trainable and the fit driver (fit_check, fit)
@@ -102,7 +104,11 @@ constexpr int64_t kMinMicrobatch = 64;
 constexpr size_t kPinSlotBytes = 64u << 10;
 constexpr size_t kPinInBytes = 1u << 20;
 constexpr int kPinSlots = 4;   // S_OUT0 .. S_OUT3
-constexpr int kCapBufs = 7;    // mmla_ctx::cap_buf (enum CapBuf)
+
+// the words of mmla_ctx::range_dev: an operand outside the fp16 range, or a split-BiLSTM workgroup that
+// gave up waiting, in a device-pointer call (sticky until mmla_range_check) or in the current pass of a
+// host-pointer micro-batch (pipeline.cpp guarded(): re-run); the two host words are neighbours
+enum RangeWord { RW_DEV_RANGE = 0, RW_HOST_RANGE, RW_HOST_TIMEOUT, RW_DEV_TIMEOUT, RW_COUNT };
 
 }  // namespace mmla
 
@@ -133,7 +139,7 @@ struct mmla_ctx {
   int64_t od_mb_cap = mmla::kOdMicrobatch, si_mb_cap = mmla::kSiMicrobatch;   // default caps of the automatic size
   int debug_fail_allocs = 0;   // test hook (env MMLA_DEBUG_FAIL_ALLOC at create): fail this many workspace allocations
   int debug_trace_guard = 0;   // test hook (env MMLA_DEBUG_TRACE_GUARD at create): mmla_debug_od_trace under the range guard
-  int precision = MMLA_PREC_F16X3;
+  int precision = MMLA_PREC_F16X3;   // mmla_set_precision: the user's setting (a pass runs its Arith)
   // SI res units as fused launches of siu.hip's one template, siu_chain_kernel<..., POOL, NU, FIN, ...>
   // (net_runners.cpp si_choose); env MMLA_NO_SIU=1 at create: two conv_h3 launches per unit (A/B)
   bool siu = true;
@@ -179,13 +185,12 @@ struct mmla_ctx {
   // test hook (env MMLA_DEBUG_LSTM_SPIN at create): the split BiLSTM's wait bound in polls (0 = default,
   // < 0 = give up at the first wait)
   int lstm_spin = 0;
-  // 3xFP16 range guard: kernels set range_dev[0] (device-pointer calls; sticky until
-  // mmla_range_check) or range_dev[1] (host-pointer micro-batches: re-run in exact f32) when an
-  // operand they split into fp16 is >= 65504 in magnitude or not finite.  The split BiLSTM's wait
-  // timeout (bilstm_h3_split_kernel) likewise: range_dev[3] (device-pointer calls, sticky) or
-  // range_dev[2] (host-pointer micro-batches: re-run on the one-workgroup-per-direction kernel)
+  // 3xFP16 range guard: kernels set a word of range_dev [RW_COUNT] (enum RangeWord) when an operand they
+  // split into fp16 is >= 65504 in magnitude or not finite (host-pointer micro-batches: re-run in exact
+  // f32), the split BiLSTM (bilstm_h3_split_kernel) when a wait timed out (host-pointer micro-batches:
+  // re-run on the one-workgroup-per-direction kernel)
   int* range_dev = nullptr;
-  int* range_host = nullptr;                // pinned copy of range_dev[1..2]
+  int* range_host = nullptr;                // pinned copy of range_dev[RW_HOST_RANGE .. RW_HOST_TIMEOUT]
   // small host-pointer calls (the real-time loops' batch-1 case): the range flag and the outputs live
   // in host-mapped coherent memory that the kernels write over the bus, so a micro-batch ends with one
   // stream synchronisation and host memcpys instead of three or four device-to-host copies, a flag
@@ -197,12 +202,9 @@ struct mmla_ctx {
   char* pin_out = nullptr;        // kPinSlots x kPinSlotBytes, host view
   char* pin_out_dev = nullptr;
   char* pin_in = nullptr;         // kPinInBytes of pinned input staging: one DMA for PCM + lens
-  int* range_ptr = nullptr;                 // what the current launches write (null: unguarded)
-  int* timeout_ptr = nullptr;               // where the split BiLSTM reports a timeout (null: nowhere)
   int64_t lstm_split_reruns = 0;
   int64_t range_reruns = 0;
   bool od_f32_only = false, si_f32_only = false;   // weights outside the fp16 range
-  bool loading_f16_bad = false;                     // mmla_load_weights / mmla_si_set_head scratch
   bool si_base_f16_bad = false;   // a non-finite tensor below the SI head (si_f32_only = this or the head's)
   // mmla_vad_reset: webrtcvad.Vad(mode) per stream (device), [2 * vad_streams]: the second half
   // holds the states a conditioned micro-batch started from, for its re-runs (pipeline.cpp)
@@ -216,11 +218,6 @@ struct mmla_ctx {
   int cap_cur = 0;
   int64_t cap_streams = 0;
   int32_t cap_rate = 0, cap_channels = 0, cap_channel = 0, cap_ir = 0, cap_or = 0;
-  // the conversion's buffers (mmla::CapBuf).  Not workspace slots: an allocation failure in the
-  // conditioned micro-batches behind the conversion frees every slot (ws_release), and the re-run must
-  // find the converted clips
-  void* cap_buf[mmla::kCapBufs] = {};
-  size_t cap_bytes[mmla::kCapBufs] = {};
   // noise gate (nr.hip): tables + the bank of noise profiles' thresholds [nr_profiles][513]
   NrTables* nr_tables = nullptr;
   float* nr_thresh = nullptr;
@@ -278,17 +275,21 @@ enum Slot {
   // then the call's staged host-pointer operands; carved anew by every call (carve_slot)
   S_FT,
   S_MIX, S_MIX_LEN,  // mmla_od_mix / mmla_od_pipeline_mixed: a micro-batch's mixed clips and their lengths
-  S_ODFT   // mmla_od_loss_grad / mmla_od_finetune / mmla_od_train: likewise for the OD blob; the staged
+  S_ODFT,  // mmla_od_loss_grad / mmla_od_finetune / mmla_od_train: likewise for the OD blob; the staged
            // operands of mmla_od_drop_mask, mmla_od_auc and mmla_od_augment
+  // kept slots: a call fills them once, in front of its micro-batches, so they outlive the ws_release
+  // before a repeated micro-batch, are not what microbatch() can reclaim, and are at least 256 bytes.
+  // A capture conversion's staged raw clips, host frame counts, per-clip entry (d0, prev), converted
+  // clips and their lengths; a host-pointer mix's pool and plan
+  S_KEPT_BEGIN,
+  S_CAP_RAW = S_KEPT_BEGIN, S_CAP_FRAMES, S_CAP_ITEM, S_CAP_CLIPS, S_CAP_LENS, S_MIX_POOL, S_MIX_PLAN,
+  S_KEPT_END
 };
-
-// mmla_ctx::cap_buf: staged raw capture, host frames, per-clip entry (d0, prev), converted clips and
-// their lengths; the pool and the plan of a host-pointer mix (they, too, must outlive a micro-batch that
-// is repeated after an allocation failure)
-enum CapBuf { CB_RAW = 0, CB_FRAMES, CB_ITEM, CB_OUT, CB_LENS, CB_MIX_POOL, CB_MIX_PLAN };
+inline bool slot_kept(int slot) { return slot >= S_KEPT_BEGIN && slot < S_KEPT_END; }
 
 int ws_get(mmla_ctx* c, int slot, size_t bytes, void** out);
-int ws_release(mmla_ctx* c);   // free every workspace slot (after the stream drains)
+// free every workspace slot once the stream has drained; the kept ones only with kept_too
+int ws_release(mmla_ctx* c, bool kept_too = false);
 int64_t microbatch(mmla_ctx* c, bool od);
 // the end of every entry point that launched: the last error, host-mode synchronisation, guard bands
 int finish(mmla_ctx* c, bool dev);
@@ -355,6 +356,18 @@ int copy_back(mmla_ctx* c, T* user, int64_t off, const T* d, size_t count, bool 
 
 // ---- network runners (net_runners.cpp): device pointers, one micro-batch -----------------------
 
+// The arithmetic of one pass over a micro-batch: the runners, their kernel choices and their
+// kernel-argument fillers read it from this argument and nothing of it from the context
+struct Arith {
+  int prec;                  // MMLA_PREC_*
+  bool split;                // the split BiLSTM may run
+  int* range = nullptr;      // the word the kernels flag an out-of-range operand in (null: unguarded)
+  int* timeout = nullptr;    // ... and the split BiLSTM a timeout (null: nowhere)
+  bool h3() const { return prec == MMLA_PREC_F16X3; }
+};
+// the user's settings, unguarded: front-end and conditioning bodies, the debug trace
+inline Arith unguarded(const mmla_ctx* c) { return Arith{c->precision, c->lstm_split}; }
+
 // the OD 'silent' gate of one micro-batch: fewer than 4000 samples (record_on_pc.py:141-154; device
 // lens (nullable) or clip_len), or the similarity of the clip's image to its denoised image below a
 // threshold (record_on_pi.py:103-124; device ssim, nullable); silent output (nullable)
@@ -366,10 +379,10 @@ struct OdGate {
   float ssim_threshold = 0.0f;
 };
 
-int run_od_net(mmla_ctx* c, const uint8_t* img_u8, const float* img_f32, int64_t n, float* probs,
-               int32_t* argmax, OdGate gate = OdGate(), int stop = -1, const float** tap = nullptr,
-               int64_t* tap_n = nullptr);
-int run_si_net(mmla_ctx* c, const float* x, int64_t n, float* probs, int32_t* argmax,
+int run_od_net(mmla_ctx* c, const Arith& ar, const uint8_t* img_u8, const float* img_f32, int64_t n,
+               float* probs, int32_t* argmax, OdGate gate = OdGate(), int stop = -1,
+               const float** tap = nullptr, int64_t* tap_n = nullptr);
+int run_si_net(mmla_ctx* c, const Arith& ar, const float* x, int64_t n, float* probs, int32_t* argmax,
                const uint8_t* silent, int ldx = SI_D, const float** tap = nullptr);
 
 }  // namespace mmla

@@ -1,8 +1,9 @@
 // libmmla network runners: OD-NET and SI-NET on one device micro-batch.  Which kernel runs each OD
 // res block is decided in od_choose(), which launch covers each SI res unit in si_choose() (pool-chain,
 // pair, single unit, conv pair in that order).  One filler per kernel argument struct, one FLOP
-// formula per block kind, one tail that advances the state.  DESIGN.md ("Where the dispatch lives")
-// says how to add a path.
+// formula per block kind, one tail that advances the state.  Precision, the split BiLSTM and the range
+// words of a run are its Arith argument (internal.h), never the context's.  DESIGN.md ("Where the
+// dispatch lives") says how to add a path.
 #include <algorithm>
 
 #include "conv.h"
@@ -90,12 +91,12 @@ ConvH3Args conv_h3_args(const ConvW& w, const float* x, float* y, int n, int h, 
 // pool_out: write MaxPool2D(2,'same') of the output instead of the output (OD pool blocks).
 // sc / sc_x (pool_out only): the block's shortcut Conv2D(1x1, stride 2) of sc_x, added to the pooled
 // output inside the same launch
-int conv_spatial(mmla_ctx* c, const ConvW& w, const float* x, float* y, int n, int h, int wd,
+int conv_spatial(mmla_ctx* c, const Arith& ar, const ConvW& w, const float* x, float* y, int n, int h, int wd,
                  const BnW* bn, int pro, int epi, const float* res, bool pool_out = false,
                  int pool_in_h = 0, const ConvW* sc = nullptr, const float* sc_x = nullptr,
                  int sc_h = 0) {
-  if (c->precision == MMLA_PREC_F16X3 && w.wh) {
-    ConvH3Args a = conv_h3_args(w, x, y, n, h, wd, bn, pro, epi, res, c->range_ptr);
+  if (ar.h3() && w.wh) {
+    ConvH3Args a = conv_h3_args(w, x, y, n, h, wd, bn, pro, epi, res, ar.range);
     double sc_flops = 0.0;
     if (sc && sc_x) {
       a.sc_x = sc_x;
@@ -131,18 +132,18 @@ int ws_floats(mmla_ctx* c, int slot, size_t count, float** out) {
 double lstm_flops(int64_t n, int T, int D) { return 2.0 * n * T * 2 * (256.0 + D) * 1024.0; }
 
 // BiLSTM on the 3xFP16 path when enabled (exact-f32 MFMA kernel otherwise)
-hipError_t lstm_run(mmla_ctx* c, const LstmW& L, const float* seq, int64_t n, int T, float* out) {
-  if (c->precision == MMLA_PREC_F16X3 && L.wth[0] && c->lstm_split &&
+hipError_t lstm_run(mmla_ctx* c, const Arith& ar, const LstmW& L, const float* seq, int64_t n, int T, float* out) {
+  if (ar.h3() && L.wth[0] && ar.split &&
       n <= std::min(c->lstm_split_max, bilstm_h3_split_max_clips())) {
     void* ws = nullptr;   // small batches (the real-time calls): each direction over eight CUs
     if (ws_get(c, S_LSTM, bilstm_h3_split_ws_bytes(), &ws) != MMLA_OK) return hipErrorOutOfMemory;
     return bilstm_h3_split_launch(seq, (int)n, T, 128, L.wth[0], L.wtl[0], L.wth[1], L.wtl[1],
-                                  L.bias[0], L.bias[1], out, c->range_ptr, L.ws[0], L.ws[1], ws,
-                                  c->timeout_ptr, c->lstm_spin, c->stream);
+                                  L.bias[0], L.bias[1], out, ar.range, L.ws[0], L.ws[1], ws,
+                                  ar.timeout, c->lstm_spin, c->stream);
   }
-  if (c->precision == MMLA_PREC_F16X3 && L.wth[0])
+  if (ar.h3() && L.wth[0])
     return bilstm_h3_launch(seq, (int)n, T, 128, L.wth[0], L.wtl[0], L.wth[1], L.wtl[1], L.bias[0],
-                            L.bias[1], out, c->range_ptr, L.ws[0], L.ws[1], c->stream);
+                            L.bias[1], out, ar.range, L.ws[0], L.ws[1], c->stream);
   return bilstm_launch(seq, (int)n, T, 128, L.wcat[0], L.wcat[1], L.bias[0], L.bias[1], out,
                        c->stream);
 }
@@ -189,9 +190,9 @@ bool odu_ok(const ResUnitW& B, bool pool, int h, int w) {
 }
 
 // stop: the debug trace's last stage (-1: none); a trace of the stem alone (0) needs it in HBM
-OdChoice od_choose(const mmla_ctx* c, const ResUnitW& B, int b, int h, int w, int stop) {
+OdChoice od_choose(const mmla_ctx* c, const Arith& ar, const ResUnitW& B, int b, int h, int w, int stop) {
   OdChoice k{OD_PAIR, false, 1, false, false};
-  if (c->precision != MMLA_PREC_F16X3) return k;
+  if (!ar.h3()) return k;
   if (c->rbs && strips_ok(B, POOL[b], h, w)) {
     k.path = OD_STRIPS;
     k.w1_lds = c->rbs_w1l && !POOL[b];
@@ -282,15 +283,15 @@ double od_block_flops(const ResUnitW& B, bool pool, int64_t n, int h, int w) {
 
 // the block as one launch per conv: X -> T1 -> the result, which is X itself for an identity block
 // (the residual is added in place) and T1 for a pool block (T2 holds the unpooled or pooled conv(4,1))
-int od_block_pair(mmla_ctx* c, const ResUnitW& B, bool pool, int n, int h, int w, float* X, float*& T1,
-                  float*& T2, float** out) {
-  CHK(conv_spatial(c, B.ca, X, T1, n, h, w, &B.bn_in, PRO_BN_ELU, EPI_BIAS, nullptr));
+int od_block_pair(mmla_ctx* c, const Arith& ar, const ResUnitW& B, bool pool, int n, int h, int w, float* X,
+                  float*& T1, float*& T2, float** out) {
+  CHK(conv_spatial(c, ar, B.ca, X, T1, n, h, w, &B.bn_in, PRO_BN_ELU, EPI_BIAS, nullptr));
   if (!pool) {
     *out = X;
-    return conv_spatial(c, B.cb, T1, X, n, h, w, &B.bn_mid, PRO_BN_ELU, EPI_ADD, X);
+    return conv_spatial(c, ar, B.cb, T1, X, n, h, w, &B.bn_mid, PRO_BN_ELU, EPI_ADD, X);
   }
-  if (c->precision != MMLA_PREC_F16X3) {
-    CHK(conv_spatial(c, B.cb, T1, T2, n, h, w, &B.bn_mid, PRO_BN_ELU, EPI_BIAS, nullptr));
+  if (!ar.h3()) {
+    CHK(conv_spatial(c, ar, B.cb, T1, T2, n, h, w, &B.bn_mid, PRO_BN_ELU, EPI_BIAS, nullptr));
     // shortcut Conv2D(1x1, stride 2) + MaxPool2D(2, 'same')(t2), fused
     ConvArgs s = conv_args(B.sc, X, T1, n, h, w, 2, nullptr, PRO_NONE, EPI_ADD_POOL, T2);
     s.hp = h;
@@ -298,13 +299,13 @@ int od_block_pair(mmla_ctx* c, const ResUnitW& B, bool pool, int n, int h, int w
     CHK(conv_run(c, s));
   } else if (B.sc.wh && B.sc.cout == B.cb.cout && B.cb.cout_pad == B.sc.cout_pad) {
     // conv(4,1) + MaxPool2D(2,'same') + the shortcut Conv2D(1x1, stride 2) of X + Add, one launch
-    CHK(conv_spatial(c, B.cb, T1, T2, n, h, w, &B.bn_mid, PRO_BN_ELU, EPI_BIAS, nullptr, true, 0, &B.sc,
+    CHK(conv_spatial(c, ar, B.cb, T1, T2, n, h, w, &B.bn_mid, PRO_BN_ELU, EPI_BIAS, nullptr, true, 0, &B.sc,
                      X));
     std::swap(T1, T2);
   } else {
     // conv(4,1) with MaxPool2D(2,'same') fused into its epilogue -> T2 at half resolution;
     // then shortcut Conv2D(1x1, stride 2) + pooled T2
-    CHK(conv_spatial(c, B.cb, T1, T2, n, h, w, &B.bn_mid, PRO_BN_ELU, EPI_BIAS, nullptr, true));
+    CHK(conv_spatial(c, ar, B.cb, T1, T2, n, h, w, &B.bn_mid, PRO_BN_ELU, EPI_BIAS, nullptr, true));
     CHK(conv_run(c, conv_args(B.sc, X, T1, n, h, w, 2, nullptr, PRO_NONE, EPI_ADD, T2)));
   }
   *out = T1;
@@ -318,8 +319,8 @@ namespace mmla __attribute__((visibility("hidden"))) {
 // OD-NET on a device batch; input = uint8 image (img_u8) or float NHWC (img_f32).
 // `stop` >= 0 (debug trace): return after stage `stop` (0 stem, 1..9 res blocks, 10 mean, 11
 // BiLSTM) with *tap / *tap_n set to that stage's output tensor.
-int run_od_net(mmla_ctx* c, const uint8_t* img_u8, const float* img_f32, int64_t n, float* probs,
-               int32_t* argmax, OdGate gate, int stop, const float** tap, int64_t* tap_n) {
+int run_od_net(mmla_ctx* c, const Arith& ar, const uint8_t* img_u8, const float* img_f32, int64_t n,
+               float* probs, int32_t* argmax, OdGate gate, int stop, const float** tap, int64_t* tap_n) {
   const OdNet& W = c->od;
   const size_t big = (size_t)n * OD_PIX * 32;
   float *X, *T1, *T2, *SEQ, *H;
@@ -329,7 +330,7 @@ int run_od_net(mmla_ctx* c, const uint8_t* img_u8, const float* img_f32, int64_t
   CHK(ws_floats(c, S_SEQ, (size_t)n * 19 * 128, &SEQ));
   CHK(ws_floats(c, S_HOUT, (size_t)n * 512, &H));
   const double stem_flops = 2.0 * n * OD_PIX * 3 * 16;
-  const OdChoice first = od_choose(c, W.blk[0], 0, OD_H, OD_W, stop);
+  const OdChoice first = od_choose(c, ar, W.blk[0], 0, OD_H, OD_W, stop);
   if (!first.stem)
     LAUNCH(c, MMLA_STAGE_GLUE, stem_flops,
            od_stem_launch(img_u8, img_f32, n * OD_PIX, W.stem.cout_pad, W.stem.wt, W.stem.bias, X,
@@ -343,7 +344,7 @@ int run_od_net(mmla_ctx* c, const uint8_t* img_u8, const float* img_f32, int64_t
   for (int b = 0; b < 9; ++b) {   // res_block, overlap_detector_temp.py:253-277
     const ResUnitW& B = W.blk[b];
     const bool pool = POOL[b];
-    const OdChoice k = b == 0 ? first : od_choose(c, B, b, h, w, stop);
+    const OdChoice k = b == 0 ? first : od_choose(c, ar, B, b, h, w, stop);
     // a fused stem's FLOPs are booked with the block that computes it
     const double flops = od_block_flops(B, pool, n, h, w) + (k.stem ? stem_flops : 0.0);
     float* out = T1;   // where the block's output lands
@@ -351,7 +352,7 @@ int run_od_net(mmla_ctx* c, const uint8_t* img_u8, const float* img_f32, int64_t
       case OD_STRIPS:
       case OD_TILES: {
         const bool tiles = k.path == OD_TILES;
-        const ResBlkArgs r = resblk_args(B, pool, tiles, X, T1, n, h, w, c->range_ptr,
+        const ResBlkArgs r = resblk_args(B, pool, tiles, X, T1, n, h, w, ar.range,
                                          k.stem ? &W.stem : nullptr, img_u8, img_f32);
         LAUNCH(c, MMLA_STAGE_CONV, flops,
                tiles ? resblk_launch(r, B.ca.cin, B.ca.cout, pool, c->stream)
@@ -359,13 +360,13 @@ int run_od_net(mmla_ctx* c, const uint8_t* img_u8, const float* img_f32, int64_t
         break;
       }
       case OD_ODU: {   // t1 stays in LDS, bit-identical to the pair
-        const OduArgs o = odu_args(B, pool, X, T1, n, c->range_ptr);
+        const OduArgs o = odu_args(B, pool, X, T1, n, ar.range);
         LAUNCH(c, MMLA_STAGE_CONV, flops,
                odu_launch(o, h, w, B.ca.cin, B.ca.cout, pool, k.strips, c->stream));
         break;
       }
       case OD_PAIR:
-        CHK(od_block_pair(c, B, pool, (int)n, h, w, X, T1, T2, &out));
+        CHK(od_block_pair(c, ar, B, pool, (int)n, h, w, X, T1, T2, &out));
         break;
     }
     // the tail every block runs through: pooled size, the output becomes X, trace tap
@@ -389,7 +390,7 @@ int run_od_net(mmla_ctx* c, const uint8_t* img_u8, const float* img_f32, int64_t
     return MMLA_OK;
   }
   LAUNCH(c, MMLA_STAGE_LSTM, lstm_flops(n, w, 128),
-         lstm_run(c, W.lstm, SEQ, n, w, H));
+         lstm_run(c, ar, W.lstm, SEQ, n, w, H));
   if (stop == 11) {
     *tap = H;
     *tap_n = n * 512;
@@ -425,8 +426,8 @@ bool sipu_ok(const ResUnitW& U, int cin) {
 
 // how many units the siu.hip launch that starts at unit u covers: a pool unit with the two units
 // after it or alone, two units without pooling or one; 0: the unit runs as conv_h3 / exact-f32 launches
-int si_choose(const mmla_ctx* c, const SiNet& W, int u) {
-  if (!c->siu || c->precision != MMLA_PREC_F16X3) return 0;
+int si_choose(const mmla_ctx* c, const Arith& ar, const SiNet& W, int u) {
+  if (!c->siu || !ar.h3()) return 0;
   const int cin = W.unit[u].ca.cin, C = W.unit[u].ca.cout;
   auto plain = [&](int v) { return v < 9 && !POOL[v] && siu_ok(W.unit[v], C); };
   if (POOL[u]) {
@@ -481,7 +482,7 @@ namespace mmla __attribute__((visibility("hidden"))) {
 // ldx: the features' row stride (39, or 40 from si_fe with a zero 40th column: the stem then stages
 // 16-B aligned rows, conv_h3's float4 path, bit-identical -- its weights' padded channels are zero)
 // tap != null: stop after the BiLSTM and return its output (base_model.layers[-2].output) in *tap
-int run_si_net(mmla_ctx* c, const float* x, int64_t n, float* probs, int32_t* argmax,
+int run_si_net(mmla_ctx* c, const Arith& ar, const float* x, int64_t n, float* probs, int32_t* argmax,
                const uint8_t* silent, int ldx, const float** tap) {
   const SiNet& W = c->si;
   const size_t big = (size_t)n * SI_T * 32;
@@ -494,19 +495,19 @@ int run_si_net(mmla_ctx* c, const float* x, int64_t n, float* probs, int32_t* ar
   CHK(ws_floats(c, S_HOUT, (size_t)n * 512, &H));
   CHK(ws_floats(c, S_LOGIT, (size_t)n * W.dense.cout_pad, &L));
   int t = SI_T;
-  const bool h3 = c->precision == MMLA_PREC_F16X3;
+  const bool h3 = ar.h3();
   bool fused_final = false;   // the last unit wrote BN + ReLU + AvgPool4 itself (siu FIN)
   // Conv1D(32, 4, same): [n, 256, 1, 39] -> [n, 256, 1, 32] (speaker_identification.py:195)
   ConvW stem = W.stem;
   if (ldx == SI_D + 1 && h3 && stem.wh && stem.cin_pad > SI_D) stem.cin = ldx;
   else if (ldx != SI_D) return fail(c, MMLA_E_INVALID, "padded SI features need the 3xFP16 stem");
-  CHK(conv_spatial(c, stem, x, X, (int)n, t, 1, nullptr, PRO_NONE, EPI_BIAS, nullptr));
+  CHK(conv_spatial(c, ar, stem, x, X, (int)n, t, 1, nullptr, PRO_NONE, EPI_BIAS, nullptr));
   for (int u = 0; u < 9; ++u) {   // res_unit, speaker_identification.py:168-190
     const ResUnitW& U = W.unit[u];
     const int cin = U.ca.cin;
     const bool pool = POOL[u];
     const int tp = pool ? (t + 1) / 2 : t;
-    const int units = si_choose(c, W, u);
+    const int units = si_choose(c, ar, W, u);
     float* out = R;   // where the unit's (or the chain's) output lands
     if (units > 0) {
       // the units in one launch (siu.hip): MaxPool1D in the staging, every t1 and the outputs between
@@ -516,7 +517,7 @@ int run_si_net(mmla_ctx* c, const float* x, int64_t n, float* probs, int32_t* ar
       double flops = 0.0;
       for (int k = 0; k < units; ++k) {
         const bool first = k == 0;
-        s[k] = siu_args(W.unit[u + k], first ? X : nullptr, k == units - 1 ? R : nullptr, n, tp, c->range_ptr,
+        s[k] = siu_args(W.unit[u + k], first ? X : nullptr, k == units - 1 ? R : nullptr, n, tp, ar.range,
                         first && pool ? t : 0);
         flops += si_unit_flops(W.unit[u + k], first && pool, n, tp);
       }
@@ -535,24 +536,24 @@ int run_si_net(mmla_ctx* c, const float* x, int64_t n, float* probs, int32_t* ar
     } else if (pool) {
       if (h3 && U.ca.wh) {
         // MaxPool1D(2, same) taken inside the conv's staging (conv_h3.hip PIN)
-        CHK(conv_spatial(c, U.ca, X, T1, (int)n, tp, 1, &U.bn_in, PRO_BN_RELU, EPI_BIAS, nullptr,
+        CHK(conv_spatial(c, ar, U.ca, X, T1, (int)n, tp, 1, &U.bn_in, PRO_BN_RELU, EPI_BIAS, nullptr,
                          false, t));
       } else {
         LAUNCH(c, MMLA_STAGE_GLUE, (double)n * t * cin,
                maxpool_t2_launch(X, (int)n, t, cin, XP, c->stream));
-        CHK(conv_spatial(c, U.ca, XP, T1, (int)n, tp, 1, &U.bn_in, PRO_BN_RELU, EPI_BIAS, nullptr));
+        CHK(conv_spatial(c, ar, U.ca, XP, T1, (int)n, tp, 1, &U.bn_in, PRO_BN_RELU, EPI_BIAS, nullptr));
       }
       if (h3 && U.cb.wh && U.sc.wh && U.sc.cout == U.cb.cout && U.sc.cout_pad == U.cb.cout_pad) {
         // Conv1D(3) + the shortcut Conv1D(1, stride 2) of X as its residual + Add, one launch
-        CHK(conv_spatial(c, U.cb, T1, R, (int)n, tp, 1, &U.bn_mid, PRO_BN_RELU, EPI_ADD, nullptr, false,
+        CHK(conv_spatial(c, ar, U.cb, T1, R, (int)n, tp, 1, &U.bn_mid, PRO_BN_RELU, EPI_ADD, nullptr, false,
                          0, &U.sc, X, t));
       } else {
         CHK(conv_run(c, conv_args(U.sc, X, R, (int)n, t, 1, 2, nullptr, PRO_NONE, EPI_BIAS, nullptr)));
-        CHK(conv_spatial(c, U.cb, T1, R, (int)n, tp, 1, &U.bn_mid, PRO_BN_RELU, EPI_ADD, R));
+        CHK(conv_spatial(c, ar, U.cb, T1, R, (int)n, tp, 1, &U.bn_mid, PRO_BN_RELU, EPI_ADD, R));
       }
     } else {
-      CHK(conv_spatial(c, U.ca, X, T1, (int)n, t, 1, &U.bn_in, PRO_BN_RELU, EPI_BIAS, nullptr));
-      CHK(conv_spatial(c, U.cb, T1, X, (int)n, t, 1, &U.bn_mid, PRO_BN_RELU, EPI_ADD, X));
+      CHK(conv_spatial(c, ar, U.ca, X, T1, (int)n, t, 1, &U.bn_in, PRO_BN_RELU, EPI_BIAS, nullptr));
+      CHK(conv_spatial(c, ar, U.cb, T1, X, (int)n, t, 1, &U.bn_mid, PRO_BN_RELU, EPI_ADD, X));
       out = X;
     }
     // the tail every unit runs through: the output becomes X, pooled rows
@@ -565,7 +566,7 @@ int run_si_net(mmla_ctx* c, const float* x, int64_t n, float* probs, int32_t* ar
            bn_relu_avgpool4_launch(X, (int)n, t, 128, W.final_bn.scale, W.final_bn.shift,
                                    SEQ, c->stream));
   LAUNCH(c, MMLA_STAGE_LSTM, lstm_flops(n, t / 4, 128),
-         lstm_run(c, W.lstm, SEQ, n, t / 4, H));
+         lstm_run(c, ar, W.lstm, SEQ, n, t / 4, H));
   if (tap) {   // mmla_si_embed: the BiLSTM output [n, 512] itself, no Dense, no head
     *tap = H;
     return MMLA_OK;
@@ -575,7 +576,7 @@ int run_si_net(mmla_ctx* c, const float* x, int64_t n, float* probs, int32_t* ar
     // all cout_pad columns are written (the padding columns: zero weights and bias), so the logits
     // keep the cout_pad row stride the head reads
     ConvH3Args a = conv_h3_args(W.dense, H, L, (int)n, 1, 1, nullptr, PRO_NONE, EPI_BIAS, nullptr,
-                                c->range_ptr);
+                                ar.range);
     a.cout = W.dense.cout_pad;
     LAUNCH(c, MMLA_STAGE_HEAD, 2.0 * n * W.dense.cin * W.dense.cout, conv_h3_launch(a, c->stream));
   } else {

@@ -110,50 +110,39 @@ int for_microbatches(mmla_ctx* c, bool od, int64_t n, F&& body, int64_t granule 
   return MMLA_OK;
 }
 
-// one micro-batch of a network call under the 3xFP16 range guard.  Device-pointer calls let the
-// kernels flag into range_dev[0] (sticky, reported by mmla_range_check / mmla_synchronize);
-// host-pointer calls check range_dev[1] after the micro-batch and re-run it in exact f32 when an
+// one micro-batch of a network call under the 3xFP16 range guard: body(ar) runs it in the arithmetic
+// ar, built here per pass from the context's settings, which no pass changes.  Device-pointer calls let
+// the kernels flag into range_dev's sticky words (reported by mmla_range_check / mmla_synchronize);
+// host-pointer calls check their own words after the micro-batch and re-run it in exact f32 when an
 // operand left the fp16 range.  f32_only: the model's weights are outside the fp16 range.
 template <class F>
 int guarded(mmla_ctx* c, bool dev, bool f32_only, F&& body) {
-  struct Restore {   // precision, split switch and flag targets of the context, restored on every return
-    mmla_ctx* c;
-    int prec;
-    bool split;
-    ~Restore() {
-      c->precision = prec;
-      c->lstm_split = split;
-      c->range_ptr = nullptr;
-      c->timeout_ptr = nullptr;
-    }
-  } restore{c, c->precision, c->lstm_split};
-  if (f32_only) c->precision = MMLA_PREC_F32;
-  if (c->precision != MMLA_PREC_F16X3) {
-    c->range_ptr = nullptr;
-    return body();
-  }
+  Arith ar = unguarded(c);
+  if (f32_only) ar.prec = MMLA_PREC_F32;
+  if (!ar.h3()) return body(ar);
   if (dev) {
-    c->range_ptr = c->range_dev;
-    c->timeout_ptr = c->range_dev + 3;
-    return body();
+    ar.range = c->range_dev + RW_DEV_RANGE;
+    ar.timeout = c->range_dev + RW_DEV_TIMEOUT;
+    return body(ar);
   }
   // one pass of the micro-batch; -> its range flag and split-BiLSTM timeout flag
   auto pass = [&](bool* flagged, bool* timed_out) -> int {
     if (c->pin_small && c->range_map) {   // the flags in host-mapped memory: no memset, no copy
-      c->range_ptr = c->range_map_dev;
-      c->timeout_ptr = c->range_map_dev + 1;
+      ar.range = c->range_map_dev;
+      ar.timeout = c->range_map_dev + 1;
       reinterpret_cast<volatile int*>(c->range_map)[0] = 0;   // host calls leave the stream idle
       reinterpret_cast<volatile int*>(c->range_map)[1] = 0;
-      CHK(body());
+      CHK(body(ar));
       HIPCHK(c, hipStreamSynchronize(c->stream));
       *flagged = reinterpret_cast<volatile int*>(c->range_map)[0] != 0;
       *timed_out = reinterpret_cast<volatile int*>(c->range_map)[1] != 0;
     } else {
-      c->range_ptr = c->range_dev + 1;
-      c->timeout_ptr = c->range_dev + 2;
-      HIPCHK(c, hipMemsetAsync(c->range_ptr, 0, 2 * sizeof(int), c->stream));
-      CHK(body());
-      HIPCHK(c, hipMemcpyAsync(c->range_host, c->range_ptr, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      static_assert(RW_HOST_TIMEOUT == RW_HOST_RANGE + 1, "one memset, one copy for both host words");
+      ar.range = c->range_dev + RW_HOST_RANGE;
+      ar.timeout = c->range_dev + RW_HOST_TIMEOUT;
+      HIPCHK(c, hipMemsetAsync(ar.range, 0, 2 * sizeof(int), c->stream));
+      CHK(body(ar));
+      HIPCHK(c, hipMemcpyAsync(c->range_host, ar.range, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
       *flagged = c->range_host[0] != 0;
       *timed_out = c->range_host[1] != 0;
@@ -163,24 +152,22 @@ int guarded(mmla_ctx* c, bool dev, bool f32_only, F&& body) {
   bool flagged = false, timed_out = false;
   CHK(pass(&flagged, &timed_out));
   if (timed_out) {   // a split-BiLSTM workgroup gave up waiting (NaN outputs): the unsplit kernel,
-    c->lstm_split = false;   // the same arithmetic bit for bit
+    ar.split = false;   // the same arithmetic bit for bit
     c->lstm_split_reruns += 1;
     CHK(pass(&flagged, &timed_out));
     if (timed_out) return fail(c, MMLA_E_HIP, "BiLSTM timed out without the split kernel");
   }
   if (flagged) {
-    c->precision = MMLA_PREC_F32;
-    c->range_ptr = nullptr;
-    c->timeout_ptr = nullptr;
     c->range_reruns += 1;
-    CHK(body());
+    CHK(body(Arith{MMLA_PREC_F32, ar.split}));
   }
   return MMLA_OK;
 }
 
 // The skeleton of the entry points over clips [0, n): null check, argument check (bad_args: the
-// message, or null), hipSetDevice, then body(c0, cnt, dev) per micro-batch with the host-mode
-// synchronisation behind it, then finish.
+// message, or null), hipSetDevice, then body(c0, cnt, dev, ar) per micro-batch with the host-mode
+// synchronisation behind it, then finish.  ar: the guard's arithmetic of this pass for a network call, the
+// unguarded one (for what the body runs outside its own guards) for every other.
 //   FEATURES_*  a front-end call: in device mode one launch over the caller's buffers
 //   NET_*       a network call: needs that model's weights; every micro-batch under the range guard
 //   COND_*      a conditioned call (OD, SI, or both for a room): needs the weights of every network it
@@ -205,19 +192,21 @@ int clip_call(mmla_ctx* c, CallKind kind, int64_t n, uint32_t flags, const char*
   const bool net = kind == NET_OD || kind == NET_SI, cond = kind >= COND_OD;
   HIPCHK(c, hipSetDevice(c->device));
   const bool dev = flags & MMLA_DEVICE_PTR;
-  auto once = [&](int64_t c0, int64_t cnt) -> int {
-    CHK(body(c0, cnt, dev));
+  auto once = [&](int64_t c0, int64_t cnt, const Arith& ar) -> int {
+    CHK(body(c0, cnt, dev, ar));
     if (!dev) HIPCHK(c, hipStreamSynchronize(c->stream));
     return MMLA_OK;
   };
   if (net) {
     CHK(for_microbatches(c, od, n, [&](int64_t c0, int64_t cnt) -> int {
-      return guarded(c, dev, od ? c->od_f32_only : c->si_f32_only, [&]() -> int { return once(c0, cnt); });
+      return guarded(c, dev, od ? c->od_f32_only : c->si_f32_only,
+                     [&](const Arith& ar) -> int { return once(c0, cnt, ar); });
     }, granule));
   } else if (dev && !cond) {
-    if (n > 0) CHK(once(0, n));
+    if (n > 0) CHK(once(0, n, unguarded(c)));
   } else {
-    CHK(for_microbatches(c, od, n, once, granule));
+    CHK(for_microbatches(c, od, n, [&](int64_t c0, int64_t cnt) -> int { return once(c0, cnt, unguarded(c)); },
+                         granule));
   }
   return finish(c, dev);
 }
@@ -295,12 +284,12 @@ int od_features_common(mmla_ctx* c, const T* pcm, int64_t n, int64_t stride, con
                 (long long)(c0 + cnt - 1));
   };
   return clip_call(c, FEATURES_OD, n, flags, bad_pcm_args(pcm, n, stride, lens, clip_len) ? "bad pcm args" : nullptr,
-                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+                   [&](int64_t c0, int64_t cnt, bool dev, const Arith&) -> int {
     PcmT<T> p;
     CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, MMLA_OD_CLIP, dev, &p));
     OdFeArgs a = od_fe_args(c, p);
     if constexpr (std::is_same<T, float>::value) {
-      a.range_flag = dev ? c->range_dev : c->range_dev + 1;
+      a.range_flag = c->range_dev + (dev ? RW_DEV_RANGE : RW_HOST_RANGE);
       if (!dev) HIPCHK(c, hipMemsetAsync(a.range_flag, 0, sizeof(int), c->stream));
     }
     CHK(out_ptr(c, db, c0 * OD_PIX, cnt * OD_PIX, dev, S_OUT0, &a.db));
@@ -315,7 +304,7 @@ int od_features_common(mmla_ctx* c, const T* pcm, int64_t n, int64_t stride, con
     if (std::is_same<T, float>::value && !dev) {   // the range word, once the launch has drained
       HIPCHK(c, hipStreamSynchronize(c->stream));
       int flag = 0;
-      HIPCHK(c, hipMemcpy(&flag, c->range_dev + 1, sizeof(int), hipMemcpyDeviceToHost));
+      HIPCHK(c, hipMemcpy(&flag, c->range_dev + RW_HOST_RANGE, sizeof(int), hipMemcpyDeviceToHost));
       if (flag) return host_range_error(c0, cnt);
     }
     return MMLA_OK;
@@ -327,14 +316,14 @@ int od_forward_common(mmla_ctx* c, const float* x_f32, const uint8_t* x_u8, int6
                       uint32_t flags) {
   const bool bad = n < 0 || (n > 0 && ((!x_f32 && !x_u8) || !probs));
   return clip_call(c, NET_OD, n, flags, bad ? "bad od_forward args" : nullptr,
-                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+                   [&](int64_t c0, int64_t cnt, bool dev, const Arith& ar) -> int {
     const float* df = nullptr;
     const uint8_t* du = nullptr;
     if (x_f32) CHK(in_ptr(c, x_f32 + c0 * OD_IMG, cnt * OD_IMG, dev, S_IN, &df));
     else CHK(in_ptr(c, x_u8 + c0 * OD_IMG, cnt * OD_IMG, dev, S_IMG, &du));
     float* dp;
     CHK(out_ptr(c, probs, c0 * 2, cnt * 2, dev, S_OUT0, &dp));
-    CHK(run_od_net(c, du, df, cnt, dp, nullptr));
+    CHK(run_od_net(c, ar, du, df, cnt, dp, nullptr));
     return copy_back(c, probs, c0 * 2, dp, cnt * 2, dev);
   });
 }
@@ -369,8 +358,8 @@ int od_image(mmla_ctx* c, const Pcm& p, int64_t cnt, int slot, const uint8_t** i
 
 // OD-NET on a micro-batch's images with the 'silent' gate on the lengths of p (and on g's SSIM fields,
 // where the caller set them), results into probs / argmax / silent at clip c0
-int od_net_out(mmla_ctx* c, const uint8_t* img, const Pcm& p, OdGate g, int64_t c0, int64_t cnt, bool dev,
-               float* probs, int32_t* argmax, uint8_t* silent) {
+int od_net_out(mmla_ctx* c, const Arith& ar, const uint8_t* img, const Pcm& p, OdGate g, int64_t c0, int64_t cnt,
+               bool dev, float* probs, int32_t* argmax, uint8_t* silent) {
   float* dp;
   int32_t* da;
   CHK(out_ptr(c, probs, c0 * 2, cnt * 2, dev, S_OUT0, &dp));
@@ -378,18 +367,18 @@ int od_net_out(mmla_ctx* c, const uint8_t* img, const Pcm& p, OdGate g, int64_t 
   CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT2, &g.silent));
   g.lens = p.lens;
   g.clip_len = p.true_len;
-  CHK(run_od_net(c, img, nullptr, cnt, dp, da, g));
+  CHK(run_od_net(c, ar, img, nullptr, cnt, dp, da, g));
   CHK(copy_back(c, probs, c0 * 2, dp, cnt * 2, dev));
   CHK(copy_back(c, argmax, c0, da, cnt, dev));
   return copy_back(c, silent, c0, g.silent, cnt, dev);
 }
 
 // OD front-end + network of one micro-batch on the device view p of its clips
-int od_fe_net(mmla_ctx* c, const Pcm& p, int64_t c0, int64_t cnt, bool dev, float* probs, int32_t* argmax,
-              uint8_t* silent) {
+int od_fe_net(mmla_ctx* c, const Arith& ar, const Pcm& p, int64_t c0, int64_t cnt, bool dev, float* probs,
+              int32_t* argmax, uint8_t* silent) {
   const uint8_t* img;
   CHK(od_image(c, p, cnt, S_IMG, &img));
-  return od_net_out(c, img, p, OdGate(), c0, cnt, dev, probs, argmax, silent);
+  return od_net_out(c, ar, img, p, OdGate(), c0, cnt, dev, probs, argmax, silent);
 }
 
 // the fused OD pipeline; `gated` adds the denoise-and-compare silence gate of record_on_pi.py:103-124
@@ -404,10 +393,10 @@ int od_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t strid
     if (nr_passes < 0) bad = "nr_passes < 0";
     else if (nr_passes > 0 && !ns && !c->nr_ready) bad = "nr_passes > 0: mmla_nr_set_noise must be called first";
   }
-  return clip_call(c, NET_OD, n, flags, bad, [&](int64_t c0, int64_t cnt, bool dev) -> int {
+  return clip_call(c, NET_OD, n, flags, bad, [&](int64_t c0, int64_t cnt, bool dev, const Arith& ar) -> int {
     Pcm p;
     CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, MMLA_OD_CLIP, dev || pcm_dev, &p));
-    if (!gated) return od_fe_net(c, p, c0, cnt, dev, probs, argmax, silent);
+    if (!gated) return od_fe_net(c, ar, p, c0, cnt, dev, probs, argmax, silent);
     const uint8_t *img, *net_img;
     CHK(od_image(c, p, cnt, S_IMG, &img));
     net_img = img;
@@ -438,20 +427,19 @@ int od_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t strid
     OdGate g;
     g.ssim = dss;
     g.ssim_threshold = ssim_threshold;
-    CHK(od_net_out(c, net_img, p, g, c0, cnt, dev, probs, argmax, silent));
+    CHK(od_net_out(c, ar, net_img, p, g, c0, cnt, dev, probs, argmax, silent));
     return copy_back(c, ssim, c0, static_cast<const float*>(dss), cnt, dev);
   });
 }
 
 // SI front-end + network of one micro-batch on the device view p of its clips, results into probs /
 // argmax / silent at clip c0 (host mode: staged in the output slots slot_p / slot_a)
-int si_fe_net(mmla_ctx* c, const Pcm& p, int64_t c0, int64_t cnt, bool dev, float* probs,
+int si_fe_net(mmla_ctx* c, const Arith& ar, const Pcm& p, int64_t c0, int64_t cnt, bool dev, float* probs,
               int32_t* argmax, uint8_t* silent, int slot_p = S_OUT0, int slot_a = S_OUT1) {
   const int k = c->si.k;
   void* pf;
   // the features stay on the device: rows of 40 floats when the 3xFP16 stem reads them
-  const int ldf = c->precision == MMLA_PREC_F16X3 && c->si.stem.wh && c->si.stem.cin_pad > SI_D &&
-                          c->si_pad_feat ? SI_D + 1 : SI_D;
+  const int ldf = ar.h3() && c->si.stem.wh && c->si.stem.cin_pad > SI_D && c->si_pad_feat ? SI_D + 1 : SI_D;
   CHK(ws_get(c, S_FEAT, cnt * SI_T * ldf * sizeof(float), &pf));
   uint8_t* pso = nullptr;   // host mode: the caller's 'silent' flags through an output slot
   if (!dev && silent) CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT2, &pso));
@@ -466,7 +454,7 @@ int si_fe_net(mmla_ctx* c, const Pcm& p, int64_t c0, int64_t cnt, bool dev, floa
   int32_t* da;
   CHK(out_ptr(c, probs, c0 * k, cnt * k, dev, slot_p, &dp));
   CHK(out_ptr(c, argmax, c0, cnt, dev, slot_a, &da));
-  CHK(run_si_net(c, a.feat, cnt, dp, da, a.silent, ldf));
+  CHK(run_si_net(c, ar, a.feat, cnt, dp, da, a.silent, ldf));
   CHK(copy_back(c, probs, c0 * k, dp, cnt * k, dev));
   CHK(copy_back(c, argmax, c0, da, cnt, dev));
   if (silent && dev)
@@ -617,7 +605,7 @@ struct Conditioner {
 // mmla_condition once cd.bad() has passed: FEATURES_* micro-batching (host mode), one pass over the whole
 // batch (device mode)
 int condition_call(mmla_ctx* c, Conditioner& cd, uint32_t flags) {
-  return clip_call(c, FEATURES_OD, cd.n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev) -> int {
+  return clip_call(c, FEATURES_OD, cd.n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev, const Arith&) -> int {
     return cd.run(c, c0, cnt, dev);
   }, std::max<int64_t>(cd.ips, 1));
 }
@@ -626,10 +614,10 @@ int si_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t strid
                        int32_t clip_len, float* probs, int32_t* argmax, uint8_t* silent, uint32_t flags,
                        bool pcm_dev = false) {
   return clip_call(c, NET_SI, n, flags, bad_pcm_args(pcm, n, stride, lens, clip_len) ? "bad pcm args" : nullptr,
-                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+                   [&](int64_t c0, int64_t cnt, bool dev, const Arith& ar) -> int {
     Pcm p;
     CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, SI_NEED_SAMPLES, dev || pcm_dev, &p));
-    return si_fe_net(c, p, c0, cnt, dev, probs, argmax, silent);
+    return si_fe_net(c, ar, p, c0, cnt, dev, probs, argmax, silent);
   });
 }
 
@@ -664,16 +652,16 @@ int conditioned_body(mmla_ctx* c, CallKind kind, Conditioner& cd, const NetOut& 
   // alone; an allocation failure repeats the micro-batch with fewer clips, the detectors restored by
   // Conditioner::run's snapshot.  With OD in the call, 'silent' (kept_len < 4000) is its gate's: SI's own
   // flag, the same rule, stays in the workspace, and SI's outputs are staged in slots of their own.
-  return clip_call(c, kind, cd.n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev) -> int {
+  return clip_call(c, kind, cd.n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev, const Arith&) -> int {
     CHK(cd.run(c, c0, cnt, dev));
     const Pcm p{cd.q, cd.clip_len, cd.kept, cd.clip_len, 0};
     if (od)
-      CHK(guarded(c, dev, c->od_f32_only, [&]() -> int {
-        return od_fe_net(c, p, c0, cnt, dev, o.od_probs, o.od_argmax, o.silent);
+      CHK(guarded(c, dev, c->od_f32_only, [&](const Arith& ar) -> int {
+        return od_fe_net(c, ar, p, c0, cnt, dev, o.od_probs, o.od_argmax, o.silent);
       }));
     if (si)
-      CHK(guarded(c, dev, c->si_f32_only, [&]() -> int {
-        return si_fe_net(c, p, c0, cnt, dev, o.si_probs, o.si_argmax, od ? nullptr : o.silent,
+      CHK(guarded(c, dev, c->si_f32_only, [&](const Arith& ar) -> int {
+        return si_fe_net(c, ar, p, c0, cnt, dev, o.si_probs, o.si_argmax, od ? nullptr : o.silent,
                          od ? S_ROOM_P : S_OUT0, od ? S_ROOM_A : S_OUT1);
       }));
     return MMLA_OK;
@@ -685,26 +673,6 @@ int conditioned_body(mmla_ctx* c, CallKind kind, Conditioner& cd, const NetOut& 
 // raw capture staged per piece of a host-pointer conversion (whole streams; one stream where a stream
 // is larger)
 constexpr size_t kCapStageBytes = 64u << 20;
-
-int cap_get(mmla_ctx* c, int which, size_t bytes, void** out) {
-  if (bytes < 256) bytes = 256;
-  if (c->cap_bytes[which] < bytes) {
-    if (c->cap_buf[which]) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipFree(c->cap_buf[which]));
-      c->cap_buf[which] = nullptr;
-      c->cap_bytes[which] = 0;
-    }
-    if (hipMalloc(&c->cap_buf[which], bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      c->cap_buf[which] = nullptr;
-      return fail(c, MMLA_E_OOM, "hipMalloc(%zu) failed for capture buffer %d", bytes, which);
-    }
-    c->cap_bytes[which] = bytes;
-  }
-  *out = c->cap_buf[which];
-  return MMLA_OK;
-}
 
 // One conversion: interleaved capture clips -> 16 kHz mono.  fresh: from fresh states, the context's
 // left alone (a whole recording); else on the states mmla_capture_reset created, advanced once.
@@ -740,19 +708,19 @@ struct Capture {
     if (n == 0) return MMLA_OK;
     const int nch = c->cap_channels;
     void *pitem = nullptr, *pfr = nullptr, *praw = nullptr;
-    CHK(cap_get(c, CB_ITEM, (size_t)n * 2 * sizeof(int32_t), &pitem));
+    CHK(ws_get(c, S_CAP_ITEM, (size_t)n * 2 * sizeof(int32_t), &pitem));
     const int32_t* dframes = frames;
     const int64_t row = (int64_t)clip_frames * nch;
     int64_t piece = n;
     if (!dev) {
       if (frames) {
-        CHK(cap_get(c, CB_FRAMES, (size_t)n * sizeof(int32_t), &pfr));
+        CHK(ws_get(c, S_CAP_FRAMES, (size_t)n * sizeof(int32_t), &pfr));
         HIPCHK(c, hipMemcpyAsync(pfr, frames, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         dframes = static_cast<const int32_t*>(pfr);
       }
       piece = std::max<int64_t>(ips, (int64_t)(kCapStageBytes / ((size_t)row * sizeof(int16_t))) / ips * ips);
       piece = std::min(piece, n);
-      CHK(cap_get(c, CB_RAW, (size_t)piece * row * sizeof(int16_t), &praw));
+      CHK(ws_get(c, S_CAP_RAW, (size_t)piece * row * sizeof(int16_t), &praw));
     }
     const int64_t ns = c->cap_streams;
     for (int64_t c0 = 0; c0 < n; c0 += piece) {
@@ -796,7 +764,7 @@ struct Capture {
 // mmla_condition (kind FEATURES_OD) and mmla_{od,si,room}_pipeline_conditioned.  cap: the _capture calls,
 // whose arguments describe the converted clips (the pointers only as non-null marks) -- every check first,
 // then the conversion of all clips once, then the conditioned pipeline on the converted clips, which stay
-// in the context's capture buffers
+// in the context's kept slots (internal.h)
 int conditioned_call(mmla_ctx* c, CallKind kind, const Capture* cap, const int16_t* pcm, int64_t n,
                      int64_t stride, const int32_t* lens, int32_t clip_len, const int32_t* profile,
                      int32_t nr_passes, int32_t silence_remove, int64_t ips, int16_t* out_pcm,
@@ -810,8 +778,8 @@ int conditioned_call(mmla_ctx* c, CallKind kind, const Capture* cap, const int16
   if (cap) {
     HIPCHK(c, hipSetDevice(c->device));
     void *pout = nullptr, *plens = nullptr;
-    CHK(cap_get(c, CB_OUT, (size_t)n * clip_len * sizeof(int16_t), &pout));
-    CHK(cap_get(c, CB_LENS, (size_t)n * sizeof(int32_t), &plens));
+    CHK(ws_get(c, S_CAP_CLIPS, (size_t)n * clip_len * sizeof(int16_t), &pout));
+    CHK(ws_get(c, S_CAP_LENS, (size_t)n * sizeof(int32_t), &plens));
     CHK(cap->run(c, dev, static_cast<int16_t*>(pout), clip_len, static_cast<int32_t*>(plens)));
     cd.pcm = static_cast<const int16_t*>(pout);
     cd.lens = static_cast<const int32_t*>(plens);
@@ -837,7 +805,7 @@ int capture_pipeline(mmla_ctx* c, CallKind kind, const int16_t* pcm, int64_t n, 
 static_assert(MIX_MAX_LAYERS == MMLA_MIX_MAX_LAYERS, "mix.h and mmla.h disagree");
 
 // A mix call's pool and plan.  check() is every test that needs no device; stage() gives the device view
-// (host mode: one upload per call into buffers that outlive the micro-batches).
+// (host mode: one upload per call into kept slots, which outlive a repeated micro-batch).
 struct Mix {
   const int16_t* pool;
   int64_t pool_len, n;
@@ -880,12 +848,12 @@ struct Mix {
       return MMLA_OK;
     }
     void *pp = nullptr, *pd = nullptr;
-    CHK(cap_get(c, CB_MIX_POOL, (size_t)pool_len * sizeof(int16_t), &pp));
+    CHK(ws_get(c, S_MIX_POOL, (size_t)pool_len * sizeof(int16_t), &pp));
     if (pool_len > 0)
       HIPCHK(c, hipMemcpyAsync(pp, pool, (size_t)pool_len * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
     // offsets first (8-byte aligned), then lengths, positions, layer counts
     const size_t m = (size_t)n * MMLA_MIX_MAX_LAYERS;
-    CHK(cap_get(c, CB_MIX_PLAN, m * 16 + (size_t)n * 4, &pd));
+    CHK(ws_get(c, S_MIX_PLAN, m * 16 + (size_t)n * 4, &pd));
     char* d = static_cast<char*>(pd);
     const hipMemcpyKind k = hipMemcpyHostToDevice;
     HIPCHK(c, hipMemcpyAsync(d, src_off, m * 8, k, c->stream));
@@ -938,7 +906,7 @@ int mmla_od_mix(mmla_ctx* c, const int16_t* pool, int64_t pool_len, int64_t n, c
   HIPCHK(c, hipSetDevice(c->device));
   MixArgs all;
   CHK(mix.stage(c, dev0, &all));
-  return clip_call(c, FEATURES_OD, n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev) -> int {
+  return clip_call(c, FEATURES_OD, n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev, const Arith&) -> int {
     if (dev) return mix_run(c, all, c0, cnt, clip_len, out + c0 * out_stride, out_stride, out_len ? out_len + c0 : nullptr);
     void *pm = nullptr, *pl = nullptr;
     CHK(ws_get(c, S_MIX, (size_t)cnt * clip_len * sizeof(int16_t), &pm));
@@ -966,14 +934,14 @@ int mmla_od_pipeline_mixed(mmla_ctx* c, const int16_t* pool, int64_t pool_len, i
   CHK(mix.stage(c, dev0, &all));
   // Per micro-batch: the mix into S_MIX / S_MIX_LEN, then mmla_od_pipeline's body on those clips with lens =
   // out_len under the range guard (a guard re-run repeats the network alone on the clips already mixed)
-  return clip_call(c, COND_OD, n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev) -> int {
+  return clip_call(c, COND_OD, n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev, const Arith&) -> int {
     void *pm = nullptr, *pl = nullptr;
     CHK(ws_get(c, S_MIX, (size_t)cnt * MMLA_OD_CLIP * sizeof(int16_t), &pm));
     CHK(ws_get(c, S_MIX_LEN, (size_t)cnt * sizeof(int32_t), &pl));
     CHK(mix_run(c, all, c0, cnt, MMLA_OD_CLIP, static_cast<int16_t*>(pm), MMLA_OD_CLIP, static_cast<int32_t*>(pl)));
     const Pcm p{static_cast<const int16_t*>(pm), MMLA_OD_CLIP, static_cast<const int32_t*>(pl), MMLA_OD_CLIP, 0};
-    return guarded(c, dev, c->od_f32_only, [&]() -> int {
-      return od_fe_net(c, p, c0, cnt, dev, probs, argmax, silent);
+    return guarded(c, dev, c->od_f32_only, [&](const Arith& ar) -> int {
+      return od_fe_net(c, ar, p, c0, cnt, dev, probs, argmax, silent);
     });
   });
 }
@@ -995,7 +963,7 @@ int mmla_si_features(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stride,
                      uint32_t flags) {
   const bool bad = bad_pcm_args(pcm, n, stride, lens, clip_len) || (n > 0 && !feat);
   return clip_call(c, FEATURES_SI, n, flags, bad ? "bad pcm/feat args" : nullptr,
-                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+                   [&](int64_t c0, int64_t cnt, bool dev, const Arith&) -> int {
     Pcm p;
     CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, SI_NEED_SAMPLES, dev, &p));
     SiFeArgs a = si_fe_args(c, p);
@@ -1084,7 +1052,7 @@ int mmla_si_enrol_embed(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stri
   // sequence front-end on the conditioned int16 with lens = kept_len, then SI-NET up to the BiLSTM on the
   // cnt * w_max windows in micro-batches of that many windows, each under mmla_si_embed's range guard.
   // A window's embedding does not depend on where it sits in a batch, so neither size enters the result
-  return clip_call(c, COND_SI, n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev) -> int {
+  return clip_call(c, COND_SI, n, flags, nullptr, [&](int64_t c0, int64_t cnt, bool dev, const Arith&) -> int {
     CHK(cd.run(c, c0, cnt, dev));
     const int64_t nwin = cnt * w_max;
     void *pf = nullptr, *pw = nullptr;
@@ -1108,9 +1076,9 @@ int mmla_si_enrol_embed(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stri
     const int64_t mb = std::max<int64_t>(1, microbatch(c, false));
     for (int64_t w0 = 0; w0 < nwin; w0 += mb) {
       const int64_t wc = std::min(mb, nwin - w0);
-      CHK(guarded(c, dev, c->si_f32_only, [&]() -> int {
+      CHK(guarded(c, dev, c->si_f32_only, [&](const Arith& ar) -> int {
         const float* h = nullptr;
-        CHK(run_si_net(c, a.feat + w0 * SI_T * SI_D, wc, nullptr, nullptr, nullptr, SI_D, &h));
+        CHK(run_si_net(c, ar, a.feat + w0 * SI_T * SI_D, wc, nullptr, nullptr, nullptr, SI_D, &h));
         HIPCHK(c, hipMemcpyAsync(emb + (c0 * w_max + w0) * MMLA_SI_EMBED, h,
                                  (size_t)wc * MMLA_SI_EMBED * sizeof(float), kind, c->stream));
         return MMLA_OK;
@@ -1131,13 +1099,13 @@ int mmla_od_forward_u8(mmla_ctx* c, const uint8_t* img, int64_t n, float* probs,
 int mmla_si_forward(mmla_ctx* c, const float* x, int64_t n, float* probs, uint32_t flags) {
   const bool bad = n < 0 || (n > 0 && (!x || !probs));
   return clip_call(c, NET_SI, n, flags, bad ? "bad si_forward args" : nullptr,
-                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+                   [&](int64_t c0, int64_t cnt, bool dev, const Arith& ar) -> int {
     const int k = c->si.k;
     const float* dx;
     CHK(in_ptr(c, x + c0 * SI_T * SI_D, cnt * SI_T * SI_D, dev, S_IN, &dx));
     float* dp;
     CHK(out_ptr(c, probs, c0 * k, cnt * k, dev, S_OUT0, &dp));
-    CHK(run_si_net(c, dx, cnt, dp, nullptr, nullptr));
+    CHK(run_si_net(c, ar, dx, cnt, dp, nullptr, nullptr));
     return copy_back(c, probs, c0 * k, dp, cnt * k, dev);
   });
 }
@@ -1145,10 +1113,10 @@ int mmla_si_forward(mmla_ctx* c, const float* x, int64_t n, float* probs, uint32
 int mmla_si_embed(mmla_ctx* c, const float* x, int64_t n, float* emb, uint32_t flags) {
   const bool bad = n < 0 || (n > 0 && (!x || !emb));
   return clip_call(c, NET_SI, n, flags, bad ? "bad si_embed args" : nullptr,
-                   [&](int64_t c0, int64_t cnt, bool dev) -> int {
+                   [&](int64_t c0, int64_t cnt, bool dev, const Arith& ar) -> int {
     const float *dx, *h = nullptr;
     CHK(in_ptr(c, x + c0 * SI_T * SI_D, cnt * SI_T * SI_D, dev, S_IN, &dx));
-    CHK(run_si_net(c, dx, cnt, nullptr, nullptr, nullptr, SI_D, &h));
+    CHK(run_si_net(c, ar, dx, cnt, nullptr, nullptr, nullptr, SI_D, &h));
     // the BiLSTM's own output buffer (S_HOUT) handed out: one copy, to the device or to the host
     HIPCHK(c, hipMemcpyAsync(emb + c0 * MMLA_SI_EMBED, h, (size_t)cnt * MMLA_SI_EMBED * sizeof(float),
                              dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
@@ -1310,8 +1278,8 @@ int mmla_capture_convert(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t str
     return finish(c, true);
   }
   void *pout = nullptr, *plens = nullptr;
-  CHK(cap_get(c, CB_OUT, (size_t)n * L * sizeof(int16_t), &pout));
-  CHK(cap_get(c, CB_LENS, (size_t)n * sizeof(int32_t), &plens));
+  CHK(ws_get(c, S_CAP_CLIPS, (size_t)n * L * sizeof(int16_t), &pout));
+  CHK(ws_get(c, S_CAP_LENS, (size_t)n * sizeof(int32_t), &plens));
   CHK(cap.run(c, false, static_cast<int16_t*>(pout), L, static_cast<int32_t*>(plens)));
   HIPCHK(c, hipMemcpy2DAsync(out, out_stride * sizeof(int16_t), pout, L * sizeof(int16_t), L * sizeof(int16_t),
                              n, hipMemcpyDeviceToHost, c->stream));
@@ -1356,10 +1324,10 @@ int mmla_debug_od_trace(mmla_ctx* c, const float* x, int64_t n, int stage, float
   HIPCHK(c, hipSetDevice(c->device));
   const float* dx;
   CHK(in_ptr(c, x, n * OD_IMG, false, S_IN, &dx));
-  auto body = [&]() -> int {
+  auto body = [&](const Arith& ar) -> int {
     const float* tap = nullptr;
     int64_t tn = 0;
-    CHK(run_od_net(c, nullptr, dx, n, nullptr, nullptr, OdGate(), stage, &tap, &tn));
+    CHK(run_od_net(c, ar, nullptr, dx, n, nullptr, nullptr, OdGate(), stage, &tap, &tn));
     if (tn > out_floats) return fail(c, MMLA_E_SHAPE, "trace stage %d needs %lld floats", stage, (long long)tn);
     HIPCHK(c, hipMemcpyAsync(out, tap, tn * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1369,7 +1337,7 @@ int mmla_debug_od_trace(mmla_ctx* c, const float* x, int64_t n, int stage, float
   // mmla_create: one host-pointer micro-batch under the range guard, like mmla_od_forward's -- an
   // operand out of range in a kernel up to `stage` re-runs the trace in exact f32 and counts in
   // mmla_range_check, so a test can tell which block's guard fired (the blocks behind `stage` do not run)
-  return c->debug_trace_guard ? guarded(c, false, c->od_f32_only, body) : body();
+  return c->debug_trace_guard ? guarded(c, false, c->od_f32_only, body) : body(unguarded(c));
 }
 
 }  // extern "C"

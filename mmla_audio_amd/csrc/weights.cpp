@@ -23,6 +23,7 @@ struct Cursor {
   const float* p;
   int64_t left;
   bool ok = true;
+  bool f16_bad = false;   // a tensor taken so far holds inf / NaN: that model runs exact f32 only
   const float* take(int64_t n) {
     if (n > left) {
       ok = false;
@@ -80,7 +81,7 @@ int take_conv(mmla_ctx* c, Cursor& cur, std::vector<void*>& al, int kh, int kw, 
   // 3xFP16: any finite tensor fits the fp16 split at its own power-of-two scale
   bool finite = true;
   w->wscale = pick_wscale(k, (size_t)kh * kw * cin * cout, &finite);
-  if (!finite) c->loading_f16_bad = true;
+  if (!finite) cur.f16_bad = true;
   w->kh = kh;
   w->kw = kw;
   w->cin = cin;
@@ -149,7 +150,7 @@ int take_lstm(mmla_ctx* c, Cursor& cur, std::vector<void*>& al, int d, LstmW* l)
     CHK(upload(c, al, b, 1024 * sizeof(float), &l->bias[dir]));
     bool finite = true;
     l->ws[dir] = pick_wscale(wc.data(), wc.size(), &finite);
-    if (!finite) c->loading_f16_bad = true;
+    if (!finite) cur.f16_bad = true;
     std::vector<uint16_t> hi(wc.size()), lo(wc.size());
     bilstm_h3_split_weights(wc.data(), d, hi.data(), lo.data(), l->ws[dir]);
     CHK(upload_u16(c, al, hi, &l->wth[dir]));
@@ -185,7 +186,6 @@ extern "C" int mmla_load_weights(mmla_ctx* c, int kind, const float* packed, int
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   Cursor cur{packed, n_floats};
-  c->loading_f16_bad = false;
   if (kind == MMLA_MODEL_OD) {
     if (n_classes != 2) return fail(c, MMLA_E_INVALID, "OD model has 2 classes, got %d", n_classes);
     free_allocs(c->od_allocs);
@@ -202,7 +202,7 @@ extern "C" int mmla_load_weights(mmla_ctx* c, int kind, const float* packed, int
     CHK(upload(c, al, hb, 2 * sizeof(float), &W.head_b));
     if (cur.left != 0)
       return fail(c, MMLA_E_SHAPE, "OD weight blob has %lld extra floats", (long long)cur.left);
-    c->od_f32_only = c->loading_f16_bad;   // some weight outside the fp16 range: exact f32 only
+    c->od_f32_only = cur.f16_bad;   // some weight outside the fp16 range: exact f32 only
     c->od_loaded = true;
     return MMLA_OK;
   }
@@ -219,14 +219,14 @@ extern "C" int mmla_load_weights(mmla_ctx* c, int kind, const float* packed, int
     CHK(take_units(c, cur, al, W.unit, 32, 3, 1, 3, 1, false));
     CHK(take_bn(c, cur, al, 128, &W.final_bn));
     CHK(take_lstm(c, cur, al, 128, &W.lstm));
-    c->si_base_f16_bad = c->loading_f16_bad;
+    c->si_base_f16_bad = cur.f16_bad;
     W.dense = ConvW();
     CHK(take_conv(c, cur, c->si_head_allocs, 1, 1, 512, n_classes, &W.dense));
     if (cur.left != 0)
       return fail(c, MMLA_E_SHAPE, "SI weight blob has %lld extra floats", (long long)cur.left);
     W.k = n_classes;
     W.head = head;
-    c->si_f32_only = c->loading_f16_bad;
+    c->si_f32_only = cur.f16_bad;
     c->si_loaded = true;
     return MMLA_OK;
   }
@@ -251,7 +251,6 @@ extern "C" int mmla_si_set_head(mmla_ctx* c, const float* w, const float* b, int
   memcpy(blob.data(), w, sizeof(float) * 512 * n_classes);
   memcpy(blob.data() + (size_t)512 * n_classes, b, sizeof(float) * n_classes);
   Cursor cur{blob.data(), (int64_t)blob.size()};
-  c->loading_f16_bad = false;
   std::vector<void*> al;
   ConvW dense;
   const int rc = take_conv(c, cur, al, 1, 1, 512, n_classes, &dense);
@@ -264,6 +263,6 @@ extern "C" int mmla_si_set_head(mmla_ctx* c, const float* w, const float* b, int
   c->si.dense = dense;
   c->si.k = n_classes;
   c->si.head = head;
-  c->si_f32_only = c->si_base_f16_bad || c->loading_f16_bad;
+  c->si_f32_only = c->si_base_f16_bad || cur.f16_bad;
   return MMLA_OK;
 }

@@ -202,6 +202,42 @@ def test_fused_call_equals_od_pipeline_on_the_mixed_clips(pool):
         c.close()
 
 
+def test_pool_and_plan_outlive_a_repeated_micro_batch(monkeypatch, pool):
+    """MMLA_DEBUG_FAIL_ALLOC=1 fails a context's first workspace allocation, which falls into the first
+    micro-batch behind the upload of the pool and the plan.  Only a micro-batch of more than 64 clips is
+    halved, so the call has 66 clips (-> 64 + 2): the workspace is released, the micro-batch repeated, and it
+    must find the pool and the plan where the call put them.  The hook is spent by the call it fails, so that
+    it is live in this path is shown on a second context made under it: 6 clips, too few to halve, report it."""
+    rng = np.random.default_rng(66)
+    clips = []
+    for i in range(66):
+        cl = (24000, 23999, 4001, 3999, 12000, 17)[i % 6]
+        clips.append([(int(rng.integers(0, 100000)) | 1, cl, 0)] +
+                     [(int(rng.integers(0, 90000)), (24000, 40000, 7, 1600)[(i + l) % 4], int(rng.integers(0, 13)) * 1600)
+                      for l in range(i % 4)])
+    plan = _lib.MixPlan.from_layers(clips)
+    quiet = (np.array(pool) // 4).astype(np.int16)
+    packed = weights.pack(weights.OD, weights.synthetic(weights.OD, seed=5))
+    monkeypatch.setenv('MMLA_DEBUG_FAIL_ALLOC', '1')
+    dbg, small = _lib.Context(0), _lib.Context(0)
+    monkeypatch.delenv('MMLA_DEBUG_FAIL_ALLOC')
+    plain = _lib.Context(0)
+    try:
+        for c in (dbg, small, plain):
+            c.load_weights(weights.OD, packed, 2)
+        with pytest.raises(_lib.MmlaError) as e:
+            small.od_pipeline_mixed(quiet, _lib.MixPlan.from_layers(clips[:6]))
+        assert e.value.code == -4, e.value
+        got = dbg.od_pipeline_mixed(quiet, plan)
+        want = plain.od_pipeline_mixed(quiet, plan)
+        for g, w, name in zip(got, want, ('probs', 'argmax', 'silent')):
+            assert g.tobytes() == w.tobytes(), name
+        assert np.isfinite(got[0]).all() and got[2].any() and not got[2].all()
+    finally:
+        for c in (dbg, small, plain):
+            c.close()
+
+
 def test_overlay_drop_in(ctx, pool):
     canvas = np.array(pool[1:5004])               # 5003 frames: 312.6875 ms, pydub's len() is 313
     seg = np.array(pool[20001:21601])

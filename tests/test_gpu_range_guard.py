@@ -195,3 +195,34 @@ def test_si_chain_overflow_host_call_reruns_in_f32(bn):
     assert c.range_check() >= 1
     p32, a32, _ = _ctx(W_si=W, prec=_lib.PREC_F32).si_pipeline(pcm)
     assert np.array_equal(p, p32) and np.array_equal(a, a32)
+
+
+def test_a_pass_leaves_the_settings_alone(monkeypatch):
+    """The arithmetic of a pass is the pass's: neither a re-run in exact f32 nor a call that fails inside
+    a guarded micro-batch leaves the context's precision or split switch changed.  MMLA_DEBUG_FAIL_ALLOC=1
+    fails the context's first workspace allocation, so the failing call (6 clips, too few to halve: it
+    reports MMLA_E_OOM) is the first one; then a host od_forward on the hot OD weights trips the guard and is
+    re-run in f32 once.  The in-range SI call behind both gives a fresh default context's bytes, which are
+    not the MMLA_PREC_F32 context's: it ran 3xFP16."""
+    from mmla_audio_amd import _lib, weights
+    W_od = _hot_od()
+    W_si = weights.synthetic(weights.SI, seed=7, n_classes=8)
+    x = np.random.default_rng(18).integers(0, 256, size=(6, 128, 151, 3)).astype(np.uint8)
+    pcm = synth.batch(360, 6, 24000)
+    monkeypatch.setenv('MMLA_DEBUG_FAIL_ALLOC', '1')
+    c = _ctx(W_od=W_od, W_si=W_si)
+    monkeypatch.delenv('MMLA_DEBUG_FAIL_ALLOC')
+    with pytest.raises(_lib.MmlaError) as e:
+        c.od_forward(x)
+    assert e.value.code == -4, e.value
+    assert c.range_check() == 0
+    p_hot = c.od_forward(x)
+    assert c.range_check() == 1                   # one micro-batch, re-run once
+    assert np.array_equal(p_hot, _ctx(W_od=W_od, prec=_lib.PREC_F32).od_forward(x))
+    p, a, s = c.si_pipeline(pcm)
+    assert c.range_check() == 1                   # ... and nothing since
+    want = _ctx(W_si=W_si).si_pipeline(pcm)
+    for g, w in zip((p, a, s), want):
+        assert g.tobytes() == w.tobytes()
+    p32 = _ctx(W_si=W_si, prec=_lib.PREC_F32).si_pipeline(pcm)[0]
+    assert not np.array_equal(p, p32)
