@@ -961,6 +961,11 @@ int mmla_debug_counters(mmla_ctx* ctx, int64_t* f32_reruns, int64_t* lstm_split_
  * one-stream-per-wave kernel, 0 for the one-thread-per-stream kernel (the same decisions and states bit
  * for bit).  Env at mmla_create: MMLA_NO_VADW=1 per thread everywhere, MMLA_VADW=1 per wave everywhere. */
 int mmla_debug_vad_path(mmla_ctx* ctx, int64_t n_streams, int32_t* wave);
+/* Debug (tests): the stationary gate's noise thresholds as the device holds them, copied to host
+ * `thresh` as [n_profiles][513] f32 (dB) after a synchronisation of the context's stream; *n_profiles
+ * (nullable) is the bank's size.  MMLA_E_INVALID without a bank (mmla_nr_set_noise / _bank) or when
+ * cap_floats < n_profiles * 513. */
+int mmla_debug_nr_thresh(mmla_ctx* ctx, float* thresh, int64_t cap_floats, int64_t* n_profiles);
 /* ms[MMLA_NSTAGES], launches[MMLA_NSTAGES], work[MMLA_NSTAGES] (each nullable); reset != 0 clears */
 int mmla_profile_read(mmla_ctx* ctx, double* ms, int64_t* launches, double* work, int reset);
 

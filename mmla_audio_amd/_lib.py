@@ -76,6 +76,7 @@ SIGNATURES = {
     'mmla_si_pipeline_capture': _COND + [_P] * 3 + [_U32],
     'mmla_room_pipeline_capture': _COND + [_P] * 5 + [_U32],
     'mmla_debug_vad_path': [_P, _I64, ctypes.POINTER(_I32)],
+    'mmla_debug_nr_thresh': [_P, _P, _I64, ctypes.POINTER(_I64)],
     'mmla_abi_version': [],
     'mmla_crc32c': [_P, _I64, ctypes.POINTER(_U32)],
     'mmla_png_unfilter': [_P, _I64, _I64, _I32, _P],
@@ -436,6 +437,18 @@ class Context:
         """profile: device int32 [n] (0: profile 0); indices outside the bank are clamped"""
         self._check(self.lib.mmla_nr_reduce_bank(self.h, y, n, stride, length, profile or None, out,
                                                  MMLA_DEVICE_PTR), 'mmla_nr_reduce_bank(dev)')
+
+    def debug_nr_thresh(self):
+        """-> float32 [P, 513]: the stationary gate's thresholds (dB) as the device holds them, one row
+        per profile of the bank.  MmlaError without a bank."""
+        n = _I64(0)
+        rc = self.lib.mmla_debug_nr_thresh(self.h, None, 0, ctypes.byref(n))   # too small: the size only
+        if n.value <= 0:
+            self._check(rc, 'mmla_debug_nr_thresh')
+        out = np.empty((n.value, 513), np.float32)
+        self._check(self.lib.mmla_debug_nr_thresh(self.h, _ptr(out), out.size, ctypes.byref(n)),
+                    'mmla_debug_nr_thresh')
+        return out
 
     def nr_set_nonstationary(self, time_constant_s=2.0, thresh_n_mult=2.0, sigmoid_slope=10.0, sr=16000):
         """Parameters of the non-stationary gate (nr_reduce_ns, nonstationary=True); a context starts

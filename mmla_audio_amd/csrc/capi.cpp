@@ -194,6 +194,20 @@ int mmla_nr_set_noise_bank(mmla_ctx* c, const float* noise, int64_t n_profiles, 
   return nr_set_bank(c, noise, n_profiles, stride, lens, len, sr, flags);
 }
 
+int mmla_debug_nr_thresh(mmla_ctx* c, float* thresh, int64_t cap_floats, int64_t* n_profiles) {
+  if (!c) return MMLA_E_INVALID;
+  if (!c->nr_ready || !c->nr_thresh) return fail(c, MMLA_E_INVALID, "mmla_nr_set_noise must be called first");
+  constexpr int64_t bins = NR_NFFT / 2 + 1;
+  if (n_profiles) *n_profiles = c->nr_profiles;
+  if (!thresh || cap_floats < c->nr_profiles * bins)
+    return fail(c, MMLA_E_INVALID, "thresholds need %lld floats (got room for %lld)",
+                (long long)(c->nr_profiles * bins), (long long)cap_floats);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(thresh, c->nr_thresh, (size_t)c->nr_profiles * bins * sizeof(float), hipMemcpyDeviceToHost));
+  return MMLA_OK;
+}
+
 }  // extern "C"
 
 // the gate of mmla_nr_reduce on device pointers; mmla_od_pipeline_gated runs its passes through it too
