@@ -948,6 +948,15 @@ int mmla_profile_enable(mmla_ctx* ctx, int on);
  * mmla_range_check. */
 int mmla_debug_od_trace(mmla_ctx* ctx, const float* x, int64_t n, int stage, float* out,
                         int64_t out_floats);
+/* Its twin for SI-NET on host features x[n,256,39]: stage 0 = stem conv [n,256,32], 1..9 = after
+ * res unit 1..9 ([n,128,32] x 3, [n,64,64] x 3, [n,32,128] x 3), 10 = final BN + ReLU + AvgPool4
+ * [n,8,128], 11 = BiLSTM output [n,512] (mmla_si_embed's), 12 = the logits [n,K] (the first K columns
+ * of each padded row).  The launches are the ones the context's switches select, whatever the stage:
+ * a stage that such a launch keeps on chip (a unit inside a fused chain or pair; unit 9 under the
+ * fused final epilogue, MMLA_NO_SIFIN unset) is MMLA_E_INVALID and mmla_last_error names the launch.
+ * MMLA_DEBUG_TRACE_GUARD=1 as above; the launches behind `stage` do not run. */
+int mmla_debug_si_trace(mmla_ctx* ctx, const float* x, int64_t n, int stage, float* out,
+                        int64_t out_floats);
 /* Debug (tests, tools): device address and size of internal workspace slot `slot` (0 and 0 when the
  * slot was never allocated), e.g. to check that no kernel of another call writes into it. */
 int mmla_debug_ws_slot(mmla_ctx* ctx, int slot, void** ptr, size_t* bytes);

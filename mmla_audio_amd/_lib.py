@@ -43,6 +43,7 @@ def si_seq_windows(n):
     """256-frame windows of a signal of n samples: ceil(T(n) / 256), 0 for an empty signal"""
     return -(-si_seq_frames(n) // SI_FRAMES) if int(n) > 0 else 0
 
+MMLA_E_INVALID = -1
 MMLA_E_RANGE = -6
 _ERRORS = {-1: 'MMLA_E_INVALID', -2: 'MMLA_E_HIP', -3: 'MMLA_E_NOWEIGHTS', -4: 'MMLA_E_OOM',
            -5: 'MMLA_E_SHAPE', -6: 'MMLA_E_RANGE'}
@@ -141,6 +142,7 @@ SIGNATURES = {
     'mmla_profile_enable': [_P, ctypes.c_int],
     'mmla_profile_read': [_P, _P, _P, _P, ctypes.c_int],
     'mmla_debug_od_trace': [_P, _P, _I64, ctypes.c_int, _P, _I64],
+    'mmla_debug_si_trace': [_P, _P, _I64, ctypes.c_int, _P, _I64],
     'mmla_debug_ws_slot': [_P, ctypes.c_int, _P, _P],
     'mmla_debug_counters': [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64)],
     'mmla_vad_reset': [_P, _I64, _I32],
@@ -368,6 +370,19 @@ class Context:
         out = np.empty((n,) + shape, np.float32)
         self._check(self.lib.mmla_debug_od_trace(self.h, _ptr(x), n, int(stage), _ptr(out), out.size),
                     'mmla_debug_od_trace')
+        return out
+
+    def debug_si_trace(self, x, stage):
+        """SI-NET intermediate tensor after `stage` (see mmla.h) for host features x [n, 256, 39]; a
+        stage that the context's launches keep on chip raises MmlaError(MMLA_E_INVALID)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n = x.shape[0]
+        shapes = {0: (256, 32), 10: (8, 128), 11: (512,), 12: (self.si_classes or 0,)}
+        units = [(128, 32), (64, 64), (32, 128)]
+        shape = shapes.get(stage) or units[(stage - 1) // 3 if 1 <= stage <= 9 else 0]   # else: the library refuses
+        out = np.empty((n,) + shape, np.float32)
+        self._check(self.lib.mmla_debug_si_trace(self.h, _ptr(x), n, int(stage), _ptr(out), out.size),
+                    'mmla_debug_si_trace')
         return out
 
     def load_weights(self, kind, packed, n_classes, head=HEAD_SOFTMAX):

@@ -138,7 +138,7 @@ struct mmla_ctx {
   int64_t od_mb = 0, si_mb = 0;            // user caps (0 = sized from free memory)
   int64_t od_mb_cap = mmla::kOdMicrobatch, si_mb_cap = mmla::kSiMicrobatch;   // default caps of the automatic size
   int debug_fail_allocs = 0;   // test hook (env MMLA_DEBUG_FAIL_ALLOC at create): fail this many workspace allocations
-  int debug_trace_guard = 0;   // test hook (env MMLA_DEBUG_TRACE_GUARD at create): mmla_debug_od_trace under the range guard
+  int debug_trace_guard = 0;   // test hook (env MMLA_DEBUG_TRACE_GUARD at create): mmla_debug_od_trace / _si_trace under the range guard
   int precision = MMLA_PREC_F16X3;   // mmla_set_precision: the user's setting (a pass runs its Arith)
   // SI res units as fused launches of siu.hip's one template, siu_chain_kernel<..., POOL, NU, FIN, ...>
   // (net_runners.cpp si_choose); env MMLA_NO_SIU=1 at create: two conv_h3 launches per unit (A/B)
@@ -383,6 +383,7 @@ int run_od_net(mmla_ctx* c, const Arith& ar, const uint8_t* img_u8, const float*
                float* probs, int32_t* argmax, OdGate gate = OdGate(), int stop = -1,
                const float** tap = nullptr, int64_t* tap_n = nullptr);
 int run_si_net(mmla_ctx* c, const Arith& ar, const float* x, int64_t n, float* probs, int32_t* argmax,
-               const uint8_t* silent, int ldx = SI_D, const float** tap = nullptr);
+               const uint8_t* silent, int ldx = SI_D, int stop = -1, const float** tap = nullptr,
+               int64_t* tap_n = nullptr);
 
 }  // namespace mmla

@@ -481,10 +481,19 @@ namespace mmla __attribute__((visibility("hidden"))) {
 
 // ldx: the features' row stride (39, or 40 from si_fe with a zero 40th column: the stem then stages
 // 16-B aligned rows, conv_h3's float4 path, bit-identical -- its weights' padded channels are zero)
-// tap != null: stop after the BiLSTM and return its output (base_model.layers[-2].output) in *tap
+// `stop` >= 0: return after stage `stop` (0 stem, 1..9 res units, 10 final BN + ReLU + AvgPool4, 11
+// BiLSTM = base_model.layers[-2].output, mmla_si_embed's; 12 the logits, rows of cout_pad floats) with
+// *tap / *tap_n (nullable) set to that stage's output tensor.  The launches are the ones the context's
+// switches select whatever `stop` is: a stage that such a launch keeps on chip is MMLA_E_INVALID
 int run_si_net(mmla_ctx* c, const Arith& ar, const float* x, int64_t n, float* probs, int32_t* argmax,
-               const uint8_t* silent, int ldx, const float** tap) {
+               const uint8_t* silent, int ldx, int stop, const float** tap, int64_t* tap_n) {
   const SiNet& W = c->si;
+  auto stopped = [&](const float* p, int64_t floats) {
+    *tap = p;
+    if (tap_n) *tap_n = floats;
+    return MMLA_OK;
+  };
+  if (stop >= 0 && !tap) return fail(c, MMLA_E_INVALID, "SI stop stage without a tap");
   const size_t big = (size_t)n * SI_T * 32;
   float *X, *T1, *XP, *R, *SEQ, *H, *L;
   CHK(ws_floats(c, S_X, big, &X));
@@ -502,6 +511,7 @@ int run_si_net(mmla_ctx* c, const Arith& ar, const float* x, int64_t n, float* p
   if (ldx == SI_D + 1 && h3 && stem.wh && stem.cin_pad > SI_D) stem.cin = ldx;
   else if (ldx != SI_D) return fail(c, MMLA_E_INVALID, "padded SI features need the 3xFP16 stem");
   CHK(conv_spatial(c, ar, stem, x, X, (int)n, t, 1, nullptr, PRO_NONE, EPI_BIAS, nullptr));
+  if (stop == 0) return stopped(X, n * t * W.stem.cout);
   for (int u = 0; u < 9; ++u) {   // res_unit, speaker_identification.py:168-190
     const ResUnitW& U = W.unit[u];
     const int cin = U.ca.cin;
@@ -531,6 +541,14 @@ int run_si_net(mmla_ctx* c, const Arith& ar, const float* x, int64_t n, float* p
         last.ft = W.final_bn.shift;
         fused_final = true;
       }
+      // the trace's stage inside this launch: the outputs between its units, and unit 9's under a fused
+      // final epilogue, never reach memory
+      if (stop > u && stop < u + units)
+        return fail(c, MMLA_E_INVALID, "SI stage %d stays on chip: one siu chain launch runs units %d-%d",
+                    stop, u + 1, u + units);
+      if (stop == 9 && fused_final)
+        return fail(c, MMLA_E_INVALID, "SI stage 9 stays on chip: the siu chain launch of units %d-9 writes "
+                    "the final BN + ReLU + AvgPool4 instead (MMLA_NO_SIFIN unset)", u + 1);
       LAUNCH(c, MMLA_STAGE_CONV, flops, siu_chain_launch(s, units, pool, cin, C, c->stream));
       u += units - 1;
     } else if (pool) {
@@ -559,18 +577,17 @@ int run_si_net(mmla_ctx* c, const Arith& ar, const float* x, int64_t n, float* p
     // the tail every unit runs through: the output becomes X, pooled rows
     if (out != X) std::swap(X, R);
     t = tp;
+    if (stop == u + 1) return stopped(X, n * t * W.unit[u].cb.cout);
   }
   // t = 32, c = 128 -> BN -> ReLU -> AvgPool1D(4) -> [n, 8, 128] (speaker_identification.py:208-212)
   if (!fused_final)
     LAUNCH(c, MMLA_STAGE_GLUE, 3.0 * n * t * 128,
            bn_relu_avgpool4_launch(X, (int)n, t, 128, W.final_bn.scale, W.final_bn.shift,
                                    SEQ, c->stream));
+  if (stop == 10) return stopped(SEQ, n * (t / 4) * 128);
   LAUNCH(c, MMLA_STAGE_LSTM, lstm_flops(n, t / 4, 128),
          lstm_run(c, ar, W.lstm, SEQ, n, t / 4, H));
-  if (tap) {   // mmla_si_embed: the BiLSTM output [n, 512] itself, no Dense, no head
-    *tap = H;
-    return MMLA_OK;
-  }
+  if (stop == 11) return stopped(H, n * 512);   // mmla_si_embed: the BiLSTM output itself, no Dense, no head
   if (h3 && W.dense.wh && W.dense.cin % 32 == 0) {
     // Dense(K) as a 1x1 conv over the clips on the 3xFP16 path (conv_h3 Conv1D tiles of 128 clips):
     // all cout_pad columns are written (the padding columns: zero weights and bias), so the logits
@@ -585,6 +602,7 @@ int run_si_net(mmla_ctx* c, const Arith& ar, const float* x, int64_t n, float* p
     d.ldy = W.dense.cout_pad;
     CHK(conv_run(c, d, MMLA_STAGE_HEAD));
   }
+  if (stop == 12) return stopped(L, n * W.dense.cout_pad);
   LAUNCH(c, MMLA_STAGE_HEAD, 4.0 * n * W.k,
          si_head_launch(L, (int)n, W.k, W.dense.cout_pad, W.head, probs,
                         argmax, silent, c->stream));

@@ -1078,7 +1078,7 @@ int mmla_si_enrol_embed(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t stri
       const int64_t wc = std::min(mb, nwin - w0);
       CHK(guarded(c, dev, c->si_f32_only, [&](const Arith& ar) -> int {
         const float* h = nullptr;
-        CHK(run_si_net(c, ar, a.feat + w0 * SI_T * SI_D, wc, nullptr, nullptr, nullptr, SI_D, &h));
+        CHK(run_si_net(c, ar, a.feat + w0 * SI_T * SI_D, wc, nullptr, nullptr, nullptr, SI_D, 11, &h));
         HIPCHK(c, hipMemcpyAsync(emb + (c0 * w_max + w0) * MMLA_SI_EMBED, h,
                                  (size_t)wc * MMLA_SI_EMBED * sizeof(float), kind, c->stream));
         return MMLA_OK;
@@ -1116,7 +1116,7 @@ int mmla_si_embed(mmla_ctx* c, const float* x, int64_t n, float* emb, uint32_t f
                    [&](int64_t c0, int64_t cnt, bool dev, const Arith& ar) -> int {
     const float *dx, *h = nullptr;
     CHK(in_ptr(c, x + c0 * SI_T * SI_D, cnt * SI_T * SI_D, dev, S_IN, &dx));
-    CHK(run_si_net(c, ar, dx, cnt, nullptr, nullptr, nullptr, SI_D, &h));
+    CHK(run_si_net(c, ar, dx, cnt, nullptr, nullptr, nullptr, SI_D, 11, &h));
     // the BiLSTM's own output buffer (S_HOUT) handed out: one copy, to the device or to the host
     HIPCHK(c, hipMemcpyAsync(emb + c0 * MMLA_SI_EMBED, h, (size_t)cnt * MMLA_SI_EMBED * sizeof(float),
                              dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
@@ -1338,6 +1338,33 @@ int mmla_debug_od_trace(mmla_ctx* c, const float* x, int64_t n, int stage, float
   // operand out of range in a kernel up to `stage` re-runs the trace in exact f32 and counts in
   // mmla_range_check, so a test can tell which block's guard fired (the blocks behind `stage` do not run)
   return c->debug_trace_guard ? guarded(c, false, c->od_f32_only, body) : body(unguarded(c));
+}
+
+int mmla_debug_si_trace(mmla_ctx* c, const float* x, int64_t n, int stage, float* out,
+                        int64_t out_floats) {
+  if (!c || !x || !out || n < 1 || stage < 0 || stage > 12) return MMLA_E_INVALID;
+  if (!c->si_loaded) return fail(c, MMLA_E_NOWEIGHTS, "SI weights not loaded");
+  HIPCHK(c, hipSetDevice(c->device));
+  const float* dx;
+  CHK(in_ptr(c, x, n * SI_T * SI_D, false, S_IN, &dx));
+  auto body = [&](const Arith& ar) -> int {
+    const float* tap = nullptr;
+    int64_t tn = 0;
+    CHK(run_si_net(c, ar, dx, n, nullptr, nullptr, nullptr, SI_D, stage, &tap, &tn));
+    // the logits: the first K columns of each cout_pad row
+    const int64_t k = c->si.k, ld = stage == 12 ? c->si.dense.cout_pad : 0;
+    if (stage == 12) tn = n * k;
+    if (tn > out_floats) return fail(c, MMLA_E_SHAPE, "trace stage %d needs %lld floats", stage, (long long)tn);
+    if (stage == 12)
+      HIPCHK(c, hipMemcpy2DAsync(out, k * sizeof(float), tap, ld * sizeof(float), k * sizeof(float), n,
+                                 hipMemcpyDeviceToHost, c->stream));
+    else
+      HIPCHK(c, hipMemcpyAsync(out, tap, tn * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MMLA_OK;
+  };
+  // mmla_debug_od_trace's two modes: unguarded, or (MMLA_DEBUG_TRACE_GUARD=1) one guarded host micro-batch
+  return c->debug_trace_guard ? guarded(c, false, c->si_f32_only, body) : body(unguarded(c));
 }
 
 }  // extern "C"
