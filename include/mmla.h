@@ -117,7 +117,7 @@ int mmla_synchronize(mmla_ctx* ctx);
  *                   reports MMLA_E_RANGE.  MMLA_PREC_F32 returns NaN for such a clip as well: its
  *                   ReLU and max-pools keep NaN.
  *   MMLA_PREC_F32   exact f32 MFMA (v_mfma_f32_32x32x2_f32), 1/5.3 of the throughput.
- * The front-ends (OD f32, SI f64), the OD stem Conv2D(1x1), the OD Dense(2) head and the softmax /
+ * The front-ends (OD f32, SI f64), the OD stem Conv2D(1x1), the OD Dense(K) head and the softmax /
  * sigmoid are the same in both modes; under MMLA_PREC_F16X3 the strided 1x1 shortcuts (OD blocks 1,
  * 4, 7; SI pool units) and the SI Dense(K) run 3xFP16 with the convolutions they are fused into.
  */
@@ -135,7 +135,8 @@ int mmla_range_check(mmla_ctx* ctx, int64_t* f32_reruns);
  * SI ~0.14 MB (65536 clips ~9 GB).  Weights: OD ~12 MB, SI ~10 MB.  Workspaces are kept for
  * reuse until mmla_release_workspace or mmla_destroy.  mmla_od_pipeline_gated with nr_passes > 0 adds
  * per clip the second image (58 KB) and two float clip buffers (2 x 4 x min(clip_len, 24000) bytes,
- * 192 KB), and per launch of the noise gate (at most 512 clips) ~6.9 MB of gate scratch per clip.
+ * 192 KB; the output slots hold 4 K + 5 bytes per clip for the K classes of the loaded OD model), and per
+ * launch of the noise gate (at most 512 clips) ~6.9 MB of gate scratch per clip.
  * mmla_condition and the conditioned pipelines add per clip two float buffers and one int16 buffer of
  * clip_len samples (10 x clip_len bytes: 0.41 MB at 40960), a byte per 30 ms frame, and the gate's
  * scratch (~8.3 MB per clip at 40960 samples, at most 512 clips at a time); their micro-batches are
@@ -156,12 +157,23 @@ int mmla_release_workspace(mmla_ctx* ctx);
  * bias; BatchNorm = gamma, beta, moving_mean, moving_variance; Bidirectional LSTM = forward
  * kernel, recurrent_kernel, bias, backward kernel, recurrent_kernel, bias.  Keras layouts.
  * Replaces tf.keras.models.load_model(...) (record_on_pc.py:88; SI record_on_pc.py:77).
- * n_classes: OD must be 2; SI = 630 (base model) or N speakers (deployed head).
+ * n_classes: OD = the K of the Dense(K) softmax head, 2 (the deployed timit2.0 model) .. MMLA_OD_MAX_CLASSES
+ *            (the reference's research models have 3: overlap_detector.py:394, tfl_convert.py:13-34); SI =
+ *            630 (base model) or N speakers (deployed head).
+ * OD: n_floats must be that K's blob, weights.od_spec(K): the two-class blob with the last two tensors
+ * [512, K] and [K].  K outside the range, or for K > 2 another n_floats, is MMLA_E_INVALID and the loaded
+ * model stays (a two-class blob of another size: MMLA_E_SHAPE, as before).  Loading a model with another K
+ * replaces the head: every OD inference entry -- mmla_od_forward, _u8, mmla_od_pipeline, _gated,
+ * _conditioned, _mixed, _capture, mmla_room_pipeline_conditioned, _capture -- writes probs [n, K] with the
+ * loaded K (mmla_od_classes), and argmax is the first index whose probability is above every earlier one.
  * head: MMLA_HEAD_SOFTMAX (base Dense(630, softmax), speaker_identification.py:215) or
  *       MMLA_HEAD_SIGMOID (deployed customized_dense, speaker_identification.py:409).
  */
+#define MMLA_OD_MAX_CLASSES 8
 int mmla_load_weights(mmla_ctx* ctx, int model_kind, const float* packed, int64_t n_floats,
                       int32_t n_classes, int32_t head);
+/* *k = the classes of the loaded OD model.  MMLA_E_NOWEIGHTS before an OD model is loaded. */
+int mmla_od_classes(mmla_ctx* ctx, int32_t* k);
 
 /*
  * OverlapDetection front-end, replaces OverlapFeaturesGenerator.generate_mels / generate_zcr /
@@ -227,7 +239,7 @@ int mmla_si_features_seq_batch(mmla_ctx* ctx, const int16_t* pcm, int64_t n_sign
                                const int32_t* lens, int32_t clip_len, float* feat, int32_t* n_windows,
                                uint32_t flags);
 
-/* OD-NET predict on float NHWC [n,128,151,3] (values 0..255) -> probs [n,2]
+/* OD-NET predict on float NHWC [n,128,151,3] (values 0..255) -> probs [n,K], K = mmla_od_classes
  * (model.predict, record_on_pc.py:159). */
 int mmla_od_forward(mmla_ctx* ctx, const float* x_nhwc, int64_t n, float* probs, uint32_t flags);
 /* Same on the uint8 image produced by mmla_od_features. */
@@ -409,7 +421,7 @@ int mmla_si_base_train(mmla_ctx* ctx, const float* packed, int64_t n_floats, int
  *             stride-2 shortcut.  Conv 'same': the (4,1) kernel pads 1 above, 2 below; the pool pads odd
  *             sizes with -inf (ties go to the first candidate in row-major order).  Mean over H, a BiLSTM
  *             over the ceil(w / 8) columns (D 128, U 256, the backward direction over the reversed
- *             sequence), Dropout(0.25), LeakyReLU(float32(0.3)), Dense(2), softmax.  h in [8, 128], w in
+ *             sequence), Dropout(0.25), LeakyReLU(float32(0.3)), Dense(K), softmax.  h in [8, 128], w in
  *             [8, 151]: 1..19 LSTM steps.
  *   training  BatchNorm on batch statistics: per channel over n h w, mean and biased variance, eps 1e-3;
  *             after every step moving <- 0.99 moving + 0.01 batch, the variance Bessel-corrected (x N /
@@ -434,9 +446,15 @@ int mmla_si_base_train(mmla_ctx* ctx, const float* packed, int64_t n_floats, int
  *             weighted mean), acc (first-index argmax), val_loss, val_acc (NaN when n_val == 0), lr.  Rows
  *             after an early stop are NaN.
  * Every sum has a fixed order and nothing is accumulated with atomics: the same inputs give the same bits.
- * Both entries work on a copy of `packed` (weights.od_spec() order, n_floats floats) in a workspace slot of
+ * Both entries work on a copy of `packed` (weights.od_spec(K) order, n_floats floats) in a workspace slot of
  * their own and do not touch the context's loaded model.  packed, the images, labels, perm, drop_mask and
- * every output are host or device pointers (flags); class_w [2] and lr [epochs] are always host pointers.
+ * every output are host or device pointers (flags); class_w [K] and lr [epochs] are always host pointers.
+ * K, the classes of the head, is read from n_floats = (the blob below the head) + 513 K, 2 <= K <=
+ * MMLA_OD_MAX_CLASSES: class_w is [K], labels lie in [0, K), the workspace pieces for the softmax outputs,
+ * the logit gradients and the head's gradients are sized by K.  The logits are z_k = b_k then fmaf over the
+ * 512 inputs ascending; q = p / sum p with k ascending; the gradient at the logits is class_w[c] (q_k -
+ * [k = c]) / batch inside the clip range, else 0 for the whole row; a hit is the first-index argmax of q.
+ * A fit at K = 2 gives the bits it gave before K was a parameter.
  *
  * mmla_od_loss_grad: ONE training-mode batch of n <= MMLA_OD_TRAIN_MAX_BATCH images, drop_mask [n, 512]
  *   (nullable) -> loss [1], grad [n_floats] in the packed order, moving_out [n_floats] (nullable): the
@@ -445,12 +463,13 @@ int mmla_si_base_train(mmla_ctx* ctx, const float* packed, int64_t n_floats, int
  *   unused), perm [epochs, n_train] the sample order of every epoch, drop_mask [epochs, n_train, 512]
  *   indexed by sample (nullable) -> packed_out [n_floats] (may be `packed`), history [epochs, 5],
  *   epochs_run [1].  epochs == 0 returns the input blob.
- * MMLA_E_INVALID, before any device work: n_floats that is not the OD blob's size, h or w outside the
+ * MMLA_E_INVALID, before any device work: n_floats that is no K's OD blob size, h or w outside the
  * range, batch < 1, min(batch, n_train) > MMLA_OD_TRAIN_MAX_BATCH (n outside [1, MAX_BATCH]), n_train < 1,
  * n_val < 0, epochs < 0, patience < 0, a null pointer, a class_w or lr that is negative or not finite, and
- * in host-pointer calls a label outside {0, 1} or a perm row that is not a permutation (device pointers:
- * a perm entry is clamped into the set, a label selects a lane by its lowest bit, a mask byte is read as
- * zero / non-zero, so a broken contract gives a wrong fit, not an access outside a buffer).
+ * in host-pointer calls a label outside [0, K) or a perm row that is not a permutation (device pointers:
+ * a perm entry is clamped into the set, a label selects a lane by its lowest bit at K = 2 and is clamped
+ * into [0, K - 1] at K > 2, a mask byte is read as zero / non-zero, so a broken contract gives a wrong fit,
+ * not an access outside a buffer).
  */
 #define MMLA_OD_TRAIN_MAX_BATCH 64
 int mmla_od_loss_grad(mmla_ctx* ctx, const float* packed, int64_t n_floats, const uint8_t* img_u8,
@@ -488,10 +507,11 @@ int mmla_od_finetune(mmla_ctx* ctx, const float* packed, int64_t n_floats, const
  * AUC (mmla_od_auc, and the two history columns): tf.keras.metrics.AUC() at its defaults, stated from Keras
  * 2.6's published source (parity with TF itself is unpinned).  200 float32 thresholds: float32(0 - 1e-7),
  * float32((i + 1) / 199.0) for i = 0..197 with the quotient in double, float32(1 + 1e-7).  multi_label =
- * False: all 2 n entries of probs [n, 2] are binary predictions against the entries of the one-hot label
- * rows; a prediction is positive iff p > thr, strictly.  Per threshold TP, FP, TN, FN are integers (one
- * thread per threshold walks the rows: no atomics); recall = TP / (TP + FN), fpr = FP / (FP + TN), 0 where
- * a denominator is 0; auc = sum_{t=0}^{198} (fpr[t] - fpr[t+1]) (recall[t] + recall[t+1]) / 2.  Deliberate
+ * False: all K n entries of probs [n, K] are binary predictions against the entries of the one-hot label
+ * rows; a prediction is positive iff p > thr, strictly.  Per threshold TP (the label's entry) and FP (the
+ * K - 1 others) are integers (one thread per threshold walks the rows: no atomics); recall = TP / n, fpr =
+ * FP / ((K - 1) n), 0 where a denominator is 0; auc = sum_{t=0}^{198} (fpr[t] - fpr[t+1]) (recall[t] +
+ * recall[t+1]) / 2.  Deliberate
  * deviation: the formula is evaluated in double from the integer counts and rounded to float32 once, where
  * Keras sums in float32 -- a difference of at most about 200 x 2^-24.
  *
@@ -510,11 +530,14 @@ int mmla_od_finetune(mmla_ctx* ctx, const float* packed, int64_t n_floats, const
  *
  * mmla_od_drop_mask: mask [n, 512] bytes (1 kept), sample_ids [n] nullable (= 0..n-1), n in [1, 2^20].
  * mmla_od_auc: probs [n, 2], labels [n] in {0, 1}, n in [1, 2^24] -> auc_out [1].
+ * mmla_od_auc_k: probs [n, n_classes], labels [n] in [0, n_classes), 2 <= n_classes <= MMLA_OD_MAX_CLASSES;
+ *   at 2 it is mmla_od_auc, bit for bit.
  * Host or device pointers (flags) throughout; class_w and lr are host pointers as above.
  * MMLA_E_INVALID, before any device work: what mmla_od_finetune rejects, ckpt_period < 0, epoch < 0, a size or
- * count outside the ranges above, a null pointer, and in host-pointer calls a src outside [0, n), a level
- * outside its range, a label outside {0, 1} or a sample id < 0 (device pointers: src and levels are clamped
- * into range, a label selects a lane by its lowest bit, a sample id is only a counter word, so a broken
+ * count or n_classes outside the ranges above, a null pointer, and in host-pointer calls a src outside [0, n),
+ * a level outside its range, a label outside [0, K) or a sample id < 0 (device pointers: src and levels are
+ * clamped into range, a label selects a lane by its lowest bit (K = 2) or is clamped (K > 2), a sample id is
+ * only a counter word, so a broken
  * contract gives a wrong result, not an access outside a buffer).
  */
 #define MMLA_OD_AUG_MAX_LEVELS 8
@@ -522,6 +545,8 @@ int mmla_od_augment(mmla_ctx* ctx, const uint8_t* img, int64_t n, int32_t h, int
                     const int32_t* levels, int64_t m, uint8_t* out, uint32_t flags);
 int mmla_od_auc(mmla_ctx* ctx, const float* probs, const int32_t* labels, int64_t n, float* auc_out,
                 uint32_t flags);
+int mmla_od_auc_k(mmla_ctx* ctx, const float* probs, const int32_t* labels, int64_t n, int32_t n_classes,
+                  float* auc_out, uint32_t flags);
 int mmla_od_drop_mask(mmla_ctx* ctx, int64_t drop_seed, int32_t epoch, const int32_t* sample_ids, int64_t n,
                       uint8_t* mask, uint32_t flags);
 int mmla_od_train(mmla_ctx* ctx, const float* packed, int64_t n_floats, const uint8_t* img_u8,

@@ -11,6 +11,8 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import weights
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libmmla.so')
 
@@ -125,6 +127,9 @@ SIGNATURES = {
     'mmla_od_augment': [_P, _P, _I64, _I32, _I32, _P, _P, _I64, _P, _U32],
     # ctx, probs, labels, n, auc_out
     'mmla_od_auc': [_P, _P, _P, _I64, _P, _U32],
+    # ctx, probs, labels, n, n_classes, auc_out
+    'mmla_od_auc_k': [_P, _P, _P, _I64, _I32, _P, _U32],
+    'mmla_od_classes': [_P, _P],
     # ctx, drop_seed, epoch, sample_ids, n, mask
     'mmla_od_drop_mask': [_P, _I64, _I32, _P, _I64, _P, _U32],
     # ctx, packed, n_floats, img_u8, labels, n_train, val_img, val_labels, n_val, h, w, class_w, epochs, batch,
@@ -710,10 +715,15 @@ class Context:
                                               int(head)), 'mmla_si_set_head')
         self.si_classes = int(k)
 
+    def _od_k(self):
+        """the classes of the loaded OD model (2 before one is loaded: the library refuses the call)"""
+        return self.od_classes or 2
+
     def od_forward(self, x):
+        """-> probs [n,K], K = od_classes"""
         x = np.ascontiguousarray(x)
         n = x.shape[0]
-        probs = np.empty((n, 2), np.float32)
+        probs = np.empty((n, self._od_k()), np.float32)
         if x.dtype == np.uint8:
             rc = self.lib.mmla_od_forward_u8(self.h, _ptr(x), n, _ptr(probs), 0)
         else:
@@ -892,15 +902,24 @@ class Context:
             raise ValueError(f'{what} {img.shape} / labels {labels.shape}: expected [n,h,w,3] and [n]')
         return img, labels
 
-    def od_loss_grad(self, packed, img, labels, class_w=(1.0, 1.0), drop_mask=None, moving=False):
+    @staticmethod
+    def _od_class_w(class_w, n_floats):
+        """class_w as float32 [K], K read from the blob's size (None: ones)"""
+        k = weights.od_classes_of(n_floats)
+        if class_w is None:
+            return np.ones(k, np.float32)
+        return np.ascontiguousarray(class_w, dtype=np.float32).reshape(k)
+
+    def od_loss_grad(self, packed, img, labels, class_w=None, drop_mask=None, moving=False):
         """The training-mode loss of ONE batch of OD feature images and its gradient (mmla_od_loss_grad):
-        packed = the OD blob of weights.pack, img uint8 [n,h,w,3], labels [n] in {0,1}, drop_mask uint8
+        packed = the OD blob of weights.pack (any K), img uint8 [n,h,w,3], labels [n] in [0,K), class_w [K]
+        (None: ones), drop_mask uint8
         [n,512] (None: every unit kept) -> (loss float32 [1], grad float32 [n_floats] in the packed order, 0
         in the moving statistics[, the blob with only the moving statistics advanced one step])."""
         packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
         img, labels = self._od_images(img, labels, 'img')
         n, h, w = img.shape[:3]
-        cw = np.ascontiguousarray(class_w, dtype=np.float32).reshape(2)
+        cw = self._od_class_w(class_w, packed.size)
         if drop_mask is not None:
             drop_mask = np.ascontiguousarray(drop_mask, dtype=np.uint8)
             if drop_mask.shape != (n, OD_DROP_UNITS):
@@ -926,7 +945,7 @@ class Context:
         n, h, w = img.shape[:3]
         epochs, perm, vi, vl, nv, opt = self._fit_args(perm, epochs, n, val_img, val_labels, self._od_images, 'val_img',
                                                         trim=True)
-        cw = np.ascontiguousarray(class_w, dtype=np.float32).reshape(2)
+        cw = self._od_class_w(class_w, packed.size)
         lr = np.ascontiguousarray(lr, dtype=np.float32).ravel()[:epochs]
         if lr.shape != (epochs,):
             raise ValueError(f'lr {lr.shape}: expected [{epochs}]')
@@ -956,7 +975,7 @@ class Context:
         n, h, w = img.shape[:3]
         epochs, perm, vi, vl, nv, opt = self._fit_args(perm, epochs, n, val_img, val_labels, self._od_images, 'val_img',
                                                         trim=True)
-        cw = np.ascontiguousarray(class_w, dtype=np.float32).reshape(2)
+        cw = self._od_class_w(class_w, packed.size)
         lr = np.ascontiguousarray(lr, dtype=np.float32).ravel()[:epochs]
         if lr.shape != (epochs,):
             raise ValueError(f'lr {lr.shape}: expected [{epochs}]')
@@ -1004,21 +1023,22 @@ class Context:
         return out
 
     def od_auc(self, probs, labels):
-        """tf.keras.metrics.AUC() at its defaults (mmla_od_auc) of probs float32 [n,2] against labels [n] in
-        {0,1} -> float32 scalar."""
+        """tf.keras.metrics.AUC() at its defaults (mmla_od_auc_k) of probs float32 [n,K] against labels [n] in
+        [0,K) -> float32 scalar."""
         probs = np.ascontiguousarray(probs, dtype=np.float32)
         labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
-        if probs.ndim != 2 or probs.shape != (labels.size, 2):
-            raise ValueError(f'probs {probs.shape} / labels {labels.shape}: expected [n,2] and [n]')
+        if probs.ndim != 2 or probs.shape[0] != labels.size:
+            raise ValueError(f'probs {probs.shape} / labels {labels.shape}: expected [n,K] and [n]')
         out = np.empty(1, np.float32)
-        self._check(self.lib.mmla_od_auc(self.h, _ptr(probs), _ptr(labels), labels.size, _ptr(out), 0), 'mmla_od_auc')
+        self._check(self.lib.mmla_od_auc_k(self.h, _ptr(probs), _ptr(labels), labels.size, probs.shape[1], _ptr(out),
+                                           0), 'mmla_od_auc_k')
         return out[0]
 
     def od_pipeline(self, pcm, lens=None):
-        """-> (probs [n,2], argmax [n] (-1 = 'silent'), silent [n] bool)."""
+        """-> (probs [n,K], argmax [n] (-1 = 'silent'), silent [n] bool)."""
         a, ln, L = self._pcm(pcm, lens)
         n = a.shape[0]
-        probs = np.empty((n, 2), np.float32)
+        probs = np.empty((n, self._od_k()), np.float32)
         am = np.empty(n, np.int32)
         silent = np.empty(n, np.uint8)
         self._check(self.lib.mmla_od_pipeline(self.h, _ptr(a), n, a.shape[1], _ptr(ln), L,
@@ -1028,12 +1048,12 @@ class Context:
 
     def od_pipeline_gated(self, pcm, lens=None, passes=4, threshold=0.3, nonstationary=False):
         """od_pipeline with the denoise-and-compare silence gate of record_on_pi.py:103-124 (noise
-        profile: nr_set_noise; nonstationary=True: the gate of nr_reduce_ns, no profile) -> (probs [n,2]
+        profile: nr_set_noise; nonstationary=True: the gate of nr_reduce_ns, no profile) -> (probs [n,K]
         of the denoised clips, argmax [n] (-1 = 'silent'), silent [n] bool, ssim [n] of each clip's
         image against its `passes` x denoised image)."""
         a, ln, L = self._pcm(pcm, lens)
         n = a.shape[0]
-        probs = np.empty((n, 2), np.float32)
+        probs = np.empty((n, self._od_k()), np.float32)
         am = np.empty(n, np.int32)
         silent = np.empty(n, np.uint8)
         ssim = np.empty(n, np.float32)
@@ -1067,12 +1087,12 @@ class Context:
 
     def od_pipeline_mixed(self, pool, plan):
         """od_mix at 24000 samples fused in front of od_pipeline, the mixed clips staying on the device ->
-        (probs [n,2], argmax [n] (-1 = 'silent': a canvas below 4000 samples), silent [n] bool); the bits of
+        (probs [n,K], argmax [n] (-1 = 'silent': a canvas below 4000 samples), silent [n] bool); the bits of
         od_pipeline(*od_mix(pool, plan))."""
         pool = np.ascontiguousarray(pool, dtype=np.int16).reshape(-1)
         nl, off, ln, pos = MixPlan(*plan).arrays()
         n = nl.size
-        probs = np.empty((n, 2), np.float32)
+        probs = np.empty((n, self._od_k()), np.float32)
         am = np.empty(n, np.int32)
         silent = np.empty(n, np.uint8)
         hold = np.zeros(1, np.int16)
@@ -1126,10 +1146,10 @@ class Context:
 
     def od_pipeline_conditioned(self, pcm, lens=None, profile=None, passes=1, silence_remove=True,
                                 items_per_stream=1, return_pcm=False, nonstationary=False):
-        """condition() fused in front of od_pipeline -> (probs [n,2], argmax [n] (-1 = 'silent': fewer
+        """condition() fused in front of od_pipeline -> (probs [n,K], argmax [n] (-1 = 'silent': fewer
         than 4000 samples kept), silent [n] bool, kept_len [n]); return_pcm adds the conditioned clips."""
-        return self._fused('mmla_od_pipeline_conditioned', (2,), self._cond_clips(pcm, lens), profile, passes,
-                           silence_remove, items_per_stream, return_pcm, nonstationary)
+        return self._fused('mmla_od_pipeline_conditioned', (self._od_k(),), self._cond_clips(pcm, lens), profile,
+                           passes, silence_remove, items_per_stream, return_pcm, nonstationary)
 
     def si_pipeline_conditioned(self, pcm, lens=None, profile=None, passes=1, silence_remove=True,
                                 items_per_stream=1, return_pcm=False, nonstationary=False):
@@ -1139,10 +1159,10 @@ class Context:
 
     def room_pipeline_conditioned(self, pcm, lens=None, profile=None, passes=1, silence_remove=True,
                                   items_per_stream=1, return_pcm=False, nonstationary=False):
-        """condition() once in front of od_pipeline and si_pipeline -> (od_probs [n,2], od_argmax [n],
+        """condition() once in front of od_pipeline and si_pipeline -> (od_probs [n,K_od], od_argmax [n],
         si_probs [n,K], si_argmax [n], silent [n] bool, kept_len [n]); return_pcm adds the conditioned
         clips.  Both argmax are -1 where fewer than 4000 samples were kept."""
-        return self._fused('mmla_room_pipeline_conditioned', (2, self.si_classes or 0),
+        return self._fused('mmla_room_pipeline_conditioned', (self._od_k(), self.si_classes or 0),
                            self._cond_clips(pcm, lens), profile, passes, silence_remove, items_per_stream,
                            return_pcm, nonstationary)
 
@@ -1226,10 +1246,10 @@ class Context:
                             items_per_stream=1, return_pcm=False, nonstationary=False):
         """od_pipeline_conditioned on interleaved capture in the capture_reset format: capture_convert
         of all clips, then the conditioned pipeline on the converted clips, which stay on the device ->
-        (probs [n,2], argmax [n], silent [n] bool, kept_len [n] at 16 kHz); return_pcm adds the
+        (probs [n,K], argmax [n], silent [n] bool, kept_len [n] at 16 kHz); return_pcm adds the
         conditioned clips [n, out_clip_len]."""
-        return self._fused('mmla_od_pipeline_capture', (2,), self._capture_clips(pcm, frames), profile, passes,
-                           silence_remove, items_per_stream, return_pcm, nonstationary)
+        return self._fused('mmla_od_pipeline_capture', (self._od_k(),), self._capture_clips(pcm, frames), profile,
+                           passes, silence_remove, items_per_stream, return_pcm, nonstationary)
 
     def si_pipeline_capture(self, pcm, frames=None, profile=None, passes=1, silence_remove=True,
                             items_per_stream=1, return_pcm=False, nonstationary=False):
@@ -1239,9 +1259,9 @@ class Context:
 
     def room_pipeline_capture(self, pcm, frames=None, profile=None, passes=1, silence_remove=True,
                               items_per_stream=1, return_pcm=False, nonstationary=False):
-        """room_pipeline_conditioned on interleaved capture -> (od_probs [n,2], od_argmax [n], si_probs
+        """room_pipeline_conditioned on interleaved capture -> (od_probs [n,K_od], od_argmax [n], si_probs
         [n,K], si_argmax [n], silent [n] bool, kept_len [n]); return_pcm adds the conditioned clips."""
-        return self._fused('mmla_room_pipeline_capture', (2, self.si_classes or 0),
+        return self._fused('mmla_room_pipeline_capture', (self._od_k(), self.si_classes or 0),
                            self._capture_clips(pcm, frames), profile, passes, silence_remove, items_per_stream,
                            return_pcm, nonstationary)
 
@@ -1311,7 +1331,7 @@ class Context:
         sig = np.ascontiguousarray(signal, dtype=np.int16).reshape(-1)
         if n < 0 or (n > 0 and (n - 1) * stride + clip_len > sig.size):
             raise MmlaError(f'{n} windows of {clip_len} at stride {stride} exceed {sig.size} samples')
-        probs = np.empty((n, 2), np.float32)
+        probs = np.empty((n, self._od_k()), np.float32)
         am = np.empty(n, np.int32)
         self._check(self.lib.mmla_od_pipeline(self.h, _ptr(sig), n, stride, None, clip_len,
                                               _ptr(probs), _ptr(am), None, 0), 'mmla_od_pipeline')
@@ -1486,8 +1506,8 @@ class Context:
 
     def od_loss_grad_dev(self, packed, n_floats, img, labels, n, h, w, class_w, drop_mask, loss, grad,
                          moving_out=0):
-        """mmla_od_loss_grad on device buffers (class_w: a host float32 [2] array)"""
-        cw = np.ascontiguousarray(class_w, dtype=np.float32).reshape(2)
+        """mmla_od_loss_grad on device buffers (class_w: a host float32 [K] array)"""
+        cw = self._od_class_w(class_w, n_floats)
         self._check(self.lib.mmla_od_loss_grad(self.h, packed, n_floats, img, labels, n, h, w, _ptr(cw),
                                                drop_mask or None, loss, grad, moving_out or None,
                                                MMLA_DEVICE_PTR), 'mmla_od_loss_grad(dev)')
@@ -1497,7 +1517,7 @@ class Context:
         """mmla_od_finetune on device buffers (class_w, lr: host float32 arrays): the caller guarantees
         labels in {0, 1} and that every perm row is a permutation; asynchronous on the context's stream
         unless patience > 0 and n_val > 0"""
-        cw = np.ascontiguousarray(class_w, dtype=np.float32).reshape(2)
+        cw = self._od_class_w(class_w, n_floats)
         lr = np.ascontiguousarray(lr, dtype=np.float32).ravel()
         self._check(self.lib.mmla_od_finetune(
             self.h, packed, n_floats, img, labels, n_train, val_img or None, val_labels or None, n_val, h, w,
@@ -1511,7 +1531,7 @@ class Context:
         int32 words): the caller guarantees labels in {0, 1} and that every perm row is a permutation;
         asynchronous on the context's stream unless a callback is on (patience or ckpt_period > 0 with
         n_val > 0)"""
-        cw = np.ascontiguousarray(class_w, dtype=np.float32).reshape(2)
+        cw = self._od_class_w(class_w, n_floats)
         lr = np.ascontiguousarray(lr, dtype=np.float32).ravel()
         self._check(self.lib.mmla_od_train(
             self.h, packed, n_floats, img, labels, n_train, val_img or None, val_labels or None, n_val, h, w,

@@ -41,6 +41,20 @@ constexpr int SI_NEED_SAMPLES = 160 * 259 + 400;   // frames 0..259 (delta-delta
 constexpr int CH[9] = {32, 32, 32, 64, 64, 64, 128, 128, 128};
 constexpr bool POOL[9] = {true, false, false, true, false, false, true, false, false};
 
+// floats of the packed OD blob (weights.od_spec(K)): everything below the Dense head, then kernel [512, K], bias [K]
+constexpr int64_t od_body_floats() {
+  int64_t n = 3 * 16 + 16;
+  int cin = 16;
+  for (int u = 0; u < 9; ++u) {
+    const int ch = CH[u];
+    n += 4 * cin + (9 * cin * ch + ch) + 4 * ch + (4 * ch * ch + ch) + (POOL[u] ? cin * ch + ch : 0);
+    cin = ch;
+  }
+  return n + 2 * ((128 + 256) * 1024 + 1024);
+}
+constexpr int64_t od_blob_floats(int k) { return od_body_floats() + 513 * (int64_t)k; }
+static_assert(od_blob_floats(2) == 1548706, "the two-class OD blob");
+
 struct ConvW {
   float* wt = nullptr;
   float* bias = nullptr;
@@ -74,8 +88,9 @@ struct OdNet {
   ConvW stem;
   ResUnitW blk[9];
   LstmW lstm;
-  float* head_w = nullptr;
+  float* head_w = nullptr;   // Dense [512, k]
   float* head_b = nullptr;
+  int k = 2;                 // classes of the loaded head, 2 .. MMLA_OD_MAX_CLASSES
 };
 struct SiNet {
   ConvW stem;

@@ -396,8 +396,8 @@ int run_od_net(mmla_ctx* c, const Arith& ar, const uint8_t* img_u8, const float*
     *tap_n = n * 512;
     return MMLA_OK;
   }
-  LAUNCH(c, MMLA_STAGE_HEAD, 2.0 * n * 512 * 2,
-         od_head_launch(H, (int)n, W.head_w, W.head_b, probs, argmax,
+  LAUNCH(c, MMLA_STAGE_HEAD, 2.0 * n * 512 * W.k,
+         od_head_launch(H, (int)n, W.k, W.head_w, W.head_b, probs, argmax,
                         gate.lens, gate.clip_len, gate.silent, gate.ssim, gate.ssim_threshold,
                         c->stream));
   return MMLA_OK;

@@ -41,11 +41,14 @@ size_t bilstm_h3_split_ws_bytes();
 int bilstm_h3_split_max_clips();
 // split at the direction's power-of-two weight scale ws (the kernel's ws_fwd / ws_bwd)
 void bilstm_h3_split_weights(const float* wcat, int D, uint16_t* hi, uint16_t* lo, float ws);
-// OD head: LeakyReLU(0.3) -> Dense(512 -> 2) -> softmax; probs [n,2], argmax [n] (nullable).
+// OD head: LeakyReLU(0.3) -> Dense(512 -> k) -> softmax; probs [n,k], argmax [n] (nullable), 2 <= k <=
+// OD_HEAD_MAX_K (else hipErrorInvalidValue).  k == 2 runs od_head_kernel, any other k od_head_k_kernel: one
+// wave per clip as well, the first index wins a tie of the probabilities written.
 // The 'silent' gate of record_on_pc.py:141-154: with clip_len >= 0, clips with fewer than 4000
 // samples (lens[i], or clip_len when lens is null) get argmax -1 and silent[i] = 1 (nullable).
 // With ssim [n] (nullable; record_on_pi.py:103-124) a clip is silent too when ssim[i] < ssim_threshold.
-hipError_t od_head_launch(const float* h, int n, const float* w /*[512][2]*/, const float* b,
+constexpr int OD_HEAD_MAX_K = 8;   // = MMLA_OD_MAX_CLASSES
+hipError_t od_head_launch(const float* h, int n, int k, const float* w /*[512][k]*/, const float* b,
                           float* probs, int32_t* argmax, const int32_t* lens, int clip_len,
                           uint8_t* silent, const float* ssim, float ssim_threshold, hipStream_t s);
 // SI head activation on logits [n, ld]: softmax (head 0) or sigmoid (head 1) over the first k;

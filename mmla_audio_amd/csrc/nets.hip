@@ -695,6 +695,63 @@ __global__ void od_head_kernel(const float* __restrict__ h, int n, const float* 
   }
 }
 
+// the K-way head (2 < K <= OD_HEAD_MAX_K): od_head_kernel's walk with K accumulators in registers -- every
+// loop over the classes is unrolled to OD_HEAD_MAX_K and cut at K, which is the same for the whole launch
+__global__ void od_head_k_kernel(const float* __restrict__ h, int n, int K, const float* __restrict__ w,
+                                 const float* __restrict__ b, float* __restrict__ probs,
+                                 int32_t* __restrict__ argmax, const int32_t* __restrict__ lens,
+                                 int clip_len, uint8_t* __restrict__ silent,
+                                 const float* __restrict__ ssim, float ssim_threshold) {
+  const int lane = threadIdx.x & 63;
+  const int64_t clip = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (clip >= n) return;
+  const float alpha = 0.30000001192092896f;   // LeakyReLU(alpha=0.3) stored float32
+  float z[OD_HEAD_MAX_K];
+#pragma unroll
+  for (int k = 0; k < OD_HEAD_MAX_K; ++k) z[k] = 0.0f;
+  for (int i = lane; i < 512; i += 64) {
+    float v = h[clip * 512 + i];
+    v = v > 0.0f ? v : v * alpha;
+#pragma unroll
+    for (int k = 0; k < OD_HEAD_MAX_K; ++k)
+      if (k < K) z[k] = fmaf(v, w[i * K + k], z[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < OD_HEAD_MAX_K; ++k)
+    if (k < K) z[k] = wave_sum(z[k]) + b[k];
+  if (lane == 0) {
+    float m = z[0];
+#pragma unroll
+    for (int k = 1; k < OD_HEAD_MAX_K; ++k)
+      if (k < K) m = fmaxf(m, z[k]);
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < OD_HEAD_MAX_K; ++k)
+      if (k < K) {
+        z[k] = expf(z[k] - m);
+        s += z[k];
+      }
+    // the first index whose probability, as written, is above every earlier one
+    int best = 0;
+    float pbest = z[0] / s;
+#pragma unroll
+    for (int k = 0; k < OD_HEAD_MAX_K; ++k)
+      if (k < K) {
+        const float p = z[k] / s;
+        if (probs) probs[clip * K + k] = p;
+        if (p > pbest) {
+          pbest = p;
+          best = k;
+        }
+      }
+    // the 'silent' rule of od_head_kernel
+    const bool sil = clip_len >= 0 && ((lens ? lens[clip] : clip_len) < 4000 ||
+                                       (ssim && ssim[clip] < ssim_threshold));
+    if (silent) silent[clip] = sil ? 1 : 0;
+    if (argmax) argmax[clip] = sil ? -1 : best;
+  }
+}
+
 __global__ void si_head_kernel(const float* __restrict__ logits, int n, int k, int ld, int head,
                                float* __restrict__ probs, int32_t* __restrict__ argmax,
                                const uint8_t* __restrict__ silent) {
@@ -869,12 +926,17 @@ void bilstm_h3_split_weights(const float* wcat, int D, uint16_t* hi, uint16_t* l
     }
 }
 
-hipError_t od_head_launch(const float* h, int n, const float* w, const float* b, float* probs,
+hipError_t od_head_launch(const float* h, int n, int k, const float* w, const float* b, float* probs,
                           int32_t* argmax, const int32_t* lens, int clip_len, uint8_t* silent,
                           const float* ssim, float ssim_threshold, hipStream_t s) {
+  if (k < 2 || k > OD_HEAD_MAX_K) return hipErrorInvalidValue;
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(od_head_kernel, dim3(blocks_for((int64_t)n * 64, 256)), dim3(256), 0, s, h, n,
-                     w, b, probs, argmax, lens, clip_len, silent, ssim, ssim_threshold);
+  if (k == 2)
+    hipLaunchKernelGGL(od_head_kernel, dim3(blocks_for((int64_t)n * 64, 256)), dim3(256), 0, s, h, n,
+                       w, b, probs, argmax, lens, clip_len, silent, ssim, ssim_threshold);
+  else
+    hipLaunchKernelGGL(od_head_k_kernel, dim3(blocks_for((int64_t)n * 64, 256)), dim3(256), 0, s, h, n, k,
+                       w, b, probs, argmax, lens, clip_len, silent, ssim, ssim_threshold);
   return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@ constexpr int ODB_RED_SLABS = 256;      // most slabs of a per-channel reduction
 constexpr int ODB_WG_SLABS = 128;       // most slabs of a weight gradient
 constexpr int ODB_HEAD_D = 512;         // BiLSTM output width
 constexpr int ODB_MAX_BATCH = 64;       // = MMLA_OD_TRAIN_MAX_BATCH
+constexpr int ODB_MAX_K = 8;            // = MMLA_OD_MAX_CLASSES
 
 // one Conv2D: x [B, h, w, cin] -> y [B, ho, wo, cout], y[ho][wo] = sum x[ho s + dy - pad_h][wo s + dx - pad_w]
 struct OdbConv {
@@ -76,22 +77,26 @@ hipError_t odb_pool_bwd(const float* dy, const uint8_t* idx, float* dx, int B, i
 hipError_t odb_mean_h(const float* x, float* seq, int B, int h, int w, int c, hipStream_t stream);
 hipError_t odb_mean_h_bwd(const float* dxs, float* dx, int B, int h, int w, int c, hipStream_t stream);
 
-// Dropout mask x 1 / 0.75 (training), LeakyReLU(float32(0.3)), Dense(2), softmax, the weighted loss
+// Dropout mask x 1 / 0.75 (training), LeakyReLU(float32(0.3)), Dense(K), softmax, the weighted loss.
+// 2 <= K <= ODB_MAX_K (else hipErrorInvalidValue).  K == 2 runs the two-class kernels, whose sums keep their
+// order; any other K the K-class ones: logits z_k = b_k then fmaf over d ascending, q = p / sum p (k ascending),
+// a hit when the first-index argmax of q is the label, demb = slope * sum_k dz_k w[d][k] with k ascending
 struct OdbHead {
   const float* emb;        // [B, 512]
   const uint8_t* mask;     // [B, 512], nullable: inference mode (no dropout, no scale)
-  const float* w;          // [512, 2]
-  const float* b;          // [2]
-  const int32_t* labels;   // [B], bit 0 is used
-  float cw[2];
-  float* dz;               // [B, 2] gradient at the logits (nullable)
+  const float* w;          // [512, K]
+  const float* b;          // [K]
+  const int32_t* labels;   // [B]; K == 2: bit 0 is used, else clamped into [0, K - 1]
+  float cw[ODB_MAX_K];     // [K]
+  float* dz;               // [B, K] gradient at the logits (nullable)
   double* acc;             // [2]: += sum of the samples' losses, += hits
   int B;
   float bsz;
-  float* probs;            // [B, 2] the softmax outputs (nullable)
+  float* probs;            // [B, K] the softmax outputs (nullable)
+  int K;
 };
 hipError_t odb_head_loss(const OdbHead& a, hipStream_t stream);
-// gw [512, 2], gb [2], demb [B, 512]
+// gw [512, K], gb [K], demb [B, 512]
 hipError_t odb_head_bwd(const OdbHead& a, float* gw, float* gb, float* demb, hipStream_t stream);
 
 // Keras Adadelta (rho 0.95, epsilon 1e-7) over the flat blob, lr = lrs[ep]; entries with trainable[i] == 0 skipped
@@ -123,12 +128,13 @@ struct OdbAucThr {
 OdbAucThr odb_auc_thresholds();
 // slabs of a count over n samples: min(ODB_AUC_SLABS, ceil(n / 4096))
 int odb_auc_slabs(int64_t n);
-// counts [slabs, 200, 2] (uint32): over the 2 n entries of probs [n, 2] against the one-hot rows of labels
-// (bit 0), TP and FP per threshold; add != 0: added to what counts holds, else written.  Integer counts
-// and no atomics: one thread per threshold walks its slab's rows
-hipError_t odb_auc_count(const float* probs, const int32_t* labels, int64_t n, const OdbAucThr& thr, int add,
+// counts [slabs, 200, 2] (uint32): over the K n entries of probs [n, K] against the one-hot rows of labels
+// (K == 2: bit 0; else clamped into [0, K - 1]), TP (the label's entry) and FP (the K - 1 others) per
+// threshold; add != 0: added to what counts holds, else written.  Integer counts and no atomics: one thread
+// per threshold walks its slab's rows.  2 <= K <= ODB_MAX_K
+hipError_t odb_auc_count(const float* probs, const int32_t* labels, int64_t n, int K, const OdbAucThr& thr, int add,
                          uint32_t* counts, hipStream_t stream);
 // out[0] = float32 of sum_t (fpr[t] - fpr[t + 1]) (recall[t] + recall[t + 1]) / 2 in double from the slabs'
-// integer sums; the 2 n entries hold n positives and n negatives, so FN = n - TP, TN = n - FP.  n == 0: NaN.
-// clear != 0: counts zeroed afterwards
-hipError_t odb_auc_final(uint32_t* counts, int slabs, int64_t n, int clear, float* out, hipStream_t stream);
+// integer sums; the K n entries hold n positives and (K - 1) n negatives, so recall = TP / n and
+// fpr = FP / ((K - 1) n).  n == 0: NaN.  clear != 0: counts zeroed afterwards
+hipError_t odb_auc_final(uint32_t* counts, int slabs, int64_t n, int K, int clear, float* out, hipStream_t stream);

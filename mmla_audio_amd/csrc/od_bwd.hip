@@ -440,6 +440,112 @@ __global__ void head_bwd_kernel(OdbHead a, float* __restrict__ gw, float* __rest
   }
 }
 
+// The K-class head (2 < K <= ODB_MAX_K).  The per-class values live in registers: every loop over the classes
+// is unrolled to ODB_MAX_K and cut at K.  A label outside [0, K - 1] (a device-pointer caller's broken
+// contract) is clamped into it.
+
+__device__ inline int clamp_label(int l, int K) { return l < 0 ? 0 : l > K - 1 ? K - 1 : l; }
+
+__global__ void __launch_bounds__(ODB_MAX_BATCH) head_loss_k_kernel(OdbHead a) {
+  __shared__ float loss[ODB_MAX_BATCH];
+  __shared__ int hit[ODB_MAX_BATCH];
+  const int s = threadIdx.x, K = a.K;
+  const float lo = 1e-7f, hi = 1.0f - 1e-7f;
+  float l = 0.0f;
+  int h = 0;
+  if (s < a.B) {
+    float z[ODB_MAX_K], slope;
+#pragma unroll
+    for (int k = 0; k < ODB_MAX_K; ++k) z[k] = k < K ? a.b[k] : 0.0f;
+    for (int d = 0; d < ODB_HEAD_D; ++d) {
+      const float v = head_in(a, s, d, &slope);
+#pragma unroll
+      for (int k = 0; k < ODB_MAX_K; ++k)
+        if (k < K) z[k] = fmaf(v, a.w[K * d + k], z[k]);
+    }
+    float m = z[0];
+#pragma unroll
+    for (int k = 1; k < ODB_MAX_K; ++k)
+      if (k < K) m = fmaxf(m, z[k]);
+    float se = 0.0f, sp = 0.0f;
+#pragma unroll
+    for (int k = 0; k < ODB_MAX_K; ++k)
+      if (k < K) {
+        z[k] = expf(z[k] - m);
+        se += z[k];
+      }
+#pragma unroll
+    for (int k = 0; k < ODB_MAX_K; ++k)
+      if (k < K) {
+        z[k] = z[k] / se;   // p_k
+        sp += z[k];
+      }
+    const int c = clamp_label(a.labels[s], K);
+    float pc = 0.0f, wc = 0.0f, qbest = 0.0f;
+    int best = 0;
+#pragma unroll
+    for (int k = 0; k < ODB_MAX_K; ++k)
+      if (k < K) {
+        if (a.probs) a.probs[K * s + k] = z[k];
+        z[k] = z[k] / sp;   // q_k
+        if (k == c) {
+          pc = z[k];
+          wc = a.cw[k];
+        }
+        if (k == 0 || z[k] > qbest) {
+          qbest = z[k];
+          best = k;
+        }
+      }
+    const bool inside = pc >= lo && pc <= hi;
+    l = wc * (float)(-log((double)fminf(fmaxf(pc, lo), hi)));
+    h = best == c ? 1 : 0;
+    if (a.dz) {
+#pragma unroll
+      for (int k = 0; k < ODB_MAX_K; ++k)
+        if (k < K) a.dz[K * s + k] = inside ? wc * (z[k] - (k == c ? 1.0f : 0.0f)) / a.bsz : 0.0f;
+    }
+  }
+  loss[s] = l;
+  hit[s] = h;
+  __syncthreads();
+  if (s == 0) {
+    double lsum = 0.0;
+    int hits = 0;
+    for (int q = 0; q < a.B && q < ODB_MAX_BATCH; ++q) {
+      lsum += (double)loss[q];
+      hits += hit[q];
+    }
+    a.acc[0] += lsum;
+    a.acc[1] += (double)hits;
+  }
+}
+
+__global__ void head_bwd_k_kernel(OdbHead a, float* __restrict__ gw, float* __restrict__ gb,
+                                  float* __restrict__ demb) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int K = a.K, nw = ODB_HEAD_D * K;
+  float slope;
+  if (i < nw) {
+    const int d = i / K, k = i % K;
+    float acc = 0.0f;
+    for (int b = 0; b < a.B; ++b) acc = fmaf(head_in(a, b, d, &slope), a.dz[K * b + k], acc);
+    gw[i] = acc;
+  } else if (i < nw + K) {
+    const int k = i - nw;
+    float acc = 0.0f;
+    for (int b = 0; b < a.B; ++b) acc += a.dz[K * b + k];
+    gb[k] = acc;
+  } else if (i < nw + K + a.B * ODB_HEAD_D) {
+    const int q = i - nw - K;
+    const int b = q / ODB_HEAD_D, d = q % ODB_HEAD_D;
+    (void)head_in(a, b, d, &slope);
+    float acc = 0.0f;
+    for (int k = 0; k < K; ++k) acc = fmaf(a.dz[K * b + k], a.w[K * d + k], acc);
+    demb[q] = acc * slope;
+  }
+}
+
 // ---- Adadelta, bookkeeping ---------------------------------------------------------------------------------
 
 __global__ void adadelta_kernel(float* __restrict__ w, float* __restrict__ acc_g, float* __restrict__ acc_d,
@@ -511,8 +617,31 @@ __global__ void __launch_bounds__(AUC_NT) auc_count_kernel(const float* __restri
   out[1] = add ? out[1] + fp : fp;
 }
 
-__global__ void __launch_bounds__(AUC_NT) auc_final_kernel(uint32_t* counts, int slabs, int64_t n, int clear,
-                                                           float* __restrict__ out) {
+// K classes (2 < K <= ODB_MAX_K): the label's entry counts towards TP, the K - 1 others towards FP
+__global__ void __launch_bounds__(AUC_NT) auc_count_k_kernel(const float* __restrict__ probs,
+                                                             const int32_t* __restrict__ labels, int64_t n, int K,
+                                                             int64_t slab_len, OdbAucThr thr, int add,
+                                                             uint32_t* __restrict__ counts) {
+  const int t = threadIdx.x;
+  if (t >= ODB_AUC_T) return;
+  const float th = thr.t[t];
+  const int64_t r0 = (int64_t)blockIdx.x * slab_len, r1 = min(n, r0 + slab_len);
+  uint32_t tp = 0, fp = 0;
+  for (int64_t r = r0; r < r1; ++r) {
+    const int c = clamp_label(labels[r], K);
+    for (int k = 0; k < K; ++k) {
+      const uint32_t pos = probs[K * r + k] > th ? 1u : 0u;
+      tp += k == c ? pos : 0u;
+      fp += k == c ? 0u : pos;
+    }
+  }
+  uint32_t* out = counts + ((size_t)blockIdx.x * ODB_AUC_T + t) * 2;
+  out[0] = add ? out[0] + tp : tp;
+  out[1] = add ? out[1] + fp : fp;
+}
+
+__global__ void __launch_bounds__(AUC_NT) auc_final_kernel(uint32_t* counts, int slabs, int64_t n, int64_t n_neg,
+                                                           int clear, float* __restrict__ out) {
   __shared__ double rec[ODB_AUC_T], fpr[ODB_AUC_T];
   const int t = threadIdx.x;
   if (t < ODB_AUC_T) {
@@ -524,7 +653,7 @@ __global__ void __launch_bounds__(AUC_NT) auc_final_kernel(uint32_t* counts, int
       if (clear) at[0] = at[1] = 0u;
     }
     rec[t] = n > 0 ? (double)tp / (double)n : 0.0;
-    fpr[t] = n > 0 ? (double)fp / (double)n : 0.0;
+    fpr[t] = n > 0 ? (double)fp / (double)n_neg : 0.0;
   }
   __syncthreads();
   if (t != 0) return;
@@ -698,15 +827,21 @@ hipError_t odb_mean_h_bwd(const float* dxs, float* dx, int B, int h, int w, int 
 }
 
 hipError_t odb_head_loss(const OdbHead& a, hipStream_t stream) {
-  if (a.B < 1 || a.B > ODB_MAX_BATCH) return hipErrorInvalidValue;
-  ODB_LAUNCH(head_loss_kernel, dim3(1), dim3(ODB_MAX_BATCH), a);
+  if (a.B < 1 || a.B > ODB_MAX_BATCH || a.K < 2 || a.K > ODB_MAX_K) return hipErrorInvalidValue;
+  if (a.K == 2)
+    ODB_LAUNCH(head_loss_kernel, dim3(1), dim3(ODB_MAX_BATCH), a);
+  else
+    ODB_LAUNCH(head_loss_k_kernel, dim3(1), dim3(ODB_MAX_BATCH), a);
   return hipSuccess;
 }
 
 hipError_t odb_head_bwd(const OdbHead& a, float* gw, float* gb, float* demb, hipStream_t stream) {
-  if (a.B < 1 || a.B > ODB_MAX_BATCH || !a.dz) return hipErrorInvalidValue;
-  ODB_LAUNCH(head_bwd_kernel, grid1((int64_t)ODB_HEAD_D * 2 + 2 + (int64_t)a.B * ODB_HEAD_D, 256), dim3(256), a,
-             gw, gb, demb);
+  if (a.B < 1 || a.B > ODB_MAX_BATCH || !a.dz || a.K < 2 || a.K > ODB_MAX_K) return hipErrorInvalidValue;
+  const dim3 grid = grid1((int64_t)ODB_HEAD_D * a.K + a.K + (int64_t)a.B * ODB_HEAD_D, 256);
+  if (a.K == 2)
+    ODB_LAUNCH(head_bwd_kernel, grid, dim3(256), a, gw, gb, demb);
+  else
+    ODB_LAUNCH(head_bwd_k_kernel, grid, dim3(256), a, gw, gb, demb);
   return hipSuccess;
 }
 
@@ -753,17 +888,20 @@ int odb_auc_slabs(int64_t n) {
   return (int)(s < 1 ? 1 : s > ODB_AUC_SLABS ? ODB_AUC_SLABS : s);
 }
 
-hipError_t odb_auc_count(const float* probs, const int32_t* labels, int64_t n, const OdbAucThr& thr, int add,
+hipError_t odb_auc_count(const float* probs, const int32_t* labels, int64_t n, int K, const OdbAucThr& thr, int add,
                          uint32_t* counts, hipStream_t stream) {
-  if (n < 1) return hipErrorInvalidValue;
+  if (n < 1 || K < 2 || K > ODB_MAX_K) return hipErrorInvalidValue;
   const int S = odb_auc_slabs(n);
   const int64_t len = (n + S - 1) / S;   // ceil: slabs * len >= n, and every slab starts inside the rows
-  ODB_LAUNCH(auc_count_kernel, dim3(S), dim3(AUC_NT), probs, labels, n, len, thr, add, counts);
+  if (K == 2)
+    ODB_LAUNCH(auc_count_kernel, dim3(S), dim3(AUC_NT), probs, labels, n, len, thr, add, counts);
+  else
+    ODB_LAUNCH(auc_count_k_kernel, dim3(S), dim3(AUC_NT), probs, labels, n, K, len, thr, add, counts);
   return hipSuccess;
 }
 
-hipError_t odb_auc_final(uint32_t* counts, int slabs, int64_t n, int clear, float* out, hipStream_t stream) {
-  if (slabs < 1 || slabs > ODB_AUC_SLABS) return hipErrorInvalidValue;
-  ODB_LAUNCH(auc_final_kernel, dim3(1), dim3(AUC_NT), counts, slabs, n, clear, out);
+hipError_t odb_auc_final(uint32_t* counts, int slabs, int64_t n, int K, int clear, float* out, hipStream_t stream) {
+  if (slabs < 1 || slabs > ODB_AUC_SLABS || K < 2 || K > ODB_MAX_K) return hipErrorInvalidValue;
+  ODB_LAUNCH(auc_final_kernel, dim3(1), dim3(AUC_NT), counts, slabs, n, n * (int64_t)(K - 1), clear, out);
   return hipSuccess;
 }

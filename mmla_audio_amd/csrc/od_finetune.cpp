@@ -25,7 +25,7 @@ namespace {
 constexpr int kMinH = 8, kMaxH = OD_H, kMinW = 8, kMaxW = OD_W;
 constexpr int C = ODB_MAX_C;
 
-// offsets (in floats) of the tensors of weights.od_spec() in the packed blob
+// offsets (in floats) of the tensors of weights.od_spec(K) in the packed blob
 struct BlkOff {
   size_t bn_in, ca_w, ca_b, bn_mid, cb_w, cb_b, sc_w, sc_b;
   int cin, cout;
@@ -37,7 +37,7 @@ struct OdOff {
   size_t lk[2], lr[2], lb[2], dw, db, total;
 };
 
-OdOff od_offsets() {
+OdOff od_offsets(int K) {
   OdOff o{};
   size_t at = 0;
   auto take = [&](size_t n) {
@@ -70,8 +70,8 @@ OdOff od_offsets() {
     o.lr[d] = take((size_t)SIB_LSTM_U * SIB_LSTM_G);
     o.lb[d] = take(SIB_LSTM_G);
   }
-  o.dw = take((size_t)ODB_HEAD_D * 2);
-  o.db = take(2);
+  o.dw = take((size_t)ODB_HEAD_D * K);
+  o.db = take(K);
   o.total = at;
   return o;
 }
@@ -87,7 +87,8 @@ struct Engine {
   mmla_ctx* c = nullptr;
   OdOff off;
   int cap = 0, h = 0, w = 0, T = 0, hl = 0;   // hl x T: the last block's output
-  float cw[2] = {1.0f, 1.0f};
+  int K = 2;   // classes of the blob's head
+  float cw[ODB_MAX_K] = {1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f};
   float *W = nullptr, *G = nullptr, *acc_g = nullptr, *acc_d = nullptr, *wt = nullptr, *stem_w = nullptr,
         *stem_b = nullptr, *zero = nullptr, *part = nullptr, *stat_all = nullptr;
   uint8_t* trainable = nullptr;
@@ -169,7 +170,7 @@ void carve(Engine& e, Carver& cv, bool train) {
   e.part = cv.take<float>(part);
   e.seq = cv.take<float>(B * T * SIB_LSTM_D);
   e.emb = cv.take<float>(B * ODB_HEAD_D);
-  e.dzh = cv.take<float>(B * 2);
+  e.dzh = cv.take<float>(B * e.K);
   e.demb = cv.take<float>(B * ODB_HEAD_D);
   for (int q = 0; q < 3; ++q) e.gbuf[q] = cv.take<float>(B * pix * 32);
   SibLstm& l = e.lstm;
@@ -181,7 +182,7 @@ void carve(Engine& e, Carver& cv, bool train) {
   l.dc = cv.take<float>(2 * B * SIB_LSTM_U);
   l.dxs = cv.take<float>(2 * B * T * SIB_LSTM_D);
   e.sid = cv.take<int32_t>(B);
-  e.probs = cv.take<float>(B * 2);
+  e.probs = cv.take<float>(B * e.K);
   e.auc_n = cv.take<uint32_t>(2 * ODB_AUC_COUNTS);
   if (cv.base) {
     wire_lstm(l, e.off, e.W, e.G);
@@ -247,6 +248,23 @@ int batch_norm(Engine& e, bool train, const float* x, int64_t n_pos, int c, size
   return MMLA_OK;
 }
 
+OdbHead head_args(const Engine& e, int B, const uint8_t* mask, float* dz, double* acc, float* probs) {
+  OdbHead h{};
+  h.emb = e.emb;
+  h.mask = mask;
+  h.w = e.W + e.off.dw;
+  h.b = e.W + e.off.db;
+  h.labels = e.lb;
+  for (int k = 0; k < e.K; ++k) h.cw[k] = e.cw[k];
+  h.dz = dz;
+  h.acc = acc;
+  h.B = B;
+  h.bsz = (float)B;
+  h.probs = probs;
+  h.K = e.K;
+  return h;
+}
+
 // forward of the B images in xb / lb / mb; train: batch statistics (the moving ones advance), dropout, the
 // pools' winners and dz kept; else the moving statistics and no dropout.  acc: += loss sum, += hits
 int forward(Engine& e, int B, bool train, double* acc) {
@@ -279,11 +297,10 @@ int forward(Engine& e, int B, bool train, double* acc) {
   RUN(odb_mean_h(net, e.seq, B, e.hl, e.T, C, s));
   e.lstm.B = B;
   RUN(sib_lstm_fwd(e.lstm, s));
-  OdbHead h{e.emb, train ? e.mb : nullptr, W + e.off.dw, W + e.off.db, e.lb, {e.cw[0], e.cw[1]},
-            train ? e.dzh : nullptr, acc, B, (float)B, e.auc ? e.probs : nullptr};
-  RUN(odb_head_loss(h, s));
+  RUN(odb_head_loss(head_args(e, B, train ? e.mb : nullptr, train ? e.dzh : nullptr, acc, e.auc ? e.probs : nullptr),
+                    s));
   // Keras accumulates a metric over the batches of an epoch: the training-mode outputs, then the validation's
-  if (e.auc) RUN(odb_auc_count(e.probs, e.lb, B, e.thr, 1, e.auc_n + (train ? 0 : ODB_AUC_COUNTS), s));
+  if (e.auc) RUN(odb_auc_count(e.probs, e.lb, B, e.K, e.thr, 1, e.auc_n + (train ? 0 : ODB_AUC_COUNTS), s));
   return MMLA_OK;
 }
 
@@ -292,8 +309,7 @@ int backward(Engine& e, int B) {
   hipStream_t s = e.c->stream;
   const float* W = e.W;
   float* G = e.G;
-  OdbHead h{e.emb, e.mb, W + e.off.dw, W + e.off.db, e.lb, {e.cw[0], e.cw[1]}, e.dzh, nullptr, B, (float)B, nullptr};
-  RUN(odb_head_bwd(h, G + e.off.dw, G + e.off.db, e.demb, s));
+  RUN(odb_head_bwd(head_args(e, B, e.mb, e.dzh, nullptr, nullptr), G + e.off.dw, G + e.off.db, e.demb, s));
   RUN(sib_lstm_bwd(e.lstm, s));
   float *cur = e.gbuf[0], *f1 = e.gbuf[1], *f2 = e.gbuf[2];
   RUN(odb_mean_h_bwd(e.lstm.dxs, cur, B, e.hl, e.T, C, s));
@@ -335,22 +351,30 @@ int backward(Engine& e, int B) {
   return MMLA_OK;
 }
 
-int check_common(mmla_ctx* c, const char* who, int64_t n_floats, int32_t h, int32_t w, const float* class_w) {
-  const int64_t want = (int64_t)od_offsets().total;
-  if (n_floats != want)
-    return fail(c, MMLA_E_INVALID, "%s: n_floats %lld, the OD blob has %lld", who, (long long)n_floats,
-                (long long)want);
+// the classes of a blob of n_floats (body + 513 K), or 0
+int blob_classes(int64_t n_floats) {
+  const int64_t head = n_floats - od_body_floats();
+  return head >= 513 * 2 && head <= 513 * (int64_t)MMLA_OD_MAX_CLASSES && head % 513 == 0 ? (int)(head / 513) : 0;
+}
+
+// *K: the blob's classes
+int check_common(mmla_ctx* c, const char* who, int64_t n_floats, int32_t h, int32_t w, const float* class_w, int* K) {
+  *K = blob_classes(n_floats);
+  if (!*K)
+    return fail(c, MMLA_E_INVALID, "%s: n_floats %lld, the OD blob has %lld + 513 K with K in [2, %d]", who,
+                (long long)n_floats, (long long)od_body_floats(), MMLA_OD_MAX_CLASSES);
   if (h < kMinH || h > kMaxH || w < kMinW || w > kMaxW)
     return fail(c, MMLA_E_INVALID, "%s: image %d x %d outside [%d, %d] x [%d, %d]", who, h, w, kMinH, kMaxH, kMinW,
                 kMaxW);
   if (!class_w) return fail(c, MMLA_E_INVALID, "%s: null pointer", who);
-  for (int k = 0; k < 2; ++k)
+  for (int k = 0; k < *K; ++k)
     if (!std::isfinite(class_w[k]) || class_w[k] < 0.0f)
       return fail(c, MMLA_E_INVALID, "%s: class_w[%d] = %g is negative or not finite", who, k, class_w[k]);
   return MMLA_OK;
 }
 
-constexpr const char* kLabelSet = "{0, 1}";
+// how check_labels names the labels of K classes (null: "[0, K)")
+const char* label_set(int K) { return K == 2 ? "{0, 1}" : nullptr; }
 
 int prepare(Engine& e, bool train) {
   hipStream_t s = e.c->stream;
@@ -366,13 +390,13 @@ int prepare(Engine& e, bool train) {
 }
 
 // the engine of a checked call: the blob's size, the class weights, every block's dimensions
-Engine engine(mmla_ctx* c, int cap, int h, int w, const float* class_w) {
+Engine engine(mmla_ctx* c, int K, int cap, int h, int w, const float* class_w) {
   Engine e;
   e.c = c;
   e.cap = cap;
-  e.off = od_offsets();
-  e.cw[0] = class_w[0];
-  e.cw[1] = class_w[1];
+  e.K = K;
+  e.off = od_offsets(K);
+  for (int k = 0; k < K; ++k) e.cw[k] = class_w[k];
   set_dims(e, h, w);
   return e;
 }
@@ -384,15 +408,16 @@ int od_fit(mmla_ctx* c, FitCall a, int32_t h, int32_t w, const float* class_w, c
            const uint8_t* drop_mask, bool scratch, int64_t drop_seed) {
   if (!c) return MMLA_E_INVALID;
   const char* who = a.who;
-  CHK(check_common(c, who, (int64_t)a.n_floats, h, w, class_w));
+  int K = 0;
+  CHK(check_common(c, who, (int64_t)a.n_floats, h, w, class_w, &K));
   const int32_t epochs = a.epochs;
   const int64_t n_train = a.n_train;
   a.unit = "images";
   a.slot = S_ODFT;
   a.max_batch = MMLA_OD_TRAIN_MAX_BATCH;
   a.val_chunk = 16;
-  a.n_classes = 2;
-  a.label_set = kLabelSet;
+  a.n_classes = K;
+  a.label_set = label_set(K);
   a.row_bytes = (size_t)h * w * 3;
   // rows after an early stop
   a.nan_fill = [](float* hist, size_t n, hipStream_t s) { return odb_fill(hist, (int64_t)n, __builtin_nanf(""), s); };
@@ -401,7 +426,7 @@ int od_fit(mmla_ctx* c, FitCall a, int32_t h, int32_t w, const float* class_w, c
   for (int ep = 0; ep < epochs; ++ep)
     if (!std::isfinite(lr[ep]) || lr[ep] < 0.0f)
       return fail(c, MMLA_E_INVALID, "%s: lr[%d] = %g is negative or not finite", who, ep, lr[ep]);
-  Engine e = engine(c, a.cap(), h, w, class_w);
+  Engine e = engine(c, K, a.cap(), h, w, class_w);
   e.auc = scratch;
   if (scratch) e.thr = odb_auc_thresholds();
   hipStream_t s = c->stream;
@@ -442,8 +467,8 @@ int od_fit(mmla_ctx* c, FitCall a, int32_t h, int32_t w, const float* class_w, c
       [&](int ep, float* row) -> int {
         RUN(odb_end_epoch(e.st, n, nv, dlr, ep, row, s));
         if (!scratch) return MMLA_OK;
-        RUN(odb_auc_final(e.auc_n, 1, n, 1, row + 5, s));
-        RUN(odb_auc_final(e.auc_n + ODB_AUC_COUNTS, 1, nv, 1, row + 6, s));   // NaN when n_val == 0
+        RUN(odb_auc_final(e.auc_n, 1, n, K, 1, row + 5, s));
+        RUN(odb_auc_final(e.auc_n + ODB_AUC_COUNTS, 1, nv, K, 1, row + 6, s));   // NaN when n_val == 0
         return MMLA_OK;
       });
 }
@@ -462,14 +487,15 @@ int mmla_od_loss_grad(mmla_ctx* c, const float* packed, int64_t n_floats, const 
                       const int32_t* labels, int64_t n, int32_t h, int32_t w, const float* class_w,
                       const uint8_t* drop_mask, float* loss, float* grad, float* moving_out, uint32_t flags) {
   if (!c) return MMLA_E_INVALID;
-  CHK(check_common(c, "od_loss_grad", n_floats, h, w, class_w));
+  int K = 0;
+  CHK(check_common(c, "od_loss_grad", n_floats, h, w, class_w, &K));
   if (n < 1 || n > MMLA_OD_TRAIN_MAX_BATCH)
     return fail(c, MMLA_E_INVALID, "od_loss_grad: n %lld outside [1, %d]", (long long)n, MMLA_OD_TRAIN_MAX_BATCH);
   if (!packed || !img_u8 || !labels || !loss || !grad) return fail(c, MMLA_E_INVALID, "od_loss_grad: null pointer");
   Stager st{c, (flags & MMLA_DEVICE_PTR) != 0};
-  if (!st.dev) CHK(check_labels(c, "labels", labels, n, 2, kLabelSet));
+  if (!st.dev) CHK(check_labels(c, "labels", labels, n, K, label_set(K)));
   HIPCHK(c, hipSetDevice(c->device));
-  Engine e = engine(c, (int)n, h, w, class_w);
+  Engine e = engine(c, K, (int)n, h, w, class_w);
   const size_t img_bytes = (size_t)h * w * 3;
   float* lp = nullptr;
   const uint8_t *dimg = nullptr, *dmask = nullptr;
@@ -556,11 +582,19 @@ int mmla_od_drop_mask(mmla_ctx* c, int64_t drop_seed, int32_t epoch, const int32
 }
 
 int mmla_od_auc(mmla_ctx* c, const float* probs, const int32_t* labels, int64_t n, float* auc_out, uint32_t flags) {
+  return mmla_od_auc_k(c, probs, labels, n, 2, auc_out, flags);
+}
+
+int mmla_od_auc_k(mmla_ctx* c, const float* probs, const int32_t* labels, int64_t n, int32_t n_classes,
+                  float* auc_out, uint32_t flags) {
   if (!c) return MMLA_E_INVALID;
+  const int K = n_classes;
+  if (K < 2 || K > MMLA_OD_MAX_CLASSES)
+    return fail(c, MMLA_E_INVALID, "od_auc: n_classes %d outside [2, %d]", K, MMLA_OD_MAX_CLASSES);
   if (n < 1 || n > (1 << 24)) return fail(c, MMLA_E_INVALID, "od_auc: n %lld outside [1, 2^24]", (long long)n);
   if (!probs || !labels || !auc_out) return fail(c, MMLA_E_INVALID, "od_auc: null pointer");
   Stager st{c, (flags & MMLA_DEVICE_PTR) != 0};
-  if (!st.dev) CHK(check_labels(c, "labels", labels, n, 2, kLabelSet));
+  if (!st.dev) CHK(check_labels(c, "labels", labels, n, K, label_set(K)));
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const int S = odb_auc_slabs(n);
@@ -570,13 +604,13 @@ int mmla_od_auc(mmla_ctx* c, const float* probs, const int32_t* labels, int64_t 
   float* da = nullptr;
   CHK(carve_slot(c, S_ODFT, [&](Carver& cv) -> int {
     counts = cv.take<uint32_t>((size_t)S * ODB_AUC_COUNTS);
-    CHK(st.in(cv, probs, (size_t)n * 2, &dp));
+    CHK(st.in(cv, probs, (size_t)n * K, &dp));
     CHK(st.in(cv, labels, (size_t)n, &dl));
     da = st.out(cv, auc_out, 1);
     return MMLA_OK;
   }));
-  RUN(odb_auc_count(dp, dl, n, odb_auc_thresholds(), 0, counts, s));
-  RUN(odb_auc_final(counts, S, n, 0, da, s));
+  RUN(odb_auc_count(dp, dl, n, K, odb_auc_thresholds(), 0, counts, s));
+  RUN(odb_auc_final(counts, S, n, K, 0, da, s));
   CHK(st.back(auc_out, da, 1));
   return finish(c, st.dev);
 }

@@ -322,9 +322,10 @@ int od_forward_common(mmla_ctx* c, const float* x_f32, const uint8_t* x_u8, int6
     if (x_f32) CHK(in_ptr(c, x_f32 + c0 * OD_IMG, cnt * OD_IMG, dev, S_IN, &df));
     else CHK(in_ptr(c, x_u8 + c0 * OD_IMG, cnt * OD_IMG, dev, S_IMG, &du));
     float* dp;
-    CHK(out_ptr(c, probs, c0 * 2, cnt * 2, dev, S_OUT0, &dp));
+    const int k = c->od.k;
+    CHK(out_ptr(c, probs, c0 * k, cnt * k, dev, S_OUT0, &dp));
     CHK(run_od_net(c, ar, du, df, cnt, dp, nullptr));
-    return copy_back(c, probs, c0 * 2, dp, cnt * 2, dev);
+    return copy_back(c, probs, c0 * k, dp, cnt * k, dev);
   });
 }
 
@@ -362,13 +363,14 @@ int od_net_out(mmla_ctx* c, const Arith& ar, const uint8_t* img, const Pcm& p, O
                bool dev, float* probs, int32_t* argmax, uint8_t* silent) {
   float* dp;
   int32_t* da;
-  CHK(out_ptr(c, probs, c0 * 2, cnt * 2, dev, S_OUT0, &dp));
+  const int k = c->od.k;   // the loaded head's classes
+  CHK(out_ptr(c, probs, c0 * k, cnt * k, dev, S_OUT0, &dp));
   CHK(out_ptr(c, argmax, c0, cnt, dev, S_OUT1, &da));
   CHK(out_ptr(c, silent, c0, cnt, dev, S_OUT2, &g.silent));
   g.lens = p.lens;
   g.clip_len = p.true_len;
   CHK(run_od_net(c, ar, img, nullptr, cnt, dp, da, g));
-  CHK(copy_back(c, probs, c0 * 2, dp, cnt * 2, dev));
+  CHK(copy_back(c, probs, c0 * k, dp, cnt * k, dev));
   CHK(copy_back(c, argmax, c0, da, cnt, dev));
   return copy_back(c, silent, c0, g.silent, cnt, dev);
 }

@@ -187,7 +187,14 @@ extern "C" int mmla_load_weights(mmla_ctx* c, int kind, const float* packed, int
   HIPCHK(c, hipStreamSynchronize(c->stream));
   Cursor cur{packed, n_floats};
   if (kind == MMLA_MODEL_OD) {
-    if (n_classes != 2) return fail(c, MMLA_E_INVALID, "OD model has 2 classes, got %d", n_classes);
+    if (n_classes < 2 || n_classes > MMLA_OD_MAX_CLASSES)
+      return fail(c, MMLA_E_INVALID, "OD n_classes %d outside [2, %d]", n_classes, MMLA_OD_MAX_CLASSES);
+    // more than two classes: the size is checked before the loaded model is let go (a two-class blob of the
+    // wrong size keeps its MMLA_E_SHAPE below)
+    const int64_t want = od_blob_floats(n_classes);
+    if (n_classes != 2 && n_floats != want)
+      return fail(c, MMLA_E_INVALID, "OD blob of %lld floats, %d classes need %lld", (long long)n_floats, n_classes,
+                  (long long)want);
     free_allocs(c->od_allocs);
     c->od_loaded = false;
     OdNet& W = c->od;
@@ -195,11 +202,12 @@ extern "C" int mmla_load_weights(mmla_ctx* c, int kind, const float* packed, int
     CHK(take_conv(c, cur, al, 1, 1, 3, 16, &W.stem));
     CHK(take_units(c, cur, al, W.blk, 16, 3, 3, 4, 1, true));
     CHK(take_lstm(c, cur, al, 128, &W.lstm));
-    const float* hw = cur.take(512 * 2);
-    const float* hb = cur.take(2);
+    const float* hw = cur.take(512 * (int64_t)n_classes);
+    const float* hb = cur.take(n_classes);
     if (!cur.ok) return fail(c, MMLA_E_SHAPE, "OD weight blob too short");
-    CHK(upload(c, al, hw, 512 * 2 * sizeof(float), &W.head_w));
-    CHK(upload(c, al, hb, 2 * sizeof(float), &W.head_b));
+    CHK(upload(c, al, hw, 512 * (size_t)n_classes * sizeof(float), &W.head_w));
+    CHK(upload(c, al, hb, (size_t)n_classes * sizeof(float), &W.head_b));
+    W.k = n_classes;
     if (cur.left != 0)
       return fail(c, MMLA_E_SHAPE, "OD weight blob has %lld extra floats", (long long)cur.left);
     c->od_f32_only = cur.f16_bad;   // some weight outside the fp16 range: exact f32 only
@@ -231,6 +239,14 @@ extern "C" int mmla_load_weights(mmla_ctx* c, int kind, const float* packed, int
     return MMLA_OK;
   }
   return fail(c, MMLA_E_INVALID, "unknown model kind %d", kind);
+}
+
+extern "C" int mmla_od_classes(mmla_ctx* c, int32_t* k) {
+  if (!c) return MMLA_E_INVALID;
+  if (!k) return fail(c, MMLA_E_INVALID, "od_classes: null pointer");
+  if (!c->od_loaded) return fail(c, MMLA_E_NOWEIGHTS, "OD weights not loaded");
+  *k = c->od.k;
+  return MMLA_OK;
 }
 
 // The Dense head of the loaded SI model replaced in place: the tensors go through take_conv as the

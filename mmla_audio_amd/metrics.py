@@ -58,8 +58,9 @@ def structural_similarity(im1, im2, *, win_size=None, gradient=False, data_range
 
 def auc(probs, labels):
     """``tf.keras.metrics.AUC()`` at its defaults, as ``OverlapDetector.train_model`` compiles it
-    (overlap_detector.py:403), through ``mmla_od_auc``: probs float32 [n, 2] against labels [n] in {0, 1} (or
-    their one-hot rows [n, 2]) -> float.  include/mmla.h states the thresholds and the one deliberate
+    (overlap_detector.py:403), through ``mmla_od_auc_k``: probs float32 [n, K] against labels [n] in [0, K) (or
+    their one-hot rows [n, K]), K = 2 .. 8 -> float.  multi_label = False: the n K entries are binary
+    predictions against the one-hot entries.  include/mmla.h states the thresholds and the one deliberate
     deviation (the final sum in double)."""
     labels = np.asarray(labels)
     if labels.ndim == 2:

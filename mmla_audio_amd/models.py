@@ -99,21 +99,24 @@ class _Model:
 
 
 class OverlapDetectionModel(_Model):
-    """OD-NET (ResLSTM, overlap_detector_temp.py:280-303): predict(float32 [N,128,151,3]) -> [N,2]."""
+    """OD-NET (ResLSTM, overlap_detector_temp.py:280-303): predict(float32 [N,128,151,3]) -> [N,K].  K, the
+    classes of the softmax head, is the width of W's Dense kernel: 2 for the deployed model, 3 for the
+    reference's research models; every [N,2] below is [N,K] for such a model."""
     kind = weights.OD
 
     def __init__(self, W, device=None, synthetic=False):
-        super().__init__(W, 2, _lib.HEAD_SOFTMAX, device, synthetic)
+        super().__init__(W, weights.od_classes(W), _lib.HEAD_SOFTMAX, device, synthetic)
         setattr(self.ctx, f'_owner_{self.kind}', self)
 
     def set_weights(self, W):
         """Replace every tensor of the model in place (one ``mmla_load_weights`` of the whole blob): the
         network an adaptation produced (``overlap_detector.continue_train``).  self.W follows only once
         the load succeeded."""
-        blob = weights.pack(self.kind, W)
-        self.ctx.load_weights(self.kind, blob, 2, _lib.HEAD_SOFTMAX)
+        k = weights.od_classes(W)
+        blob = weights.pack(self.kind, W, k)
+        self.ctx.load_weights(self.kind, blob, k, _lib.HEAD_SOFTMAX)
         setattr(self.ctx, f'_owner_{self.kind}', self)
-        self.W = dict(W)
+        self.W, self.n_classes = dict(W), k
 
     def predict(self, x, batch_size=None, verbose=0):
         self._ensure_loaded()
@@ -272,6 +275,8 @@ def load_model(path, kind=None, n_classes=None, head=None, seed=0, device=None,
         if lay is not None and kind == weights.SI:   # the layout the index names (K, head)
             n_classes = lay[1] if n_classes is None else n_classes
             head = lay[2] if head is None else head
+        if lay is not None and kind == weights.OD and lay[0] == weights.OD and n_classes is None:
+            n_classes = lay[1]                        # the Dense shape the index names
         warnings.warn(f'{path}: trained weights absent (reference .MISSING_LARGE_BLOBS); using seeded '
                       f'synthetic weights in the reference layout (seed={seed})')
         W = weights.synthetic(kind, seed=seed, n_classes=n_classes)

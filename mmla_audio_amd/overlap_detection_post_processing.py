@@ -35,6 +35,13 @@ OVERLAP_DEGREE = {'0': 'non-overlapped', '1': 'overlapped'}   # overlap_detectio
 LABELS = dict(OVERLAP_DEGREE, **{'-1': 'silent'})
 
 
+def class_label(k, n_classes=2):
+    """The log's text for class k of an n_classes-way model: the reference names the two-class model's classes
+    alone, so a model with more classes logs the class number; -1 is 'silent' for every model."""
+    k = int(k)
+    return LABELS[str(k)] if n_classes == 2 or k == -1 else str(k)
+
+
 def segment_bounds(nframes, framerate, win_time_stride, step_time):
     """(window frames, step frames, segment count) exactly as the reference computes them (:50-53)."""
     win = int(framerate * win_time_stride)
@@ -82,7 +89,8 @@ def segmentation(src_dir, dst_dir, win_time_stride, step_time, fixed_format=None
 def predict_segments(pcm, model, sr=16000, win_time_stride=1.5, step_time=1.5):
     """All windows of one mono 16 kHz int16 conversation through the fused OD pipeline.
 
-    Returns (probs float32 [n, 2], argmax int32 [n], labels list of 'overlapped'/'non-overlapped').
+    Returns (probs float32 [n, K], argmax int32 [n], labels list of 'overlapped'/'non-overlapped'; of the
+    class numbers as strings for a model with K > 2 classes).
     ``model`` is an ``OverlapDetectionModel`` (``models.load_model``).
     """
     if sr != 16000:
@@ -90,10 +98,10 @@ def predict_segments(pcm, model, sr=16000, win_time_stride=1.5, step_time=1.5):
     sig = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
     win, step, n = segment_bounds(sig.size, sr, win_time_stride, step_time)
     if n == 0:
-        return np.zeros((0, 2), np.float32), np.zeros(0, np.int32), []
+        return np.zeros((0, model.n_classes), np.float32), np.zeros(0, np.int32), []
     model._ensure_loaded()
     probs, am = model.ctx.od_pipeline_strided(sig, n, step, win)
-    return probs, am, [LABELS[str(int(k))] for k in am]
+    return probs, am, [class_label(k, model.n_classes) for k in am]
 
 
 def predict_wav(path, model, win_time_stride=1.5, step_time=1.5):
@@ -106,9 +114,10 @@ def predict_wav(path, model, win_time_stride=1.5, step_time=1.5):
     return predict_segments(sig, model, framerate, win_time_stride, step_time)
 
 
-def write_log(log_path, argmax, start_time=None):
+def write_log(log_path, argmax, start_time=None, n_classes=2):
     """The per-conversation TSV log of post_anlysing (:212-226): a header, then one line per
-    segment with its overlap degree and a timestamp advancing 1.5 s per segment (hard-coded there)."""
+    segment with its overlap degree (``class_label``) and a timestamp advancing 1.5 s per segment
+    (hard-coded there)."""
     time = start_time or datetime.today()
     with open(log_path, 'w') as f:
         f.write('segment' + '\t' + 'overlapped degree' + '\t' + 'timestamp')
@@ -116,7 +125,7 @@ def write_log(log_path, argmax, start_time=None):
         for count, k in enumerate(argmax):
             if count > 0:
                 time = time + timedelta(seconds=1.5)
-            f.write(str(count) + '\t' + str(LABELS[str(int(k))]) + '\t' + str(time))
+            f.write(str(count) + '\t' + class_label(k, n_classes) + '\t' + str(time))
             f.write('\n')
 
 
@@ -249,12 +258,12 @@ def predict_frames(x, nchannels, model, sr=16000, win_time_stride=1.5, step_time
     y = np.ascontiguousarray(y, dtype=np.float32)
     win, step, n = segment_bounds(y.size, sr, win_time_stride, step_time)
     if n == 0:
-        return np.zeros((0, 2), np.float32), np.zeros(0, np.int32), []
+        return np.zeros((0, model.n_classes), np.float32), np.zeros(0, np.int32), []
     model._ensure_loaded()
     f = model.ctx.od_features_strided(y, n, step, win, db=False, norm=False, zcr=False, img=True)
     probs = model.ctx.od_forward(f['img'])
     am = probs.argmax(1).astype(np.int32)
-    return probs, am, [LABELS[str(int(k))] for k in am]
+    return probs, am, [class_label(k, model.n_classes) for k in am]
 
 
 def _segment_index(name):
@@ -273,7 +282,7 @@ def _window_images(x, nchannels, model, sr, win_time_stride, step_time):
             -1, nchannels).T, axis=0), dtype=np.float32)
     win, step, n = segment_bounds(sig.size, sr, win_time_stride, step_time)
     if n == 0:
-        return np.zeros((0, 128, 151, 3), np.uint8), np.zeros((0, 2), np.float32)
+        return np.zeros((0, 128, 151, 3), np.uint8), np.zeros((0, model.n_classes), np.float32)
     model._ensure_loaded()
     f = model.ctx.od_features_strided(sig, n, step, win, db=False, norm=False, zcr=False, img=True)
     return f['img'], model.ctx.od_forward(f['img'])
@@ -325,7 +334,7 @@ def post_anlysing(root_dir, model, ctx=None, noise_path=None, start_time=None, w
         time = start_time if start_time is not None else datetime.today()
         rate, nch, _, pcm = _read_wav(std[i])
         images, probs = _window_images(pcm, nch, model, rate, 1.5, 1.5)
-        labels = [LABELS[str(int(k))] for k in probs.argmax(1)]
+        labels = [class_label(k, model.n_classes) for k in probs.argmax(1)]
         rows = []
         with open(logs[i], 'w') as f:
             f.write('segment' + '\t' + 'overlapped degree' + '\t' + 'timestamp')
@@ -339,7 +348,7 @@ def post_anlysing(root_dir, model, ctx=None, noise_path=None, start_time=None, w
                 else:   # not a window of this conversation: predict the file itself
                     r2, c2, _, x2 = _read_wav(os.path.join(seg_dir, name))
                     im2, p2 = _window_images(x2, c2, model, r2, len(x2) / c2 / r2, 1.5)
-                    label, img = LABELS[str(int(p2.argmax(1)[0]))], im2[0]
+                    label, img = class_label(p2.argmax(1)[0], model.n_classes), im2[0]
                 if write_features:
                     write_png_rgba(feats[i] + str(count) + '.png', img)
                 f.write(str(count) + '\t' + str(label) + '\t' + str(time))

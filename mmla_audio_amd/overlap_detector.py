@@ -7,8 +7,12 @@ and the AUC metric, after the pyramid-blur class balancing of ``augment_images``
 ``mmla_od_augment``).  include/mmla.h states what is computed; parity with TensorFlow and OpenCV themselves
 is unpinned.
 
+The detector has K classes, 2 <= K <= ``weights.OD_MAX_CLASSES``: two for the deployed model, three (``Overlap``
+column values 0, 1, 2; class 2 = overlapped) for the reference's research models.  ``train_model`` takes K from
+the labels, ``continue_train`` from the weights, and ``evaluation`` (:513-543) scores the last class.
+
 Not here: the xlsx / PNG dataset loaders, ``StratifiedKFold``, ``restore_best_weights`` (the reference never
-sets it), the three-class variant of ``evaluation`` and multi-GPU training.
+sets it) and multi-GPU training.
 """
 import math
 
@@ -51,20 +55,21 @@ def fit_plan(labels, seed, epochs, val_ratio=0.2):
 
 
 def continue_train(W, images, labels, plan, epochs, batch_size, weighted=True, patience=10, device=None):
-    """``continue_train_model`` on the device: W {name: array} (weights.od_spec), images uint8 [n,h,w,3],
-    labels [n] in {0, 1}, plan = fit_plan(labels, seed, epochs).  weighted: the loss's class weights are
-    cal_weighted_penalty of the training labels, else [1, 1].
+    """``continue_train_model`` on the device: W {name: array} (weights.od_spec(K), K from its head), images
+    uint8 [n,h,w,3], labels [n] in [0, K), plan = fit_plan(labels, seed, epochs).  weighted: the loss's class
+    weights are cal_weighted_penalty of the training labels, else ones.
     -> (W' {name: float32 array}, history [epochs_total, 5] = loss, acc, val_loss, val_acc, lr, epochs_run)"""
     ctx = device if isinstance(device, _lib.Context) else _lib.default_context(device)
     images = np.asarray(images, np.uint8)
     labels = np.asarray(labels, np.int32)
     tr, va = plan['train'], plan['val']
-    cw = cal_weighted_penalty(np.eye(2)[labels[tr]]) if weighted else np.ones(2)
-    out, hist, ran = ctx.od_finetune(weights.pack(weights.OD, W), images[tr], labels[tr],
+    K = weights.od_classes(W)
+    cw = cal_weighted_penalty(np.eye(K)[labels[tr]]) if weighted else np.ones(K)
+    out, hist, ran = ctx.od_finetune(weights.pack(weights.OD, W, K), images[tr], labels[tr],
                                      images[va] if len(va) else None, labels[va] if len(va) else None, cw,
                                      cosine_lr(epochs), plan['perm'], plan['drop_mask'], epochs, batch_size,
                                      patience)
-    return weights.unpack(weights.OD, out), hist, ran
+    return weights.unpack(weights.OD, out, K), hist, ran
 
 
 # ---- training from scratch: augment_images (:143-220), train_model (:392-451) -----------------------------
@@ -86,15 +91,28 @@ class History:
 
 
 def _class_labels(y, what):
-    """labels [n] of integers, or one-hot rows [n, 2] as ``labels_loader`` returns them -> int32 [n]"""
+    """labels [n] of integers, or one-hot rows [n, K] as ``labels_loader`` returns them -> int32 [n]"""
     y = np.asarray(y)
     if y.ndim == 2:
-        if y.shape[1] != 2 or not (((y == 0) | (y == 1)).all() and (y.sum(axis=1) == 1).all()):
-            raise ValueError(f'{what} {y.shape}: expected one-hot rows of two classes')
+        if not 2 <= y.shape[1] <= weights.OD_MAX_CLASSES or \
+                not (((y == 0) | (y == 1)).all() and (y.sum(axis=1) == 1).all()):
+            raise ValueError(f'{what} {y.shape}: expected one-hot rows of 2..{weights.OD_MAX_CLASSES} classes')
         return y.argmax(axis=1).astype(np.int32)
     if y.ndim != 1 or not np.issubdtype(y.dtype, np.integer):
-        raise ValueError(f'{what} {y.shape} {y.dtype}: expected integer labels [n] or one-hot rows [n,2]')
+        raise ValueError(f'{what} {y.shape} {y.dtype}: expected integer labels [n] or one-hot rows [n,K]')
     return y.astype(np.int32)
+
+
+def _n_classes(n_classes, *ys):
+    """K of a fit: the given one, else the one-hot width of the first two-dimensional y, else max label + 1;
+    never below 2"""
+    if n_classes is not None:
+        return int(n_classes)
+    for y in ys:
+        if y is not None and np.ndim(y) == 2:
+            return max(2, int(np.shape(y)[1]))
+    top = max([int(np.max(y)) for y in ys if y is not None and np.size(y)], default=1)
+    return max(2, top + 1)
 
 
 def augment_plan(labels, n_classes=None):
@@ -140,13 +158,15 @@ def augment_images(images, labels, ctx=None):
 
 
 def train_model(x_train, y_train, x_val, y_val, *, epochs, batch_size, weighted=False, augmented=False, seed=0,
-                patience=10, checkpoint_path=None, save_path=None, device=None):
+                patience=10, checkpoint_path=None, save_path=None, device=None, n_classes=None):
     """``OverlapDetector.train_model`` on the device (``mmla_od_train``): ``__ResBLSTM`` from its Keras initial
     state (``weights.initial_od(seed)``) under Adadelta with the cosine schedule, EarlyStopping(val_loss,
     patience) and ModelCheckpoint(val_categorical_accuracy, save_best_only, 'max', period=1).  Images uint8
     [n,h,w,3]; labels integers or one-hot rows.  augmented: the training set is balanced first
     (``augment_images``); weighted: the loss's class weights are ``cal_weighted_penalty`` of the (possibly
-    augmented) training labels, else [1, 1].  x_val None or empty: no validation set, no callbacks.
+    augmented) training labels, else ones.  n_classes (the script's ``class_dim = y_train.shape[1]``, :394):
+    None = the width of one-hot labels, or the largest label + 1, never below 2.  x_val None or empty: no
+    validation set, no callbacks.
     -> (OverlapDetectionModel, History): the model holds the LAST epoch's weights (no restore_best_weights)
     and is installed on the device.  The best checkpoint's weights go to checkpoint_path when one was taken,
     the final model to save_path (``tfbundle.save_overlap``).  Everything random comes from `seed` through
@@ -170,24 +190,56 @@ def train_model(x_train, y_train, x_val, y_val, *, epochs, batch_size, weighted=
     epochs = int(epochs)
     if epochs < 0 or batch_size < 1:
         raise ValueError('epochs must be >= 0 and batch_size >= 1')
+    K = _n_classes(n_classes, y_train, y_val if nv else None)
+    if not 2 <= K <= weights.OD_MAX_CLASSES:
+        raise ValueError(f'n_classes {K} outside [2, {weights.OD_MAX_CLASSES}]')
+    for what, l in (('y_train', labels), ('y_val', vl)):
+        if l is not None and len(l) and (l.min() < 0 or l.max() >= K):
+            raise ValueError(f'{what}: a label outside the {K} classes')
     if augmented:
-        src, levels, labels = augment_plan(labels, 2)
+        src, levels, labels = augment_plan(labels, K)
         x_train = ctx.od_augment(x_train, src, levels)
-    cw = cal_weighted_penalty(np.eye(2)[labels]) if weighted else np.ones(2)
+    cw = cal_weighted_penalty(np.eye(K)[labels]) if weighted else np.ones(K)
     n = len(labels)
     rng_p = np.random.default_rng([int(seed), 1])       # fit_plan's generator of the epochs' orders
     perm = np.stack([rng_p.permutation(n) for _ in range(epochs)]).astype(np.int32) if epochs else \
         np.zeros((0, n), np.int32)
     drop_seed = int(np.random.default_rng([int(seed), 2]).integers(0, 2 ** 63))
-    W0 = weights.initial_od(seed)
-    out, best, hist, ran, best_ep = ctx.od_train(weights.pack(weights.OD, W0), x_train, labels, vx, vl, cw,
+    W0 = weights.initial_od(seed, K)
+    out, best, hist, ran, best_ep = ctx.od_train(weights.pack(weights.OD, W0, K), x_train, labels, vx, vl, cw,
                                                  cosine_lr(epochs), perm, epochs, batch_size, drop_seed, patience,
                                                  1)
-    model = models.OverlapDetectionModel(weights.unpack(weights.OD, out), device=ctx)
+    model = models.OverlapDetectionModel(weights.unpack(weights.OD, out, K), device=ctx)
     if checkpoint_path is not None and best is not None:
         os.makedirs(checkpoint_path, exist_ok=True)
-        tfbundle.save_overlap(checkpoint_path, weights.unpack(weights.OD, best))
+        tfbundle.save_overlap(checkpoint_path, weights.unpack(weights.OD, best, K))
     if save_path is not None:
         os.makedirs(save_path, exist_ok=True)
         tfbundle.save_overlap(save_path, model.W)
     return model, History(hist, ran, best_ep)
+
+
+def evaluation(model, x_eval, y_eval):
+    """``OverlapDetector.evaluation`` (:513-543) for a K-class model: the argmax of ``model.predict(x_eval)``
+    against y_eval (integers [n] or one-hot rows [n, K]) -> (confusion [K, K] float64, rows = ground truth,
+    columns = predicted; recall and precision of class K - 1, the script's 'overlapped' class: NaN where the
+    script divides 0 by 0).  Printed as the script prints them."""
+    K = int(model.n_classes)
+    truth = _class_labels(y_eval, 'y_eval')
+    if len(truth) and (truth.min() < 0 or truth.max() >= K):
+        raise ValueError(f'y_eval: a label outside the {K} classes')
+    predicted = np.argmax(model.predict(x_eval), axis=1)
+    if len(predicted) != len(truth):
+        raise ValueError(f'x_eval / y_eval: {len(predicted)} predictions for {len(truth)} labels')
+    confusion_matrix = np.zeros((K, K))
+    np.add.at(confusion_matrix, (truth, predicted), 1)
+    tp = confusion_matrix[K - 1, K - 1]
+    fn = confusion_matrix[K - 1, :K - 1].sum()
+    fp = confusion_matrix[:K - 1, K - 1].sum()
+    with np.errstate(invalid='ignore', divide='ignore'):
+        recall = np.float64(tp) / (tp + fn)
+        precision = np.float64(tp) / (tp + fp)
+    # rows = ground truth; cols = predicted
+    print(confusion_matrix)
+    print('Overlapped recall: ', recall, " precision: ", precision)
+    return confusion_matrix, float(recall), float(precision)

@@ -17,7 +17,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from .overlap_detection_post_processing import LABELS as _OD_LABELS
+from .overlap_detection_post_processing import class_label as _od_label
 
 RoomResult = namedtuple('RoomResult', 'od_probs od_argmax si_probs si_argmax silent kept_len pcm',
                         defaults=(None,))
@@ -75,8 +75,9 @@ class Room:
 
     def tick(self, pcm, mic=None, lens=None, passes=1, silence_remove=True, items_per_stream=1,
              reset_vad=False, return_pcm=False, reset_capture=False):
-        """int16 [N, L] (or a list of clips) -> RoomResult(od_probs [N,2], od_argmax [N], si_probs [N,K],
-        si_argmax [N], silent [N] bool, kept_len [N], pcm).  Clip c is gated `passes` times against the
+        """int16 [N, L] (or a list of clips) -> RoomResult(od_probs [N,C] for an OD model of C classes
+        (2 for the deployed one), od_argmax [N], si_probs [N,K], si_argmax [N], silent [N] bool, kept_len [N],
+        pcm).  Clip c is gated `passes` times against the
         noise clip of microphone mic[c] (default: its stream), its silence is removed by its stream's
         detector (stream s owns clips [s * items_per_stream, (s + 1) * items_per_stream)); with fewer than
         4000 samples left it is 'silent' and both argmax are -1.  pcm (return_pcm=True) is the conditioned
@@ -220,6 +221,12 @@ class Room:
             self.si.set_head(fit.w, fit.b, _lib.HEAD_SIGMOID)
         return Registration(speaker_id_dict, accuracy, kept_len, n_windows, fit.history, ft_history)
 
+    def _two_class_od(self, what):
+        """overlap_plan labels two classes (single / overlapped): an OD model with another head cannot be
+        scored or fitted on its mixes"""
+        if self.od.n_classes != 2:
+            raise ValueError(f'{what}: the mix recipe labels two classes, the OD model has K = {self.od.n_classes}')
+
     def overlap_check(self, recordings, mic=None, passes=1, silence_remove=True, n_overlapped=256,
                       n_single=256, seed=1):
         """Does the room's OD model tell overlap from single speech for ITS speakers, through its microphones
@@ -237,6 +244,7 @@ class Room:
 
         from . import _lib
         from .data_augmentation import confusion, overlap_plan
+        self._two_class_od('overlap_check')
         K = len(recordings)
         if K < 2:
             raise ValueError(f'{K} recordings: an overlap check needs at least two speakers')
@@ -278,6 +286,7 @@ class Room:
 
         from . import _lib, overlap_detector, tfbundle
         from .data_augmentation import confusion, overlap_plan
+        self._two_class_od('overlap_adapt')
         K = len(recordings)
         if K < 2:
             raise ValueError(f'{K} recordings: an overlap adaptation needs at least two speakers')
@@ -332,7 +341,9 @@ class Room:
     @staticmethod
     def labels(result, speaker_id_dict):
         """-> (overlap labels, speaker labels) per clip in the reference's strings: 'overlapped' /
-        'non-overlapped' and speaker_id_dict[str(argmax)]; 'silent' where the argmax is -1."""
-        od = [_OD_LABELS[str(int(a))] for a in np.asarray(result.od_argmax)]
+        'non-overlapped' (the class number for an OD model of more than two classes) and
+        speaker_id_dict[str(argmax)]; 'silent' where the argmax is -1."""
+        k = np.shape(result.od_probs)[1]
+        od = [_od_label(a, k) for a in np.asarray(result.od_argmax)]
         si = ['silent' if a < 0 else speaker_id_dict[str(int(a))] for a in np.asarray(result.si_argmax)]
         return od, si

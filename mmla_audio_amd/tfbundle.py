@@ -182,7 +182,9 @@ def layout(shapes):
         k0 = shapes.get('layer_with_weights-0/kernel')
         kind = weights.OD if k0 is not None and len(k0) == 4 else weights.SI
         if kind == weights.OD:
-            items, n_classes, head = weights.od_spec(), 2, _lib.HEAD_SOFTMAX
+            hk = shapes.get('layer_with_weights-41/kernel')
+            n_classes = int(hk[1]) if hk is not None and len(hk) == 2 else 2   # the Dense(K) head
+            items, head = weights.od_spec(n_classes), _lib.HEAD_SOFTMAX
         else:
             head_kernel = shapes.get('layer_with_weights-42/kernel')
             if head_kernel is None or len(head_kernel) != 2:
@@ -315,9 +317,10 @@ def save_overlap(model_dir, W):
     ``load_bundle`` / ``models.load_model`` return every tensor bit for bit.  As with ``save_deployed`` only
     the variables are written, and parity of the key layout with a real TF save is unpinned."""
     from . import weights
-    weights.check(weights.OD, W)
+    k = weights.od_classes(W)      # any K: the head is the last item, so the BiLSTM's indices do not move
+    weights.check(weights.OD, W, k)
     tensors = {}
-    for i, (name, _, role) in enumerate(weights.od_spec()):
+    for i, (name, _, role) in enumerate(weights.od_spec(k)):
         tensors[f'variables/{i}' if role.startswith('lstm_') else name] = W[name]
     _write_bundle(model_dir, tensors)
 

@@ -51,8 +51,14 @@ def _bilstm(k, d):
     return out
 
 
-def od_spec():
-    """[(name, shape, role)] in packed order for OD-NET."""
+OD_MAX_CLASSES = 8   # MMLA_OD_MAX_CLASSES
+
+
+def od_spec(n_classes=2):
+    """[(name, shape, role)] in packed order for OD-NET with a K-way head (its last item; 2: the deployed
+    timit2.0 model, 3: the reference's research models, overlap_detector.py:394)."""
+    if not 2 <= int(n_classes) <= OD_MAX_CLASSES:
+        raise ValueError(f'OD n_classes {n_classes} outside [2, {OD_MAX_CLASSES}]')
     s = _conv(0, (1, 1, 3, 16))
     k = 1
     cin = 16
@@ -65,7 +71,7 @@ def od_spec():
             k += 4
         cin = c
     s += _bilstm(40, 128)
-    s += _conv(41, (512, 2))
+    s += _conv(41, (512, int(n_classes)))
     return s
 
 
@@ -91,7 +97,7 @@ def si_spec(n_classes=630):
 
 def spec(kind, n_classes=None):
     if kind == OD:
-        return od_spec()
+        return od_spec(2 if n_classes is None else n_classes)
     return si_spec(630 if n_classes is None else n_classes)
 
 
@@ -113,6 +119,19 @@ def _orthogonal(rng, shape):
 
 
 SI_HEAD_GAIN = 10.0   # synthetic SI Dense kernel scale: decisive argmax at K = 630 (logit std ~4)
+
+
+def od_classes_of(n_floats):
+    """K of a packed OD blob of n_floats = (the blob below the head) + 513 K; ValueError for any other size."""
+    k, rest = divmod(int(n_floats) - (n_params(OD) - 513 * 2), 513)
+    if rest or not 2 <= k <= OD_MAX_CLASSES:
+        raise ValueError(f'{n_floats} floats is not an OD blob of 2..{OD_MAX_CLASSES} classes')
+    return k
+
+
+def od_classes(W):
+    """K of an OD weight dict: the width of its Dense head."""
+    return int(W['layer_with_weights-41/kernel'].shape[1])
 
 
 def synthetic(kind, seed=0, n_classes=None, head_gain=None):
@@ -195,11 +214,11 @@ def initial(kind, seed=0, n_classes=None):
     return _initial(spec(kind, n_classes), 0x696E6974 + 7919 * int(seed))
 
 
-def initial_od(seed=0):
+def initial_od(seed=0, n_classes=2):
     """The Keras initial state of ``__ResBLSTM`` (overlap_detector.py:362-390), what ``train_model`` starts
-    from: the same initialisers as ``initial`` over ``od_spec()``, with numpy's draws from a stream of its
-    own."""
-    return _initial(od_spec(), 0x696E6F64 + 7919 * int(seed))
+    from: the same initialisers as ``initial`` over ``od_spec(n_classes)``, with numpy's draws from a stream
+    of its own.  The head is the last draw, so every other tensor is the two-class draw bit for bit."""
+    return _initial(od_spec(n_classes), 0x696E6F64 + 7919 * int(seed))
 
 
 def _initial(items, stream):
