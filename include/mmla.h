@@ -48,6 +48,26 @@ enum mmla_head { MMLA_HEAD_SOFTMAX = 0, MMLA_HEAD_SIGMOID = 1 };
 /* the calls that take nr_passes (mmla_condition, mmla_{od,si,room}_pipeline_conditioned,
  * mmla_od_pipeline_gated): the passes run the non-stationary gate of mmla_nr_reduce_ns */
 #define MMLA_NR_NONSTATIONARY 0x2u
+/*
+ * The feature images of the OD detector (overlap_features_generator.py:119-177), all [128,151,3] u8 of the
+ * same normalised log-mel, rows flipped (origin="lower"):
+ *   MMLA_OD_IMG_ZCR     generate_zcr_image: R = trunc(255 zcr), G = B = trunc(255 (1 - norm))
+ *   MMLA_OD_IMG_GRAY    generate_gary_image(cmap="gray"): plt.imsave's pixel LUT_gray[min(trunc(256 norm), 255)],
+ *                       written R = G = B as decode_png(png, 3) reads it (decode_png(png, 1) gives that byte)
+ *   MMLA_OD_IMG_VIRIDIS generate_viridis_image: LUT_viridis[min(trunc(256 norm), 255)]
+ * LUT = matplotlib.colormaps[name](np.arange(256), bytes=True)[:, :3] (matplotlib 3.10.8; the gray table is
+ * not the identity).  No autoscale: the clip's normalised minimum and maximum are 0 and 1.  A NaN pixel
+ * (digital silence) is (0, 0, 0): imsave's RGBA (0, 0, 0, 0).
+ * mmla_od_features, mmla_od_features_f32 (strided and device-pointer calls alike) take the type in two flag
+ * bits, MMLA_OD_IMG_FLAGS(type): none set = ZCR, both set = MMLA_E_INVALID.  The pipelines make the
+ * loaded model's type (mmla_od_set_image_type).
+ */
+#define MMLA_OD_IMG_ZCR 0
+#define MMLA_OD_IMG_GRAY 1
+#define MMLA_OD_IMG_VIRIDIS 2
+#define MMLA_OD_IMG_SHIFT 4
+#define MMLA_OD_IMG_MASK (0x3u << MMLA_OD_IMG_SHIFT)
+#define MMLA_OD_IMG_FLAGS(type) ((uint32_t)(type) << MMLA_OD_IMG_SHIFT)
 
 /* OD front-end geometry (overlap_features_generator.py:39-42,73-81) */
 #define MMLA_OD_MELS 128
@@ -79,6 +99,11 @@ int mmla_crc32c(const void* data, int64_t n, uint32_t* crc);
  * libpng's row reconstruction inside tf.image.decode_png (record_on_pc.py:157,
  * overlap_detection_post_processing.py:205; mmla_audio_amd/tf_compat/image.py). */
 int mmla_png_unfilter(const uint8_t* raw, int64_t h, int64_t row_bytes, int32_t bpp, uint8_t* out);
+
+/* Test hook: the colour map compiled into the front-end for image type MMLA_OD_IMG_GRAY (1) or MMLA_OD_IMG_VIRIDIS (2) (host
+ * only, no context or device): rgb [256][3] u8 = matplotlib.colormaps[name](np.arange(256), bytes=True)[:, :3].
+ * MMLA_E_INVALID for any other type. */
+int mmla_debug_od_image_lut(int32_t type, uint8_t* rgb);
 
 /* Create a context on HIP device `device` (owns a stream, device workspaces and loaded weights). */
 int mmla_create(int device, mmla_ctx** out);
@@ -144,6 +169,9 @@ int mmla_range_check(mmla_ctx* ctx, int64_t* f32_reruns);
  * mmla_od_pipeline_mixed adds per clip the mixed-clip buffer (24000 int16: 48 KB) and 4 bytes of length,
  * and per host-pointer call the pool and the plan (160 bytes per clip), which stay until
  * mmla_release_workspace; a host-pointer mmla_od_mix holds the same (2 x clip_len bytes per clip).
+ * mmla_od_forward / _u8 with a one-channel model (mmla_od_image) widen the caller's [.,1] images into the
+ * three-channel image buffer above; a host-pointer call adds the staged one-channel images per clip (19 KB
+ * u8, 77 KB float).
  */
 int mmla_set_microbatch(mmla_ctx* ctx, int64_t od_clips, int64_t si_clips);
 /* The micro-batch sizes the next call would use. */
@@ -174,6 +202,23 @@ int mmla_load_weights(mmla_ctx* ctx, int model_kind, const float* packed, int64_
                       int32_t n_classes, int32_t head);
 /* *k = the classes of the loaded OD model.  MMLA_E_NOWEIGHTS before an OD model is loaded. */
 int mmla_od_classes(mmla_ctx* ctx, int32_t* k);
+/*
+ * The image type of the loaded OD model (MMLA_OD_IMG_*): what every pipeline entry that runs the front-end
+ * in front of OD-NET produces -- mmla_od_pipeline, _conditioned, _mixed, _capture,
+ * mmla_room_pipeline_conditioned, _capture.  It is a property of the loaded model: mmla_load_weights
+ * resets it to ZCR for a three-channel model (stem [1,1,3,16]) and to GRAY for a one-channel model (stem
+ * [1,1,1,16], OverlapDetector(imagetype='gray'), overlap_detector.py:84-90).  A three-channel model takes
+ * all three types (a gray PNG read with three channels is a legitimate input); a one-channel model only
+ * GRAY, anything else is MMLA_E_INVALID.  MMLA_E_NOWEIGHTS before an OD model is loaded.
+ * mmla_od_image: *type and *channels (both nullable) of the loaded model.
+ * One-channel models: a blob whose stem kernel is [1,1,1,16] is 32 floats shorter than
+ * weights.od_spec(K); 513 K - 32 is no multiple of 513, so mmla_load_weights tells (K, channels) from
+ * n_floats.  mmla_od_forward / _u8 then take [n,128,151,1] (float / u8).  The device keeps 3 bytes per
+ * pixel: the stem is stored with two zero rows and a caller's image is widened to (g, g, g) as it
+ * enters; the fused pipelines need no widening, the front-end writes R = G = B.
+ */
+int mmla_od_set_image_type(mmla_ctx* ctx, int32_t type);
+int mmla_od_image(mmla_ctx* ctx, int32_t* type, int32_t* channels);
 
 /*
  * OverlapDetection front-end, replaces OverlapFeaturesGenerator.generate_mels / generate_zcr /
@@ -183,8 +228,9 @@ int mmla_od_classes(mmla_ctx* ctx, int32_t* k);
  *   norm_db [n,128,151] f32  normalize_matrix(db) in [0,1] (NaN for digital silence) (nullable)
  *   zcr     [n,151]     f32  zero_crossing_rate(frame 400, hop 160)                 (nullable)
  *   img     [n,128,151,3] u8 the decoded PNG the model reads: rows flipped
- *                            (origin="lower"), R = trunc(255*zcr), G = B = trunc(255*(1-norm))
- *                                                                                   (nullable)
+ *                            (origin="lower"), R = trunc(255*zcr), G = B = trunc(255*(1-norm));
+ *                            with MMLA_OD_IMG_FLAGS(type) in flags the gray or viridis image instead
+ *                            (MMLA_OD_IMG_* above)                                  (nullable)
  */
 int mmla_od_features(mmla_ctx* ctx, const int16_t* pcm, int64_t n_clips, int64_t clip_stride,
                      const int32_t* lens, int32_t clip_len, float* db, float* norm_db, float* zcr,
@@ -239,10 +285,12 @@ int mmla_si_features_seq_batch(mmla_ctx* ctx, const int16_t* pcm, int64_t n_sign
                                const int32_t* lens, int32_t clip_len, float* feat, int32_t* n_windows,
                                uint32_t flags);
 
-/* OD-NET predict on float NHWC [n,128,151,3] (values 0..255) -> probs [n,K], K = mmla_od_classes
- * (model.predict, record_on_pc.py:159). */
+/* OD-NET predict on float NHWC [n,128,151,C] (values 0..255; C = the loaded model's channels,
+ * mmla_od_image: 3, or 1 for a one-channel model) -> probs [n,K], K = mmla_od_classes (model.predict,
+ * record_on_pc.py:159). */
 int mmla_od_forward(mmla_ctx* ctx, const float* x_nhwc, int64_t n, float* probs, uint32_t flags);
-/* Same on the uint8 image produced by mmla_od_features. */
+/* Same on the uint8 image produced by mmla_od_features: [n,128,151,C]; a one-channel model reads channel 0
+ * of the MMLA_OD_IMG_GRAY image. */
 int mmla_od_forward_u8(mmla_ctx* ctx, const uint8_t* img, int64_t n, float* probs, uint32_t flags);
 
 /* SI-NET predict on [n,256,39] -> probs [n,K] (SI record_on_pc.py:136;
@@ -415,7 +463,10 @@ int mmla_si_base_train(mmla_ctx* ctx, const float* packed, int64_t n_floats, int
  * trained detector fitted further on labelled feature images.  Float32 HIP (od_bwd.hip, with conv.hip's
  * exact-f32 MFMA convolution and si_bwd.hip's BiLSTM), stated from the script and Keras 2.6's published
  * source; TensorFlow is not available here: parity with TF itself is unpinned.
- *   graph     OD-NET (oracle/nets_torch.Nets.od_forward): img_u8 [n, h, w, 3] PNG values taken as float;
+ *   graph     OD-NET (oracle/nets_torch.Nets.od_forward): img_u8 [n, h, w, C] PNG values taken as float, C
+ *             the channels of the blob's stem kernel [1,1,C,16]: 3, or 1 for a blob 32 floats shorter (the
+ *             network of OverlapDetector(imagetype='gray'); n_floats tells (K, C), the gradient and every
+ *             blob going out have the blob's own layout: 16 stem-kernel entries for C = 1);
  *             stem Conv2D 1x1; nine res blocks BN - ELU - Conv 3x3 - BN - ELU - Conv (4,1) with pool =
  *             (T,F,F,T,F,F,T,F,F): a pool block adds MaxPool2D(2,'same') of the main path to a 1x1
  *             stride-2 shortcut.  Conv 'same': the (4,1) kernel pads 1 above, 2 below; the pool pads odd
@@ -595,6 +646,8 @@ int mmla_ssim_u8(mmla_ctx* ctx, const uint8_t* a, const uint8_t* b, int64_t n, i
  *   probs[c] = OD-NET on image B;  argmax[c] = -1 where silent.
  * nr_passes = 0: B = A, ssim = 1, the results of mmla_od_pipeline, no noise profile needed.
  * MMLA_E_INVALID: nr_passes < 0, or nr_passes > 0 before mmla_nr_set_noise.  ssim [n] f32 is nullable.
+ * The gate's SSIM is defined on the ZCR images (record_on_pi.py:117-120): with a loaded model whose image
+ * type (mmla_od_set_image_type) is not MMLA_OD_IMG_ZCR this call is MMLA_E_INVALID.
  * Micro-batched as mmla_od_pipeline (mmla_set_microbatch lists the extra workspace).  The gate runs at
  * most 512 clips per launch with a stream synchronisation between launches and between passes, so with
  * MMLA_DEVICE_PTR and nr_passes > 0 this call synchronises the context stream internally (its last
@@ -964,7 +1017,7 @@ enum mmla_stage {
 };
 int mmla_profile_enable(mmla_ctx* ctx, int on);
 
-/* Layer-wise parity tap (tests): run OD-NET on host float NHWC x[n,128,151,3] up to `stage`
+/* Layer-wise parity tap (tests): run OD-NET on host float NHWC x[n,128,151,C] (the model's C) up to `stage`
  * (0 = stem conv, 1..9 = after res_block 1..9 in NHWC, 10 = mean over H [n,19,128],
  * 11 = BiLSTM output [n,512]) and copy that tensor to host `out` (capacity out_floats).
  * Unguarded: it shows what the selected arithmetic computes.  Env MMLA_DEBUG_TRACE_GUARD=1 at

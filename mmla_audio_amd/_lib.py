@@ -23,6 +23,27 @@ MMLA_CAPTURE_FRESH = 0x4
 MMLA_CAPTURE_MEAN = -1
 MODEL_OD, MODEL_SI = 0, 1
 HEAD_SOFTMAX, HEAD_SIGMOID = 0, 1
+# the OD feature images (mmla.h MMLA_OD_IMG_*); a feature call takes the type in two flag bits
+OD_IMG_ZCR, OD_IMG_GRAY, OD_IMG_VIRIDIS = 0, 1, 2
+OD_IMAGE_TYPES = {'zcr': OD_IMG_ZCR, 'gray': OD_IMG_GRAY, 'viridis': OD_IMG_VIRIDIS}
+_OD_IMG_SHIFT = 4
+
+
+def od_image_type(t):
+    """'zcr' / 'gray' / 'viridis' (or the OD_IMG_* integer, or None = ZCR) -> the OD_IMG_* integer"""
+    if t is None:
+        return OD_IMG_ZCR
+    if isinstance(t, str):
+        if t not in OD_IMAGE_TYPES:
+            raise ValueError(f'image type {t!r}: expected one of {sorted(OD_IMAGE_TYPES)}')
+        return OD_IMAGE_TYPES[t]
+    if int(t) not in OD_IMAGE_TYPES.values():
+        raise ValueError(f'image type {t!r}: expected one of {sorted(OD_IMAGE_TYPES)}')
+    return int(t)
+
+
+def _img_flags(t):
+    return od_image_type(t) << _OD_IMG_SHIFT
 PREC_F32, PREC_F16X3 = 0, 1
 
 OD_MELS, OD_FRAMES, OD_CLIP = 128, 151, 24000
@@ -83,6 +104,7 @@ SIGNATURES = {
     'mmla_abi_version': [],
     'mmla_crc32c': [_P, _I64, ctypes.POINTER(_U32)],
     'mmla_png_unfilter': [_P, _I64, _I64, _I32, _P],
+    'mmla_debug_od_image_lut': [_I32, _P],
     'mmla_create': [ctypes.c_int, ctypes.POINTER(_P)],
     'mmla_destroy': [_P],
     'mmla_set_stream': [_P, _P],
@@ -130,6 +152,8 @@ SIGNATURES = {
     # ctx, probs, labels, n, n_classes, auc_out
     'mmla_od_auc_k': [_P, _P, _P, _I64, _I32, _P, _U32],
     'mmla_od_classes': [_P, _P],
+    'mmla_od_set_image_type': [_P, _I32],
+    'mmla_od_image': [_P, _P, _P],
     # ctx, drop_seed, epoch, sample_ids, n, mask
     'mmla_od_drop_mask': [_P, _I64, _I32, _P, _I64, _P, _U32],
     # ctx, packed, n_floats, img_u8, labels, n_train, val_img, val_labels, n_val, h, w, class_w, epochs, batch,
@@ -220,6 +244,16 @@ def png_unfilter(raw, h, row_bytes, bpp):
     return out
 
 
+def od_image_lut(image_type):
+    """The colour map of the 'gray' or 'viridis' feature image as the library holds it (mmla_debug_od_image_lut; host
+    only, no device needed) -> uint8 [256, 3]."""
+    out = np.empty((256, 3), np.uint8)
+    rc = load_library().mmla_debug_od_image_lut(od_image_type(image_type), out.ctypes.data)
+    if rc != MMLA_OK:
+        raise ValueError(f'image type {image_type!r} has no colour map')
+    return out
+
+
 class MixPlan(namedtuple('MixPlan', 'n_layers src_off src_len pos')):
     """The descriptors of a batch of layered mixes over one pool (mmla_od_mix): n_layers int32 [n] in
     1..MIX_MAX_LAYERS; src_off int64, src_len int32, pos int32, each [n, MIX_MAX_LAYERS].  Layer 0 of a clip
@@ -295,6 +329,8 @@ class Context:
         self.h = h
         self.device = device
         self.od_classes = None
+        self.od_channels = None      # channels of the loaded OD model's stem: 3, or 1 (imagetype='gray')
+        self.od_image_type = None    # OD_IMG_* its pipelines make (od_set_image_type)
         self.si_classes = None
 
     def close(self):
@@ -368,6 +404,9 @@ class Context:
         """OD-NET intermediate tensor after `stage` (see mmla.h) for float NHWC input x."""
         x = np.ascontiguousarray(x, dtype=np.float32)
         n = x.shape[0]
+        ch = self.od_channels or 3
+        if x.shape[1:] != (OD_MELS, OD_FRAMES, ch):
+            raise ValueError(f'debug_od_trace: images {x.shape}, the loaded model reads [n,{OD_MELS},{OD_FRAMES},{ch}]')
         shapes = {0: (128, 151, 16), 10: (19, 128), 11: (512,)}
         hw = [(64, 76, 32), (64, 76, 32), (64, 76, 32), (32, 38, 64), (32, 38, 64), (32, 38, 64),
               (16, 19, 128), (16, 19, 128), (16, 19, 128)]
@@ -396,6 +435,9 @@ class Context:
                                                int(n_classes), int(head)), 'mmla_load_weights')
         if kind == MODEL_OD:
             self.od_classes = int(n_classes)
+            t, ch = ctypes.c_int32(), ctypes.c_int32()
+            self._check(self.lib.mmla_od_image(self.h, ctypes.byref(t), ctypes.byref(ch)), 'mmla_od_image')
+            self.od_image_type, self.od_channels = int(t.value), int(ch.value)   # the type resets on load
         else:
             self.si_classes = int(n_classes)
 
@@ -624,10 +666,18 @@ class Context:
         ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
         return a, ln, a.shape[1]
 
-    def od_features(self, pcm, lens=None, db=True, norm=True, zcr=True, img=True):
+    def od_set_image_type(self, image_type):
+        """The image the pipelines make in front of the loaded OD model: 'zcr', 'gray' or 'viridis' (or
+        OD_IMG_*).  A one-channel model takes 'gray' only; loading a model resets the type."""
+        t = od_image_type(image_type)
+        self._check(self.lib.mmla_od_set_image_type(self.h, t), 'mmla_od_set_image_type')
+        self.od_image_type = t
+
+    def od_features(self, pcm, lens=None, db=True, norm=True, zcr=True, img=True, image_type=None):
         """int16 PCM [n, L] (or a list of 1-D int16 arrays) -> dict of features.  Float audio
         (librosa.load scale, any floating dtype or a list of float arrays) goes through
-        mmla_od_features_f32 instead."""
+        mmla_od_features_f32 instead.  image_type: 'zcr' (default), 'gray' or 'viridis' -- img is
+        [n,128,151,3] for all three (gray as R = G = B)."""
         fl = self._float_pcm(pcm, lens)
         if fl is not None:
             a, ln, L = fl
@@ -645,7 +695,7 @@ class Context:
             bufs[key] = np.empty(shape, dt) if want else None
         self._check(fn(
             self.h, _ptr(a), n, a.shape[1], _ptr(ln), L, _ptr(bufs['db']), _ptr(bufs['norm']),
-            _ptr(bufs['zcr']), _ptr(bufs['img']), 0), 'mmla_od_features')
+            _ptr(bufs['zcr']), _ptr(bufs['img']), _img_flags(image_type)), 'mmla_od_features')
         for k, v in bufs.items():
             if v is not None:
                 out[k] = v
@@ -720,9 +770,14 @@ class Context:
         return self.od_classes or 2
 
     def od_forward(self, x):
-        """-> probs [n,K], K = od_classes"""
+        """x [n,128,151,C], C = od_channels of the loaded model (uint8, or float 0..255) -> probs [n,K],
+        K = od_classes"""
         x = np.ascontiguousarray(x)
         n = x.shape[0]
+        ch = self.od_channels or 3
+        # the library reads n * 128 * 151 * C values: an array of another shape never reaches it
+        if x.ndim != 4 or x.shape[1:] != (OD_MELS, OD_FRAMES, ch):
+            raise ValueError(f'od_forward: images {x.shape}, the loaded model reads [n,{OD_MELS},{OD_FRAMES},{ch}]')
         probs = np.empty((n, self._od_k()), np.float32)
         if x.dtype == np.uint8:
             rc = self.lib.mmla_od_forward_u8(self.h, _ptr(x), n, _ptr(probs), 0)
@@ -898,26 +953,34 @@ class Context:
     def _od_images(img, labels, what):
         img = np.ascontiguousarray(img, dtype=np.uint8)
         labels = np.ascontiguousarray(labels, dtype=np.int32)
-        if img.ndim != 4 or img.shape[3] != 3 or labels.shape != (img.shape[0],):
-            raise ValueError(f'{what} {img.shape} / labels {labels.shape}: expected [n,h,w,3] and [n]')
+        if img.ndim != 4 or img.shape[3] not in weights.OD_CHANNELS or labels.shape != (img.shape[0],):
+            raise ValueError(f'{what} {img.shape} / labels {labels.shape}: expected [n,h,w,C] (C = 3 or 1) and [n]')
         return img, labels
+
+    @staticmethod
+    def _od_blob_channels(packed, img):
+        """the images' channels must be the blob's (weights.od_layout_of): the library reads h w C bytes per image"""
+        ch = weights.od_layout_of(packed.size)[1]
+        if img.shape[3] != ch:
+            raise ValueError(f'img {img.shape}: the blob of {packed.size} floats has a {ch}-channel stem')
 
     @staticmethod
     def _od_class_w(class_w, n_floats):
         """class_w as float32 [K], K read from the blob's size (None: ones)"""
-        k = weights.od_classes_of(n_floats)
+        k = weights.od_layout_of(n_floats)[0]
         if class_w is None:
             return np.ones(k, np.float32)
         return np.ascontiguousarray(class_w, dtype=np.float32).reshape(k)
 
     def od_loss_grad(self, packed, img, labels, class_w=None, drop_mask=None, moving=False):
         """The training-mode loss of ONE batch of OD feature images and its gradient (mmla_od_loss_grad):
-        packed = the OD blob of weights.pack (any K), img uint8 [n,h,w,3], labels [n] in [0,K), class_w [K]
+        packed = the OD blob of weights.pack (any K; C = 3 or 1 channels), img uint8 [n,h,w,C], labels [n] in [0,K), class_w [K]
         (None: ones), drop_mask uint8
         [n,512] (None: every unit kept) -> (loss float32 [1], grad float32 [n_floats] in the packed order, 0
         in the moving statistics[, the blob with only the moving statistics advanced one step])."""
         packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
         img, labels = self._od_images(img, labels, 'img')
+        self._od_blob_channels(packed, img)
         n, h, w = img.shape[:3]
         cw = self._od_class_w(class_w, packed.size)
         if drop_mask is not None:
@@ -935,13 +998,15 @@ class Context:
     def od_finetune(self, packed, img, labels, val_img, val_labels, class_w, lr, perm, drop_mask, epochs,
                     batch=16, patience=0):
         """OverlapDetector.continue_train_model on the device (mmla_od_finetune): Adadelta through the whole
-        OD network from the blob `packed`, BatchNorm on batch statistics.  img uint8 [n,h,w,3], labels [n];
+        OD network from the blob `packed`, BatchNorm on batch statistics.  img uint8 [n,h,w,C] with the blob's C
+        (3, or 1 for a one-channel stem; the blob coming out has the same layout), labels [n];
         val_* likewise (None or empty: no validation set); lr [epochs]; perm [epochs,n] the sample order
         of every epoch; drop_mask uint8 [epochs,n,512] indexed by sample (None: every unit kept).
         -> (packed_out float32 [n_floats], history [epochs,5] = loss, acc, val_loss, val_acc, lr (NaN rows
         after an early stop), epochs_run)."""
         packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
         img, labels = self._od_images(img, labels, 'img')
+        self._od_blob_channels(packed, img)
         n, h, w = img.shape[:3]
         epochs, perm, vi, vl, nv, opt = self._fit_args(perm, epochs, n, val_img, val_labels, self._od_images, 'val_img',
                                                         trim=True)
@@ -954,7 +1019,7 @@ class Context:
             if drop_mask.shape != (epochs, n, OD_DROP_UNITS):
                 raise ValueError(f'drop_mask {drop_mask.shape}: expected [{epochs},{n},{OD_DROP_UNITS}]')
         if nv and vi.shape[1:] != img.shape[1:]:
-            raise ValueError(f'val_img {vi.shape}: expected [n,{h},{w},3]')
+            raise ValueError(f'val_img {vi.shape}: expected [n,{h},{w},{img.shape[3]}]')
         out = np.empty_like(packed)
         hist = np.empty((epochs, 5), np.float32)
         ran = np.zeros(1, np.int32)
@@ -972,6 +1037,7 @@ class Context:
         val_loss, val_acc, lr, auc, val_auc (NaN rows after an early stop), epochs_run, best_epoch or -1)."""
         packed = np.ascontiguousarray(packed, dtype=np.float32).ravel()
         img, labels = self._od_images(img, labels, 'img')
+        self._od_blob_channels(packed, img)
         n, h, w = img.shape[:3]
         epochs, perm, vi, vl, nv, opt = self._fit_args(perm, epochs, n, val_img, val_labels, self._od_images, 'val_img',
                                                         trim=True)
@@ -980,7 +1046,7 @@ class Context:
         if lr.shape != (epochs,):
             raise ValueError(f'lr {lr.shape}: expected [{epochs}]')
         if nv and vi.shape[1:] != img.shape[1:]:
-            raise ValueError(f'val_img {vi.shape}: expected [n,{h},{w},3]')
+            raise ValueError(f'val_img {vi.shape}: expected [n,{h},{w},{img.shape[3]}]')
         out = np.empty_like(packed)
         best = np.empty_like(packed)
         hist = np.empty((epochs, 7), np.float32)
@@ -1337,7 +1403,8 @@ class Context:
                                               _ptr(probs), _ptr(am), None, 0), 'mmla_od_pipeline')
         return probs, am
 
-    def od_features_strided(self, signal, n, stride, clip_len, db=True, norm=True, zcr=True, img=True):
+    def od_features_strided(self, signal, n, stride, clip_len, db=True, norm=True, zcr=True, img=True,
+                            image_type=None):
         """OD features of n windows of one long signal: window c = signal[c*stride : c*stride +
         clip_len] (int16 -> mmla_od_features, float -> mmla_od_features_f32; no host copies)"""
         fl = np.issubdtype(np.asarray(signal).dtype, np.floating)
@@ -1352,7 +1419,7 @@ class Context:
             bufs[key] = np.empty(shape, dt) if want else None
         fn = self.lib.mmla_od_features_f32 if fl else self.lib.mmla_od_features
         self._check(fn(self.h, _ptr(sig), n, stride, None, clip_len, _ptr(bufs['db']),
-                       _ptr(bufs['norm']), _ptr(bufs['zcr']), _ptr(bufs['img']), 0),
+                       _ptr(bufs['norm']), _ptr(bufs['zcr']), _ptr(bufs['img']), _img_flags(image_type)),
                     'mmla_od_features(strided)')
         return {k: v for k, v in bufs.items() if v is not None}
 
@@ -1368,10 +1435,10 @@ class Context:
         return probs, am, silent.astype(bool)
 
     # -- device-pointer API (asynchronous on the context stream) -------------------------------
-    def od_features_dev(self, pcm, n, stride, clip_len, db=0, norm=0, zcr=0, img=0, lens=0):
+    def od_features_dev(self, pcm, n, stride, clip_len, db=0, norm=0, zcr=0, img=0, lens=0, image_type=None):
         self._check(self.lib.mmla_od_features(self.h, pcm, n, stride, lens or None, clip_len,
                                               db or None, norm or None, zcr or None, img or None,
-                                              MMLA_DEVICE_PTR), 'mmla_od_features(dev)')
+                                              MMLA_DEVICE_PTR | _img_flags(image_type)), 'mmla_od_features(dev)')
 
     def si_features_dev(self, pcm, n, stride, clip_len, feat, silent=0, lens=0):
         self._check(self.lib.mmla_si_features(self.h, pcm, n, stride, lens or None, clip_len, feat,

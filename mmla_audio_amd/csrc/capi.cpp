@@ -49,6 +49,14 @@ int mmla_crc32c(const void* data, int64_t n, uint32_t* crc) {
   return MMLA_OK;
 }
 
+int mmla_debug_od_image_lut(int32_t type, uint8_t* rgb) {
+  const uint32_t* lut = od_fe_lut(type);
+  if (!lut || !rgb) return MMLA_E_INVALID;
+  for (int i = 0; i < 256; ++i)
+    for (int ch = 0; ch < 3; ++ch) rgb[3 * i + ch] = (uint8_t)(lut[i] >> (8 * ch));
+  return MMLA_OK;
+}
+
 int mmla_png_unfilter(const uint8_t* raw, int64_t h, int64_t row_bytes, int32_t bpp, uint8_t* out) {
   if (h < 0 || row_bytes < 0 || bpp < 1 || bpp > 8 || ((!raw || !out) && h * row_bytes > 0))
     return MMLA_E_INVALID;

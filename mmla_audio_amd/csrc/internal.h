@@ -52,7 +52,9 @@ constexpr int64_t od_body_floats() {
   }
   return n + 2 * ((128 + 256) * 1024 + 1024);
 }
-constexpr int64_t od_blob_floats(int k) { return od_body_floats() + 513 * (int64_t)k; }
+constexpr int64_t od_blob_floats(int k, int channels = 3) {
+  return od_body_floats() + 513 * (int64_t)k - (channels == 1 ? 32 : 0);   // stem kernel [1,1,C,16]
+}
 static_assert(od_blob_floats(2) == 1548706, "the two-class OD blob");
 
 struct ConvW {
@@ -91,6 +93,9 @@ struct OdNet {
   float* head_w = nullptr;   // Dense [512, k]
   float* head_b = nullptr;
   int k = 2;                 // classes of the loaded head, 2 .. MMLA_OD_MAX_CLASSES
+  // channels of the blob's stem kernel [1,1,C,16], 3 or 1.  The device-side image has 3 bytes per pixel
+  // either way: a one-channel stem is stored as rows {w, 0, 0} and reads the pixel (g, g, g)
+  int channels = 3;
 };
 struct SiNet {
   ConvW stem;
@@ -141,6 +146,9 @@ struct mmla_ctx {
   OdFeTables* od_tables = nullptr;
   SiFeTables* si_tables = nullptr;
   bool od_loaded = false, si_loaded = false;
+  // the image the front-end makes in front of OD-NET (MMLA_OD_IMG_*): a property of the loaded OD model,
+  // reset by mmla_load_weights, changed by mmla_od_set_image_type
+  int od_img_type = MMLA_OD_IMG_ZCR;
   mmla::OdNet od;
   mmla::SiNet si;
   std::vector<void*> od_allocs, si_allocs;
@@ -290,6 +298,7 @@ enum Slot {
   // then the call's staged host-pointer operands; carved anew by every call (carve_slot)
   S_FT,
   S_MIX, S_MIX_LEN,  // mmla_od_mix / mmla_od_pipeline_mixed: a micro-batch's mixed clips and their lengths
+  S_WIDE,  // a one-channel OD model's staged [.,1] images, before od_widen_launch widens them
   S_ODFT,  // mmla_od_loss_grad / mmla_od_finetune / mmla_od_train: likewise for the OD blob; the staged
            // operands of mmla_od_drop_mask, mmla_od_auc and mmla_od_augment
   // kept slots: a call fills them once, in front of its micro-batches, so they outlive the ws_release

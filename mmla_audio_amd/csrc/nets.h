@@ -7,6 +7,9 @@
 hipError_t od_stem_launch(const uint8_t* img_u8, const float* img_f32, int64_t n_pix, int ldw,
                           const float* w /*[3][16]*/, const float* b /*[16]*/, float* y,
                           hipStream_t s);
+// A one-channel model's image as the network reads it: g [n_pix] -> y [n_pix][3] = (g, g, g), what
+// decode_png(gray png, 3) gives (the loaded stem's rows 1 and 2 are zero).  Exactly one of g_u8 / g_f32.
+hipError_t od_widen_launch(const uint8_t* g_u8, const float* g_f32, int64_t n_pix, void* y, hipStream_t s);
 // Lambda(K.mean(x, axis=1)): [n, h, w, c] -> [n, w, c]
 hipError_t mean_h_launch(const float* x, int n, int h, int w, int c, float* y, hipStream_t s);
 // MaxPool1D(2, 'same') on [n, t, c] -> [n, ceil(t/2), c]

@@ -20,7 +20,14 @@ struct OdFeTables {
   int mel_unit[16];         // wave -> 2 bt + frame half; per SIMD (waves w, w + 4, w + 8, w + 12) balanced
   float mel_a[64][64];      // A fragments [frag][lane]: A[m = l & 15][k = l >> 4] = mel_w[16 bt + m][bin0 + 4 j + k] x 2^-38
   uint16_t zero16;          // a zero sample: the target of reads past a clip's length
+  // the gray and viridis images' colour maps (od_fe_lut.h), [OD_IMG_GRAY - 1, OD_IMG_VIRIDIS - 1]: entry
+  // idx < 256 = R | G << 8 | B << 16, entry 256 = 0 (a NaN pixel: imsave's transparent black)
+  uint32_t lut[2][257];
 };
+
+// the image the front-end writes (MMLA_OD_IMG_*): the ZCR-enhanced RGB image, or the normalised log-mel
+// through matplotlib's gray / viridis colour map
+enum OdImgType { OD_IMG_ZCR = 0, OD_IMG_GRAY = 1, OD_IMG_VIRIDIS = 2 };
 
 struct OdFeArgs {
   const int16_t* pcm;
@@ -28,6 +35,8 @@ struct OdFeArgs {
   int64_t clip_stride;
   const int32_t* lens;      // nullable
   int32_t clip_len;
+  int32_t img_type;         // OdImgType of img (read by the launch; in the padding the struct always had,
+                            // so the kernels' argument block keeps its size and offsets)
   const OdFeTables* tables; // device copy
   float* db;                // [n,128,151] nullable
   float* norm;              // [n,128,151] nullable
@@ -38,5 +47,7 @@ struct OdFeArgs {
 };
 
 void od_fe_build_tables(OdFeTables* t);
+// the 256 packed entries of a colour map (type OD_IMG_GRAY or OD_IMG_VIRIDIS), null for any other type
+const uint32_t* od_fe_lut(int type);
 bool od_fe_tables_ok(const OdFeTables& t);   // the mel schedule fits the kernel's LDS rows and fragments
 hipError_t od_fe_launch(const OdFeArgs& a, int64_t n_clips, hipStream_t stream);

@@ -25,6 +25,7 @@
 // that the reference does in float64 (ref dB, image quantisation) are done in float64 here.
 #include "common.h"
 #include "od_fe.h"
+#include "od_fe_lut.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -215,7 +216,8 @@ __device__ unsigned long long fe_trace_buf[256 * 16 * 5 * 8];
 #define FE_T(i) do { } while (0)
 #define FE_TFLUSH(t) do { } while (0)
 #endif
-template <bool DB, bool NM, bool IMG>
+// TY (OdImgType) picks the image's epilogue; without an image it stays OD_IMG_ZCR
+template <bool DB, bool NM, bool IMG, int TY = OD_IMG_ZCR>
 __global__ void __launch_bounds__(NTH, 1) od_fe3_kernel(OdFeArgs a, int64_t n_clips) {
   __shared__ __attribute__((aligned(16))) Smem sm;
   const OdFeTables& tb = *a.tables;
@@ -649,7 +651,7 @@ __global__ void __launch_bounds__(NTH, 1) od_fe3_kernel(OdFeArgs a, int64_t n_cl
     for (int t = 0; t < NTILE; ++t) {
       if (TF * t + TF > NF && TF * t + fr >= NF) continue;
       uint32_t rr = 0;
-      if (IMG) rr = (uint32_t)(int)(((double)sm.zc[par][TF * t + fr] / 400.0) * 255.0) & 255u;
+      if (IMG && TY == OD_IMG_ZCR) rr = (uint32_t)(int)(((double)sm.zc[par][TF * t + fr] / 400.0) * 255.0) & 255u;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float d = fmaxf(fmaf(dbv[t][i], DB_PER_LOG2, nref), thr);
@@ -660,13 +662,24 @@ __global__ void __launch_bounds__(NTH, 1) od_fe3_kernel(OdFeArgs a, int64_t n_cl
         const int so = sf + (i * NF + TF * t) * 4;
         if (NM) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, nv), rn, vf, so, 0);
         if (DB) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, d), rd, vf, so, 0);
-        if (IMG) {
+        if constexpr (IMG && TY == OD_IMG_ZCR) {
           const double v = (1.0 - (double)nv) * 255.0;
           const uint32_t gb = (v >= 0.0) ? ((uint32_t)(int)v & 255u) : 0u;
           const int soi = si + ((3 - i) * NF + TF * t) * 3;
           __builtin_amdgcn_raw_buffer_store_b8((uint8_t)rr, ri, vi, soi, 0);
           __builtin_amdgcn_raw_buffer_store_b8((uint8_t)gb, ri, vi + 1, soi, 0);
           __builtin_amdgcn_raw_buffer_store_b8((uint8_t)gb, ri, vi + 2, soi, 0);
+        } else if constexpr (IMG) {
+          // plt.imsave(norm, cmap=...): entry trunc(256 nv) of the colour map (the product is exact in
+          // float32; 256, from nv >= 1, is entry 255; no autoscale: the clip's own min / max are 0 / 1),
+          // NaN -> entry 256 = 0.  One packed RGB dword per pixel, from the tables through the cache
+          const float s256 = nv * 256.0f;
+          const int idx = s256 == s256 ? (int)fminf(fmaxf(s256, 0.0f), 255.0f) : 256;
+          const uint32_t px = tb.lut[TY - 1][idx];
+          const int soi = si + ((3 - i) * NF + TF * t) * 3;
+          __builtin_amdgcn_raw_buffer_store_b8((uint8_t)px, ri, vi, soi, 0);
+          __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(px >> 8), ri, vi + 1, soi, 0);
+          __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(px >> 16), ri, vi + 2, soi, 0);
         }
       }
     }
@@ -803,6 +816,21 @@ static void launch_v3(const OdFeArgs& a, int64_t n, hipStream_t s) {
   }();
   const dim3 g((unsigned)std::min<int64_t>(n, n_cu)), b(v3::NTH);
   const int k = (a.db ? 4 : 0) | (a.norm ? 2 : 0) | (a.img ? 1 : 0);
+  if (a.img && a.img_type != OD_IMG_ZCR) {   // the colour-map images (od_fe_launch checked the type)
+#define FE3_TY(D, N)                                                                                        \
+  do {                                                                                                      \
+    if (a.img_type == OD_IMG_GRAY) hipLaunchKernelGGL((v3::od_fe3_kernel<D, N, true, OD_IMG_GRAY>), g, b, 0, s, a, n); \
+    else hipLaunchKernelGGL((v3::od_fe3_kernel<D, N, true, OD_IMG_VIRIDIS>), g, b, 0, s, a, n);             \
+  } while (0)
+    switch (k >> 1) {
+      case 0: FE3_TY(false, false); break;
+      case 1: FE3_TY(false, true); break;
+      case 2: FE3_TY(true, false); break;
+      default: FE3_TY(true, true); break;
+    }
+#undef FE3_TY
+    return;
+  }
   switch (k) {
     case 0: hipLaunchKernelGGL((v3::od_fe3_kernel<false, false, false>), g, b, 0, s, a, n); break;
     case 1: hipLaunchKernelGGL((v3::od_fe3_kernel<false, false, true>), g, b, 0, s, a, n); break;
@@ -816,9 +844,14 @@ static void launch_v3(const OdFeArgs& a, int64_t n, hipStream_t s) {
 }
 
 hipError_t od_fe_launch(const OdFeArgs& a, int64_t n_clips, hipStream_t stream) {
+  if (a.img_type < OD_IMG_ZCR || a.img_type > OD_IMG_VIRIDIS) return hipErrorInvalidValue;
   if (n_clips <= 0) return hipSuccess;
   launch_v3(a, n_clips, stream);
   return hipGetLastError();
+}
+
+const uint32_t* od_fe_lut(int type) {
+  return type == OD_IMG_GRAY ? kOdLutGray : type == OD_IMG_VIRIDIS ? kOdLutViridis : nullptr;
 }
 
 void od_fe_build_tables(OdFeTables* t) {
@@ -844,6 +877,10 @@ void od_fe_build_tables(OdFeTables* t) {
     mel_f[i] = mel_to_hz(m);
   }
   t->zero16 = 0;
+  for (int i = 0; i < 257; ++i) {
+    t->lut[OD_IMG_GRAY - 1][i] = i < 256 ? od_fe_lut(OD_IMG_GRAY)[i] : 0u;
+    t->lut[OD_IMG_VIRIDIS - 1][i] = i < 256 ? od_fe_lut(OD_IMG_VIRIDIS)[i] : 0u;
+  }
   for (int m = 0; m < NMEL; ++m) {
     int st = -1, cnt = 0;
     float w[16] = {0};

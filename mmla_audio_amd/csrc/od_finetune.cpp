@@ -25,7 +25,7 @@ namespace {
 constexpr int kMinH = 8, kMaxH = OD_H, kMinW = 8, kMaxW = OD_W;
 constexpr int C = ODB_MAX_C;
 
-// offsets (in floats) of the tensors of weights.od_spec(K) in the packed blob
+// offsets (in floats) of the tensors of weights.od_spec(K, channels) in the packed blob
 struct BlkOff {
   size_t bn_in, ca_w, ca_b, bn_mid, cb_w, cb_b, sc_w, sc_b;
   int cin, cout;
@@ -37,7 +37,7 @@ struct OdOff {
   size_t lk[2], lr[2], lb[2], dw, db, total;
 };
 
-OdOff od_offsets(int K) {
+OdOff od_offsets(int K, int ch) {
   OdOff o{};
   size_t at = 0;
   auto take = [&](size_t n) {
@@ -45,7 +45,7 @@ OdOff od_offsets(int K) {
     at += n;
     return r;
   };
-  o.stem_w = take(3 * 16);
+  o.stem_w = take((size_t)ch * 16);   // [1,1,ch,16]: the blob's own rows, none for a channel it lacks
   o.stem_b = take(16);
   int cin = 16;
   for (int i = 0; i < 9; ++i) {
@@ -88,6 +88,7 @@ struct Engine {
   OdOff off;
   int cap = 0, h = 0, w = 0, T = 0, hl = 0;   // hl x T: the last block's output
   int K = 2;   // classes of the blob's head
+  int ch = 3;  // channels of the blob's stem and of the images: 3, or 1 (imagetype='gray')
   float cw[ODB_MAX_K] = {1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f};
   float *W = nullptr, *G = nullptr, *acc_g = nullptr, *acc_d = nullptr, *wt = nullptr, *stem_w = nullptr,
         *stem_b = nullptr, *zero = nullptr, *part = nullptr, *stat_all = nullptr;
@@ -152,7 +153,7 @@ void carve(Engine& e, Carver& cv, bool train) {
   e.mb = cv.take<uint8_t>(B * ODB_HEAD_D);
   e.net0 = cv.take<float>(B * pix * 16);
   size_t part = (size_t)ODB_RED_SLABS * 2 * C;
-  part = std::max(part, odb_wgrad_part_floats(geom((int)B, e.h, e.w, 3, 16, 1, 1, 1)));
+  part = std::max(part, odb_wgrad_part_floats(geom((int)B, e.h, e.w, e.ch, 16, 1, 1, 1)));
   for (int i = 0; i < 9; ++i) {
     const BlkOff& u = e.off.u[i];
     BlkAct& a = e.ba[i];
@@ -270,9 +271,9 @@ OdbHead head_args(const Engine& e, int B, const uint8_t* mask, float* dz, double
 int forward(Engine& e, int B, bool train, double* acc) {
   hipStream_t s = e.c->stream;
   const float* W = e.W;
-  RUN(odb_pad_cols(W + e.off.stem_w, 3, 16, 32, e.stem_w, s));
+  RUN(odb_pad_cols(W + e.off.stem_w, e.ch, 16, 32, e.stem_w, s));
   RUN(odb_pad_cols(W + e.off.stem_b, 1, 16, 32, e.stem_b, s));
-  RUN(conv_fwd(geom(B, e.h, e.w, 3, 16, 1, 1, 1), e.xb, e.stem_w, e.stem_b, 32, nullptr, EPI_BIAS, nullptr, 0, 0,
+  RUN(conv_fwd(geom(B, e.h, e.w, e.ch, 16, 1, 1, 1), e.xb, e.stem_w, e.stem_b, 32, nullptr, EPI_BIAS, nullptr, 0, 0,
                e.net0, s));
   const float* net = e.net0;
   for (int i = 0; i < 9; ++i) {
@@ -345,24 +346,32 @@ int backward(Engine& e, int B) {
     RUN(odb_bn_elu_bwd(inp, f2, n_in, u.cin, a.stat_in, e.part, f1, f1, G + u.bn_in, s));
     std::swap(cur, f1);
   }
-  const OdbConv g0 = geom(B, e.h, e.w, 3, 16, 1, 1, 1);
+  const OdbConv g0 = geom(B, e.h, e.w, e.ch, 16, 1, 1, 1);   // [ch, 16]: 16 entries for a one-channel stem
   RUN(odb_conv_wgrad(g0, e.xb, nullptr, nullptr, cur, e.part, G + e.off.stem_w, s));
   RUN(odb_bias_grad(cur, (int64_t)B * e.h * e.w, 16, e.part, G + e.off.stem_b, s));
   return MMLA_OK;
 }
 
-// the classes of a blob of n_floats (body + 513 K), or 0
-int blob_classes(int64_t n_floats) {
-  const int64_t head = n_floats - od_body_floats();
-  return head >= 513 * 2 && head <= 513 * (int64_t)MMLA_OD_MAX_CLASSES && head % 513 == 0 ? (int)(head / 513) : 0;
+// the classes of a blob of n_floats (body + 513 K, 32 fewer for a one-channel stem: no two layouts share a
+// size) and its channels into *ch, or 0
+int blob_classes(int64_t n_floats, int* ch) {
+  for (int c : {3, 1}) {
+    const int64_t head = n_floats - od_body_floats() + (c == 1 ? 32 : 0);
+    if (head >= 513 * 2 && head <= 513 * (int64_t)MMLA_OD_MAX_CLASSES && head % 513 == 0) {
+      *ch = c;
+      return (int)(head / 513);
+    }
+  }
+  return 0;
 }
 
-// *K: the blob's classes
-int check_common(mmla_ctx* c, const char* who, int64_t n_floats, int32_t h, int32_t w, const float* class_w, int* K) {
-  *K = blob_classes(n_floats);
+// *K, *ch: the blob's classes and channels
+int check_common(mmla_ctx* c, const char* who, int64_t n_floats, int32_t h, int32_t w, const float* class_w, int* K,
+                 int* ch) {
+  *K = blob_classes(n_floats, ch);
   if (!*K)
-    return fail(c, MMLA_E_INVALID, "%s: n_floats %lld, the OD blob has %lld + 513 K with K in [2, %d]", who,
-                (long long)n_floats, (long long)od_body_floats(), MMLA_OD_MAX_CLASSES);
+    return fail(c, MMLA_E_INVALID, "%s: n_floats %lld, the OD blob has %lld + 513 K with K in [2, %d] (32 fewer "
+                "with a one-channel stem)", who, (long long)n_floats, (long long)od_body_floats(), MMLA_OD_MAX_CLASSES);
   if (h < kMinH || h > kMaxH || w < kMinW || w > kMaxW)
     return fail(c, MMLA_E_INVALID, "%s: image %d x %d outside [%d, %d] x [%d, %d]", who, h, w, kMinH, kMaxH, kMinW,
                 kMaxW);
@@ -390,12 +399,13 @@ int prepare(Engine& e, bool train) {
 }
 
 // the engine of a checked call: the blob's size, the class weights, every block's dimensions
-Engine engine(mmla_ctx* c, int K, int cap, int h, int w, const float* class_w) {
+Engine engine(mmla_ctx* c, int K, int ch, int cap, int h, int w, const float* class_w) {
   Engine e;
   e.c = c;
   e.cap = cap;
   e.K = K;
-  e.off = od_offsets(K);
+  e.ch = ch;
+  e.off = od_offsets(K, ch);
   for (int k = 0; k < K; ++k) e.cw[k] = class_w[k];
   set_dims(e, h, w);
   return e;
@@ -408,8 +418,8 @@ int od_fit(mmla_ctx* c, FitCall a, int32_t h, int32_t w, const float* class_w, c
            const uint8_t* drop_mask, bool scratch, int64_t drop_seed) {
   if (!c) return MMLA_E_INVALID;
   const char* who = a.who;
-  int K = 0;
-  CHK(check_common(c, who, (int64_t)a.n_floats, h, w, class_w, &K));
+  int K = 0, ch = 3;
+  CHK(check_common(c, who, (int64_t)a.n_floats, h, w, class_w, &K, &ch));
   const int32_t epochs = a.epochs;
   const int64_t n_train = a.n_train;
   a.unit = "images";
@@ -418,7 +428,7 @@ int od_fit(mmla_ctx* c, FitCall a, int32_t h, int32_t w, const float* class_w, c
   a.val_chunk = 16;
   a.n_classes = K;
   a.label_set = label_set(K);
-  a.row_bytes = (size_t)h * w * 3;
+  a.row_bytes = (size_t)h * w * ch;
   // rows after an early stop
   a.nan_fill = [](float* hist, size_t n, hipStream_t s) { return odb_fill(hist, (int64_t)n, __builtin_nanf(""), s); };
   CHK(fit_check(c, a));
@@ -426,7 +436,7 @@ int od_fit(mmla_ctx* c, FitCall a, int32_t h, int32_t w, const float* class_w, c
   for (int ep = 0; ep < epochs; ++ep)
     if (!std::isfinite(lr[ep]) || lr[ep] < 0.0f)
       return fail(c, MMLA_E_INVALID, "%s: lr[%d] = %g is negative or not finite", who, ep, lr[ep]);
-  Engine e = engine(c, K, a.cap(), h, w, class_w);
+  Engine e = engine(c, K, ch, a.cap(), h, w, class_w);
   e.auc = scratch;
   if (scratch) e.thr = odb_auc_thresholds();
   hipStream_t s = c->stream;
@@ -487,16 +497,16 @@ int mmla_od_loss_grad(mmla_ctx* c, const float* packed, int64_t n_floats, const 
                       const int32_t* labels, int64_t n, int32_t h, int32_t w, const float* class_w,
                       const uint8_t* drop_mask, float* loss, float* grad, float* moving_out, uint32_t flags) {
   if (!c) return MMLA_E_INVALID;
-  int K = 0;
-  CHK(check_common(c, "od_loss_grad", n_floats, h, w, class_w, &K));
+  int K = 0, ch = 3;
+  CHK(check_common(c, "od_loss_grad", n_floats, h, w, class_w, &K, &ch));
   if (n < 1 || n > MMLA_OD_TRAIN_MAX_BATCH)
     return fail(c, MMLA_E_INVALID, "od_loss_grad: n %lld outside [1, %d]", (long long)n, MMLA_OD_TRAIN_MAX_BATCH);
   if (!packed || !img_u8 || !labels || !loss || !grad) return fail(c, MMLA_E_INVALID, "od_loss_grad: null pointer");
   Stager st{c, (flags & MMLA_DEVICE_PTR) != 0};
   if (!st.dev) CHK(check_labels(c, "labels", labels, n, K, label_set(K)));
   HIPCHK(c, hipSetDevice(c->device));
-  Engine e = engine(c, K, (int)n, h, w, class_w);
-  const size_t img_bytes = (size_t)h * w * 3;
+  Engine e = engine(c, K, ch, (int)n, h, w, class_w);
+  const size_t img_bytes = (size_t)h * w * ch;
   float* lp = nullptr;
   const uint8_t *dimg = nullptr, *dmask = nullptr;
   const int32_t* dl = nullptr;

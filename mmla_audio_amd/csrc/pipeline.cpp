@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "internal.h"
+#include "nets.h"
 #include "resample.h"
 
 using namespace mmla;
@@ -211,10 +212,12 @@ int clip_call(mmla_ctx* c, CallKind kind, int64_t n, uint32_t flags, const char*
   return finish(c, dev);
 }
 
-// The front-ends' arguments on a device view of clips; the outputs are the caller's to set
+// The front-ends' arguments on a device view of clips; the outputs are the caller's to set.  img_type: the
+// image a feature call asks for; the pipelines (-1) make the loaded OD model's (mmla_od_set_image_type)
 template <typename T>
-OdFeArgs od_fe_args(const mmla_ctx* c, const PcmT<T>& p) {
+OdFeArgs od_fe_args(const mmla_ctx* c, const PcmT<T>& p, int img_type = -1) {
   OdFeArgs a{};
+  a.img_type = img_type < 0 ? c->od_img_type : img_type;
   if constexpr (std::is_same<T, float>::value) a.pcm_f32 = p.p;
   else a.pcm = p.p;
   a.clip_stride = p.stride;
@@ -283,11 +286,15 @@ int od_features_common(mmla_ctx* c, const T* pcm, int64_t n, int64_t stride, con
     return fail(c, MMLA_E_RANGE, "float PCM outside |y| < 8188 in clips %lld..%lld", (long long)c0,
                 (long long)(c0 + cnt - 1));
   };
-  return clip_call(c, FEATURES_OD, n, flags, bad_pcm_args(pcm, n, stride, lens, clip_len) ? "bad pcm args" : nullptr,
-                   [&](int64_t c0, int64_t cnt, bool dev, const Arith&) -> int {
+  // the image type in the flags' two bits: none = ZCR, both = no type
+  const int img_type = (int)((flags & MMLA_OD_IMG_MASK) >> MMLA_OD_IMG_SHIFT);
+  const char* bad = bad_pcm_args(pcm, n, stride, lens, clip_len) ? "bad pcm args"
+                    : img_type > MMLA_OD_IMG_VIRIDIS             ? "both image-type flags set"
+                                                                 : nullptr;
+  return clip_call(c, FEATURES_OD, n, flags, bad, [&](int64_t c0, int64_t cnt, bool dev, const Arith&) -> int {
     PcmT<T> p;
     CHK(stage_pcm(c, pcm, c0, cnt, stride, lens, clip_len, MMLA_OD_CLIP, dev, &p));
-    OdFeArgs a = od_fe_args(c, p);
+    OdFeArgs a = od_fe_args(c, p, img_type);
     if constexpr (std::is_same<T, float>::value) {
       a.range_flag = c->range_dev + (dev ? RW_DEV_RANGE : RW_HOST_RANGE);
       if (!dev) HIPCHK(c, hipMemsetAsync(a.range_flag, 0, sizeof(int), c->stream));
@@ -311,6 +318,24 @@ int od_features_common(mmla_ctx* c, const T* pcm, int64_t n, int64_t stride, con
   });
 }
 
+// A caller's OD images [cnt,128,151,C] (C of the loaded model) on the device as the network reads them,
+// 3 per pixel: a three-channel model's as they are (host: copied into `slot`), a one-channel model's
+// widened to (g, g, g) into `slot`
+template <typename T>
+int od_net_input(mmla_ctx* c, const T* user, int64_t cnt, bool dev, int slot, const T** d) {
+  if (c->od.channels == 3) return in_ptr(c, user, cnt * OD_IMG, dev, slot, d);
+  const T* g = nullptr;
+  CHK(in_ptr(c, user, cnt * OD_PIX, dev, S_WIDE, &g));
+  void* w = nullptr;
+  CHK(ws_get(c, slot, cnt * OD_IMG * sizeof(T), &w));
+  if constexpr (std::is_same<T, float>::value)
+    LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * OD_PIX * 16, od_widen_launch(nullptr, g, cnt * OD_PIX, w, c->stream));
+  else
+    LAUNCH(c, MMLA_STAGE_GLUE, (double)cnt * OD_PIX * 4, od_widen_launch(g, nullptr, cnt * OD_PIX, w, c->stream));
+  *d = static_cast<const T*>(w);
+  return MMLA_OK;
+}
+
 // OD-NET over float NHWC (x_f32) or uint8 (x_u8) images
 int od_forward_common(mmla_ctx* c, const float* x_f32, const uint8_t* x_u8, int64_t n, float* probs,
                       uint32_t flags) {
@@ -319,8 +344,9 @@ int od_forward_common(mmla_ctx* c, const float* x_f32, const uint8_t* x_u8, int6
                    [&](int64_t c0, int64_t cnt, bool dev, const Arith& ar) -> int {
     const float* df = nullptr;
     const uint8_t* du = nullptr;
-    if (x_f32) CHK(in_ptr(c, x_f32 + c0 * OD_IMG, cnt * OD_IMG, dev, S_IN, &df));
-    else CHK(in_ptr(c, x_u8 + c0 * OD_IMG, cnt * OD_IMG, dev, S_IMG, &du));
+    const int64_t per = (int64_t)OD_PIX * c->od.channels;
+    if (x_f32) CHK(od_net_input(c, x_f32 + c0 * per, cnt, dev, S_IN, &df));
+    else CHK(od_net_input(c, x_u8 + c0 * per, cnt, dev, S_IMG, &du));
     float* dp;
     const int k = c->od.k;
     CHK(out_ptr(c, probs, c0 * k, cnt * k, dev, S_OUT0, &dp));
@@ -392,7 +418,9 @@ int od_pipeline_common(mmla_ctx* c, const int16_t* pcm, int64_t n, int64_t strid
   const char* bad = bad_pcm_args(pcm, n, stride, lens, clip_len) ? "bad pcm args" : nullptr;
   const bool ns = flags & MMLA_NR_NONSTATIONARY;   // the passes run the non-stationary gate: no bank
   if (c && !bad && gated) {
-    if (nr_passes < 0) bad = "nr_passes < 0";
+    // the gate's SSIM is defined on the ZCR images (record_on_pi.py:117-120)
+    if (c->od_loaded && c->od_img_type != MMLA_OD_IMG_ZCR) bad = "the gated pipeline needs a ZCR model";
+    else if (nr_passes < 0) bad = "nr_passes < 0";
     else if (nr_passes > 0 && !ns && !c->nr_ready) bad = "nr_passes > 0: mmla_nr_set_noise must be called first";
   }
   return clip_call(c, NET_OD, n, flags, bad, [&](int64_t c0, int64_t cnt, bool dev, const Arith& ar) -> int {
@@ -1325,7 +1353,7 @@ int mmla_debug_od_trace(mmla_ctx* c, const float* x, int64_t n, int stage, float
   if (!c->od_loaded) return fail(c, MMLA_E_NOWEIGHTS, "OD weights not loaded");
   HIPCHK(c, hipSetDevice(c->device));
   const float* dx;
-  CHK(in_ptr(c, x, n * OD_IMG, false, S_IN, &dx));
+  CHK(od_net_input(c, x, n, false, S_IN, &dx));
   auto body = [&](const Arith& ar) -> int {
     const float* tap = nullptr;
     int64_t tn = 0;

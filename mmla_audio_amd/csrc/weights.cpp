@@ -191,15 +191,32 @@ extern "C" int mmla_load_weights(mmla_ctx* c, int kind, const float* packed, int
       return fail(c, MMLA_E_INVALID, "OD n_classes %d outside [2, %d]", n_classes, MMLA_OD_MAX_CLASSES);
     // more than two classes: the size is checked before the loaded model is let go (a two-class blob of the
     // wrong size keeps its MMLA_E_SHAPE below)
+    // a one-channel model's blob (stem [1,1,1,16]) is 32 floats shorter; 513 K - 32 is no multiple of 513,
+    // so no three-channel blob has that size
+    const int channels = n_floats == od_blob_floats(n_classes, 1) ? 1 : 3;
     const int64_t want = od_blob_floats(n_classes);
-    if (n_classes != 2 && n_floats != want)
+    if (n_classes != 2 && channels == 3 && n_floats != want)
       return fail(c, MMLA_E_INVALID, "OD blob of %lld floats, %d classes need %lld", (long long)n_floats, n_classes,
                   (long long)want);
     free_allocs(c->od_allocs);
     c->od_loaded = false;
     OdNet& W = c->od;
     auto& al = c->od_allocs;
-    CHK(take_conv(c, cur, al, 1, 1, 3, 16, &W.stem));
+    if (channels == 1) {
+      // the stem as three rows {w, 0, 0} (and its bias): the network reads the pixel (g, g, g), and
+      // fma(g, 0, acc) leaves the one-channel sum as it is
+      const float* k1 = cur.take(16);
+      const float* b1 = cur.take(16);
+      if (!cur.ok) return fail(c, MMLA_E_SHAPE, "weight blob too short");
+      float wide[4 * 16] = {0.0f};
+      memcpy(wide, k1, 16 * sizeof(float));
+      memcpy(wide + 3 * 16, b1, 16 * sizeof(float));
+      Cursor cs{wide, 4 * 16};
+      CHK(take_conv(c, cs, al, 1, 1, 3, 16, &W.stem));
+      if (cs.f16_bad) cur.f16_bad = true;
+    } else {
+      CHK(take_conv(c, cur, al, 1, 1, 3, 16, &W.stem));
+    }
     CHK(take_units(c, cur, al, W.blk, 16, 3, 3, 4, 1, true));
     CHK(take_lstm(c, cur, al, 128, &W.lstm));
     const float* hw = cur.take(512 * (int64_t)n_classes);
@@ -210,6 +227,8 @@ extern "C" int mmla_load_weights(mmla_ctx* c, int kind, const float* packed, int
     W.k = n_classes;
     if (cur.left != 0)
       return fail(c, MMLA_E_SHAPE, "OD weight blob has %lld extra floats", (long long)cur.left);
+    W.channels = channels;
+    c->od_img_type = channels == 1 ? MMLA_OD_IMG_GRAY : MMLA_OD_IMG_ZCR;   // the type is the model's: reset
     c->od_f32_only = cur.f16_bad;   // some weight outside the fp16 range: exact f32 only
     c->od_loaded = true;
     return MMLA_OK;
@@ -246,6 +265,24 @@ extern "C" int mmla_od_classes(mmla_ctx* c, int32_t* k) {
   if (!k) return fail(c, MMLA_E_INVALID, "od_classes: null pointer");
   if (!c->od_loaded) return fail(c, MMLA_E_NOWEIGHTS, "OD weights not loaded");
   *k = c->od.k;
+  return MMLA_OK;
+}
+
+extern "C" int mmla_od_set_image_type(mmla_ctx* c, int32_t type) {
+  if (!c) return MMLA_E_INVALID;
+  if (!c->od_loaded) return fail(c, MMLA_E_NOWEIGHTS, "OD weights not loaded");
+  if (type < MMLA_OD_IMG_ZCR || type > MMLA_OD_IMG_VIRIDIS) return fail(c, MMLA_E_INVALID, "unknown image type %d", type);
+  if (c->od.channels == 1 && type != MMLA_OD_IMG_GRAY)
+    return fail(c, MMLA_E_INVALID, "a one-channel OD model reads gray images only (type %d)", type);
+  c->od_img_type = type;
+  return MMLA_OK;
+}
+
+extern "C" int mmla_od_image(mmla_ctx* c, int32_t* type, int32_t* channels) {
+  if (!c) return MMLA_E_INVALID;
+  if (!c->od_loaded) return fail(c, MMLA_E_NOWEIGHTS, "OD weights not loaded");
+  if (type) *type = c->od_img_type;
+  if (channels) *channels = c->od.channels;
   return MMLA_OK;
 }
 

@@ -30,6 +30,16 @@ def _layout_from_path(path):
     return None
 
 
+def _od_channels_from_path(path):
+    """the channels the bundle index names for an OD stem kernel [1,1,C,16]; 3 without one"""
+    idx = os.path.join(path, 'variables', 'variables.index')
+    if os.path.exists(idx):
+        k0 = tfbundle.variable_shapes(idx).get('layer_with_weights-0/kernel')
+        if k0 is not None and len(k0) == 4 and int(k0[2]) in weights.OD_CHANNELS:
+            return int(k0[2])
+    return 3
+
+
 def _kind_from_path(path):
     lay = _layout_from_path(path)
     if lay is not None:
@@ -47,14 +57,19 @@ class _Model:
         self.head = head
         self.synthetic = synthetic
         self.W = W
-        self.ctx.load_weights(self.kind, weights.pack(self.kind, W, n_classes), n_classes, head)
+        self._load()
+
+    def _pack(self):
+        return weights.pack(self.kind, self.W, self.n_classes)
+
+    def _load(self):
+        self.ctx.load_weights(self.kind, self._pack(), self.n_classes, self.head)
 
     def _ensure_loaded(self):
         # several models can share one context; re-load if another model of this kind replaced ours
         cls = self.ctx.od_classes if self.kind == weights.OD else self.ctx.si_classes
         if getattr(self.ctx, f'_owner_{self.kind}', None) is not self or cls != self.n_classes:
-            self.ctx.load_weights(self.kind, weights.pack(self.kind, self.W, self.n_classes),
-                                  self.n_classes, self.head)
+            self._load()
             setattr(self.ctx, f'_owner_{self.kind}', self)
 
     def _predict_conditioned(self, call, pcm, noise, mic, lens, passes, silence_remove,
@@ -101,28 +116,57 @@ class _Model:
 class OverlapDetectionModel(_Model):
     """OD-NET (ResLSTM, overlap_detector_temp.py:280-303): predict(float32 [N,128,151,3]) -> [N,K].  K, the
     classes of the softmax head, is the width of W's Dense kernel: 2 for the deployed model, 3 for the
-    reference's research models; every [N,2] below is [N,K] for such a model."""
+    reference's research models; every [N,2] below is [N,K] for such a model.
+
+    ``channels`` is the stem kernel's [1,1,C,16]: 3, or 1 for a model of ``OverlapDetector(imagetype='gray')``
+    (overlap_detector.py:84-90), whose predict reads [N,128,151,1].  ``image_type`` ('zcr', 'gray' or
+    'viridis') is the feature image the model was trained on, what ``predict_wavs*`` make in front of the
+    network; default 'zcr' for three channels and 'gray' for one (a one-channel model takes no other).  The
+    type is not stored in a TF checkpoint -- a three-channel model trained on gray or viridis images must
+    be told: ``load_model(path, image_type='viridis')``."""
     kind = weights.OD
 
-    def __init__(self, W, device=None, synthetic=False):
+    def __init__(self, W, device=None, synthetic=False, image_type=None):
+        self.channels = weights.od_channels(W)
+        if image_type is None:
+            image_type = 'gray' if self.channels == 1 else 'zcr'
+        t = _lib.od_image_type(image_type)
+        self.image_type = {v: k for k, v in _lib.OD_IMAGE_TYPES.items()}[t]
+        if self.channels == 1 and t != _lib.OD_IMG_GRAY:
+            raise ValueError(f"a one-channel OD model reads gray images, not {self.image_type!r}")
         super().__init__(W, weights.od_classes(W), _lib.HEAD_SOFTMAX, device, synthetic)
         setattr(self.ctx, f'_owner_{self.kind}', self)
+
+    def _pack(self):
+        return weights.pack(self.kind, self.W, self.n_classes, weights.od_channels(self.W))
+
+    def _load(self):
+        super()._load()      # the load resets the context's image type to the channel count's default
+        self.ctx.od_set_image_type(self.image_type)
+
+    def _ensure_loaded(self):
+        super()._ensure_loaded()
+        if self.ctx.od_image_type != _lib.od_image_type(self.image_type):   # set behind the model's back
+            self.ctx.od_set_image_type(self.image_type)
 
     def set_weights(self, W):
         """Replace every tensor of the model in place (one ``mmla_load_weights`` of the whole blob): the
         network an adaptation produced (``overlap_detector.continue_train``).  self.W follows only once
         the load succeeded."""
-        k = weights.od_classes(W)
-        blob = weights.pack(self.kind, W, k)
+        k, ch = weights.od_classes(W), weights.od_channels(W)
+        if ch != self.channels:
+            raise ValueError(f'set_weights: a {ch}-channel network for a {self.channels}-channel model')
+        blob = weights.pack(self.kind, W, k, ch)
         self.ctx.load_weights(self.kind, blob, k, _lib.HEAD_SOFTMAX)
+        self.ctx.od_set_image_type(self.image_type)
         setattr(self.ctx, f'_owner_{self.kind}', self)
         self.W, self.n_classes = dict(W), k
 
     def predict(self, x, batch_size=None, verbose=0):
         self._ensure_loaded()
         x = np.asarray(x)
-        if x.ndim != 4 or x.shape[1:] != (128, 151, 3):
-            raise ValueError(f'OD model expects [N,128,151,3], got {x.shape}')
+        if x.ndim != 4 or x.shape[1:] != (128, 151, self.channels):
+            raise ValueError(f'OD model expects [N,128,151,{self.channels}], got {x.shape}')
         return self.ctx.od_forward(x)
 
     def predict_wavs(self, pcm, lens=None):
@@ -247,13 +291,15 @@ class SpeakerIdModel(_Model):
 
 
 def load_model(path, kind=None, n_classes=None, head=None, seed=0, device=None,
-               allow_synthetic=False):
+               allow_synthetic=False, image_type=None):
     """tf.keras.models.load_model drop-in for the reference's model directories: the OD base models
     (timit/models/timit{1.0,2.0}), the SI base model (timit/model, Dense(630) softmax) and the
     deployed SI model transfer_learning saves (experiment/model: the sliced base nested inside a
     model with the customized_dense sigmoid head, speaker_identification.py:401-410,456) -- the
     layout is read from the bundle index (tfbundle.layout), K and the head from its head kernel.
-    Raises FileNotFoundError when the trained variables are absent, unless allow_synthetic=True."""
+    Raises FileNotFoundError when the trained variables are absent, unless allow_synthetic=True.
+    image_type (OD only): the feature image the model reads, 'zcr', 'gray' or 'viridis'; None = 'zcr' for a
+    three-channel model, 'gray' for a one-channel one.  A TF checkpoint does not store it."""
     lay = _layout_from_path(path)
     kind = (lay[0] if lay else _kind_from_path(path)) if kind is None else kind
     synthetic = False
@@ -279,10 +325,11 @@ def load_model(path, kind=None, n_classes=None, head=None, seed=0, device=None,
             n_classes = lay[1]                        # the Dense shape the index names
         warnings.warn(f'{path}: trained weights absent (reference .MISSING_LARGE_BLOBS); using seeded '
                       f'synthetic weights in the reference layout (seed={seed})')
-        W = weights.synthetic(kind, seed=seed, n_classes=n_classes)
+        channels = _od_channels_from_path(path) if kind == weights.OD else 3
+        W = weights.synthetic(kind, seed=seed, n_classes=n_classes, channels=channels)
         synthetic = True
     if kind == weights.OD:
-        return OverlapDetectionModel(W, device=device, synthetic=synthetic)
+        return OverlapDetectionModel(W, device=device, synthetic=synthetic, image_type=image_type)
     if n_classes is None:
         n_classes = W['layer_with_weights-42/kernel'].shape[1]
     if head is None:

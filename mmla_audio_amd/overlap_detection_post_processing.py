@@ -248,7 +248,8 @@ def predict_frames(x, nchannels, model, sr=16000, win_time_stride=1.5, step_time
     """predict_segments of interleaved 16-bit frames: a mono signal goes through the fused int16
     pipeline; a multi-channel one as what librosa.load(segment, sr=None) gives each segment file --
     the float32 channel mean (x / 2^15 per channel) -- through the float front-end entry
-    (mmla_od_features_f32) over the same strided windows, then OD-NET on the images."""
+    (mmla_od_features_f32) over the same strided windows, then OD-NET on the images.  Both make the
+    model's image type (``model.image_type``; a one-channel model reads channel 0 of the gray image)."""
     x = np.ascontiguousarray(x, dtype=np.int16).reshape(-1)
     if nchannels == 1:
         return predict_segments(x, model, sr, win_time_stride, step_time)
@@ -260,10 +261,20 @@ def predict_frames(x, nchannels, model, sr=16000, win_time_stride=1.5, step_time
     if n == 0:
         return np.zeros((0, model.n_classes), np.float32), np.zeros(0, np.int32), []
     model._ensure_loaded()
-    f = model.ctx.od_features_strided(y, n, step, win, db=False, norm=False, zcr=False, img=True)
-    probs = model.ctx.od_forward(f['img'])
+    probs = _model_forward(model, _model_images(model, y, n, step, win))
     am = probs.argmax(1).astype(np.int32)
     return probs, am, [class_label(k, model.n_classes) for k in am]
+
+
+def _model_images(model, sig, n, step, win):
+    """the images [n,128,151,3] of n strided windows of `sig` in the model's image type (gray: R = G = B)"""
+    return model.ctx.od_features_strided(sig, n, step, win, db=False, norm=False, zcr=False, img=True,
+                                         image_type=model.image_type)['img']
+
+
+def _model_forward(model, images):
+    """OD-NET on front-end images: a one-channel model reads channel 0, what decode_png(png, 1) gives"""
+    return model.ctx.od_forward(np.ascontiguousarray(images[..., :model.channels]))
 
 
 def _segment_index(name):
@@ -272,7 +283,8 @@ def _segment_index(name):
 
 
 def _window_images(x, nchannels, model, sr, win_time_stride, step_time):
-    """the model-input images of every segment window (what generate_zcr_image writes as PNG) and
+    """the model-input images of every segment window (what generate_zcr_image -- or, for a gray or
+    viridis model, generate_gary_image / generate_viridis_image -- writes as PNG; uint8 [n,128,151,3]) and
     their OD-NET probabilities"""
     x = np.ascontiguousarray(x, dtype=np.int16).reshape(-1)
     if nchannels == 1:
@@ -284,8 +296,8 @@ def _window_images(x, nchannels, model, sr, win_time_stride, step_time):
     if n == 0:
         return np.zeros((0, 128, 151, 3), np.uint8), np.zeros((0, model.n_classes), np.float32)
     model._ensure_loaded()
-    f = model.ctx.od_features_strided(sig, n, step, win, db=False, norm=False, zcr=False, img=True)
-    return f['img'], model.ctx.od_forward(f['img'])
+    images = _model_images(model, sig, n, step, win)
+    return images, _model_forward(model, images)
 
 
 def post_anlysing(root_dir, model, ctx=None, noise_path=None, start_time=None, write_features=True):

@@ -56,20 +56,21 @@ def fit_plan(labels, seed, epochs, val_ratio=0.2):
 
 def continue_train(W, images, labels, plan, epochs, batch_size, weighted=True, patience=10, device=None):
     """``continue_train_model`` on the device: W {name: array} (weights.od_spec(K), K from its head), images
-    uint8 [n,h,w,3], labels [n] in [0, K), plan = fit_plan(labels, seed, epochs).  weighted: the loss's class
-    weights are cal_weighted_penalty of the training labels, else ones.
+    uint8 [n,h,w,C] with C the channels of W's stem (3, or 1 for an imagetype='gray' model), labels [n] in
+    [0, K), plan = fit_plan(labels, seed, epochs).  weighted: the loss's class weights are
+    cal_weighted_penalty of the training labels, else ones.
     -> (W' {name: float32 array}, history [epochs_total, 5] = loss, acc, val_loss, val_acc, lr, epochs_run)"""
     ctx = device if isinstance(device, _lib.Context) else _lib.default_context(device)
     images = np.asarray(images, np.uint8)
     labels = np.asarray(labels, np.int32)
     tr, va = plan['train'], plan['val']
-    K = weights.od_classes(W)
+    K, ch = weights.od_classes(W), weights.od_channels(W)
     cw = cal_weighted_penalty(np.eye(K)[labels[tr]]) if weighted else np.ones(K)
-    out, hist, ran = ctx.od_finetune(weights.pack(weights.OD, W, K), images[tr], labels[tr],
+    out, hist, ran = ctx.od_finetune(weights.pack(weights.OD, W, K, ch), images[tr], labels[tr],
                                      images[va] if len(va) else None, labels[va] if len(va) else None, cw,
                                      cosine_lr(epochs), plan['perm'], plan['drop_mask'], epochs, batch_size,
                                      patience)
-    return weights.unpack(weights.OD, out, K), hist, ran
+    return weights.unpack(weights.OD, out, K, ch), hist, ran
 
 
 # ---- training from scratch: augment_images (:143-220), train_model (:392-451) -----------------------------
@@ -146,15 +147,25 @@ def augment_plan(labels, n_classes=None):
     return src, np.concatenate(levels).astype(np.int32), labels[src].astype(np.int32)
 
 
+def _augment(ctx, images, src, levels):
+    """``mmla_od_augment`` on [n,h,w,3], or on one-channel images [n,h,w,1]: widened to three equal channels
+    (what ``cv.imread`` gives the reference for a gray PNG), blurred on the same kernel, channel 0 returned --
+    the blur is per channel, so this is exact"""
+    if images.shape[3] == 1:
+        return np.ascontiguousarray(ctx.od_augment(np.repeat(images, 3, axis=3), src, levels)[..., :1])
+    return ctx.od_augment(images, src, levels)
+
+
 def augment_images(images, labels, ctx=None):
-    """``augment_images`` on arrays: images uint8 [n,h,w,3], labels [n] -> (images_aug [m,h,w,3], labels_aug
-    [m]) in ``augment_plan``'s order, the blurred copies through ``mmla_od_augment``."""
+    """``augment_images`` on arrays: images uint8 [n,h,w,C] (C = 3 or 1), labels [n] -> (images_aug [m,h,w,C],
+    labels_aug [m]) in ``augment_plan``'s order, the blurred copies through ``mmla_od_augment``."""
     ctx = ctx if isinstance(ctx, _lib.Context) else _lib.default_context(ctx)
     images = np.asarray(images)
-    if images.dtype != np.uint8 or images.ndim != 4 or images.shape[0] != len(labels):
-        raise ValueError(f'images {images.shape} {images.dtype}: expected uint8 [n,h,w,3], one per label')
+    if images.dtype != np.uint8 or images.ndim != 4 or images.shape[3] not in weights.OD_CHANNELS or \
+            images.shape[0] != len(labels):
+        raise ValueError(f'images {images.shape} {images.dtype}: expected uint8 [n,h,w,3] or [n,h,w,1], one per label')
     src, levels, new_labels = augment_plan(labels)
-    return ctx.od_augment(images, src, levels), new_labels
+    return _augment(ctx, images, src, levels), new_labels
 
 
 def train_model(x_train, y_train, x_val, y_val, *, epochs, batch_size, weighted=False, augmented=False, seed=0,
@@ -162,7 +173,9 @@ def train_model(x_train, y_train, x_val, y_val, *, epochs, batch_size, weighted=
     """``OverlapDetector.train_model`` on the device (``mmla_od_train``): ``__ResBLSTM`` from its Keras initial
     state (``weights.initial_od(seed)``) under Adadelta with the cosine schedule, EarlyStopping(val_loss,
     patience) and ModelCheckpoint(val_categorical_accuracy, save_best_only, 'max', period=1).  Images uint8
-    [n,h,w,3]; labels integers or one-hot rows.  augmented: the training set is balanced first
+    [n,h,w,3], or [n,h,w,1] for the one-channel network of ``OverlapDetector(imagetype='gray')`` (:84-90: the
+    stem is Conv2D(16, 1) on one channel; the model returned then has ``channels == 1``); labels integers or
+    one-hot rows.  augmented: the training set is balanced first
     (``augment_images``); weighted: the loss's class weights are ``cal_weighted_penalty`` of the (possibly
     augmented) training labels, else ones.  n_classes (the script's ``class_dim = y_train.shape[1]``, :394):
     None = the width of one-hot labels, or the largest label + 1, never below 2.  x_val None or empty: no
@@ -178,15 +191,18 @@ def train_model(x_train, y_train, x_val, y_val, *, epochs, batch_size, weighted=
     ctx = device if isinstance(device, _lib.Context) else _lib.default_context(device)
     x_train = np.asarray(x_train)
     labels = _class_labels(y_train, 'y_train')
-    if x_train.dtype != np.uint8 or x_train.ndim != 4 or len(x_train) != len(labels):
-        raise ValueError(f'x_train {x_train.shape} {x_train.dtype}: expected uint8 [n,h,w,3], one per label')
+    if x_train.dtype != np.uint8 or x_train.ndim != 4 or x_train.shape[3] not in weights.OD_CHANNELS or \
+            len(x_train) != len(labels):
+        raise ValueError(f'x_train {x_train.shape} {x_train.dtype}: expected uint8 [n,h,w,3] or [n,h,w,1], one '
+                         'per label')
+    ch = int(x_train.shape[3])
     nv = 0 if x_val is None else len(x_val)
     vx = vl = None
     if nv:
         vx, vl = np.asarray(x_val), _class_labels(y_val, 'y_val')
         if vx.dtype != np.uint8 or vx.shape[1:] != x_train.shape[1:] or len(vl) != nv:
             raise ValueError(f'x_val {vx.shape} {vx.dtype}: expected uint8 [n,{x_train.shape[1]},'
-                             f'{x_train.shape[2]},3], one per label')
+                             f'{x_train.shape[2]},{ch}], one per label')
     epochs = int(epochs)
     if epochs < 0 or batch_size < 1:
         raise ValueError('epochs must be >= 0 and batch_size >= 1')
@@ -198,21 +214,21 @@ def train_model(x_train, y_train, x_val, y_val, *, epochs, batch_size, weighted=
             raise ValueError(f'{what}: a label outside the {K} classes')
     if augmented:
         src, levels, labels = augment_plan(labels, K)
-        x_train = ctx.od_augment(x_train, src, levels)
+        x_train = _augment(ctx, x_train, src, levels)
     cw = cal_weighted_penalty(np.eye(K)[labels]) if weighted else np.ones(K)
     n = len(labels)
     rng_p = np.random.default_rng([int(seed), 1])       # fit_plan's generator of the epochs' orders
     perm = np.stack([rng_p.permutation(n) for _ in range(epochs)]).astype(np.int32) if epochs else \
         np.zeros((0, n), np.int32)
     drop_seed = int(np.random.default_rng([int(seed), 2]).integers(0, 2 ** 63))
-    W0 = weights.initial_od(seed, K)
-    out, best, hist, ran, best_ep = ctx.od_train(weights.pack(weights.OD, W0, K), x_train, labels, vx, vl, cw,
+    W0 = weights.initial_od(seed, K, ch)
+    out, best, hist, ran, best_ep = ctx.od_train(weights.pack(weights.OD, W0, K, ch), x_train, labels, vx, vl, cw,
                                                  cosine_lr(epochs), perm, epochs, batch_size, drop_seed, patience,
                                                  1)
-    model = models.OverlapDetectionModel(weights.unpack(weights.OD, out, K), device=ctx)
+    model = models.OverlapDetectionModel(weights.unpack(weights.OD, out, K, ch), device=ctx)
     if checkpoint_path is not None and best is not None:
         os.makedirs(checkpoint_path, exist_ok=True)
-        tfbundle.save_overlap(checkpoint_path, weights.unpack(weights.OD, best, K))
+        tfbundle.save_overlap(checkpoint_path, weights.unpack(weights.OD, best, K, ch))
     if save_path is not None:
         os.makedirs(save_path, exist_ok=True)
         tfbundle.save_overlap(save_path, model.W)

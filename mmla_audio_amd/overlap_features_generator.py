@@ -54,23 +54,28 @@ def _features(ctx, x, **kw):
     return ctx.od_features(x[None], lens=np.array([len(x)], np.int32), **kw)
 
 
-def write_png_rgba(path, rgb):
+def write_png_rgba(path, rgb, alpha=None):
     """Write the image file ``plt.imsave(path, img, origin="lower")`` writes (:151) for the already
     flipped and quantised uint8 pixels ``rgb``: through matplotlib's own writer when it is
     importable (uint8 RGB is written as is, alpha 255 -- the same bytes as the reference for the
     same pixels and matplotlib version), else a minimal RGBA PNG encoder.  Either way decoders
-    reading 3 channels (``tf.image.decode_png(img, 3)``, record_on_pc.py:157) get ``rgb`` back."""
+    reading 3 channels (``tf.image.decode_png(img, 3)``, record_on_pc.py:157) get ``rgb`` back.
+    ``alpha`` (uint8 [h, w], default all 255): the colour-mapped images carry alpha 0 where the value was
+    NaN (``imsave(..., cmap=...)`` of a silent clip writes RGBA (0, 0, 0, 0))."""
     try:
         from matplotlib import image as mimage
     except ImportError:
         mimage = None
-    if mimage is not None:
+    h, w, _ = rgb.shape
+    if mimage is not None and alpha is None:
         mimage.imsave(path, np.ascontiguousarray(rgb, dtype=np.uint8), origin='upper')
         return
-    h, w, _ = rgb.shape
     rgba = np.empty((h, w, 4), np.uint8)
     rgba[..., :3] = rgb
-    rgba[..., 3] = 255
+    rgba[..., 3] = 255 if alpha is None else alpha
+    if mimage is not None:       # uint8 RGBA is written as is
+        mimage.imsave(path, rgba, origin='upper')
+        return
     raw = b''.join(b'\x00' + rgba[r].tobytes() for r in range(h))
 
     def chunk(tag, data):
@@ -158,7 +163,39 @@ class OverlapFeaturesGenerator:
         write_png_rgba(out_dir + out_name, f['img'][0])
         return None
 
+    def _cmap_image(self, wav_file_path, out_dir, out_name, image_type):
+        if not os.path.isdir(out_dir):
+            os.mkdir(out_dir)
+        _, x = _load(wav_file_path)
+        f = _features(self._ctx, x, db=False, zcr=False, image_type=image_type)
+        # a NaN value (digital silence: every pixel of the clip) is imsave's transparent black
+        alpha = np.where(np.isnan(f['norm'][0][::-1]), 0, 255).astype(np.uint8)
+        write_png_rgba(out_dir + out_name, f['img'][0], alpha)
+
+    def generate_gary_image(self, wav_file_path, out_dir, out_name):
+        """(:119-124; the reference's spelling.)  Writes ``out_dir + out_name``: the PNG of
+        ``plt.imsave(path, norm, origin="lower", cmap="gray")`` -- pixel ``LUT_gray[min(trunc(256 v), 255)]``
+        as R = G = B with alpha 255, RGBA (0, 0, 0, 0) for a silent clip's NaN."""
+        self._cmap_image(wav_file_path, out_dir, out_name, 'gray')
+
+    def generate_viridis_image(self, wav_file_path, out_dir, out_name):
+        """(:126-131.)  As ``generate_gary_image`` with ``cmap="viridis"``."""
+        self._cmap_image(wav_file_path, out_dir, out_name, 'viridis')
+
+    def generate_images(self, wav_file_path, out_name):
+        """(:153-177.)  Writes ``./mel_spectrum_viridis/``, ``./mel_spectrum_gray/`` and
+        ``./mel_spectrum_zcr/`` + out_name, creating the directories.
+
+        Deviation: the reference's body cannot run -- it calls ``self.resize_features`` (no such method;
+        ``resize_mel_features`` would crop to 150 frames) and ``self.generate_zcr_image(wav_file_path)``
+        without its ``out_dir``.  This writes what its three per-image methods write: the uncropped
+        [128, 151] images of ``generate_viridis_image``, ``generate_gary_image`` and ``generate_zcr_image``."""
+        self.generate_viridis_image(wav_file_path, './mel_spectrum_viridis/', out_name)
+        self.generate_gary_image(wav_file_path, './mel_spectrum_gray/', out_name)
+        self.generate_zcr_image(wav_file_path, './mel_spectrum_zcr/', out_name)
+
     # -- batched API (the MI355X-native path) ----------------------------------------------------
-    def generate_batch(self, pcm, lens=None, db=False, norm=True, zcr=True, img=True):
-        """int16 PCM [n, L] (or a list of 1-D arrays) -> dict of batched features."""
-        return self._ctx.od_features(pcm, lens=lens, db=db, norm=norm, zcr=zcr, img=img)
+    def generate_batch(self, pcm, lens=None, db=False, norm=True, zcr=True, img=True, image_type='zcr'):
+        """int16 PCM [n, L] (or a list of 1-D arrays) -> dict of batched features; image_type 'zcr',
+        'gray' or 'viridis' picks the image (uint8 [n,128,151,3] for all three, gray as R = G = B)."""
+        return self._ctx.od_features(pcm, lens=lens, db=db, norm=norm, zcr=zcr, img=img, image_type=image_type)

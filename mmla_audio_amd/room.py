@@ -273,7 +273,8 @@ class Room:
         training pool and the rest to the validation pool, so validation mixes are made of audio the fit never
         saw.  ``data_augmentation.overlap_plan`` (one random.Random(seed)) draws n_overlapped + n_single
         training mixes, then a quarter as many (at least one each) validation mixes; ``od_mix`` mixes them and
-        the project's front end makes the feature images.  The validation mixes are scored with the current
+        the project's front end makes the feature images, of the model's image type (a three-channel model of any
+        type; a one-channel model raises ValueError).  The validation mixes are scored with the current
         model (`before`), the fit runs `epochs` epochs at most (Adadelta, the cosine schedule, class weights
         when `weighted`, early stopping with `patience`), and they are scored again (`after`).  ``install``
         loads the new weights into the room in place; ``save_to`` writes them (``tfbundle.save_overlap``).
@@ -287,6 +288,9 @@ class Room:
         from . import _lib, overlap_detector, tfbundle
         from .data_augmentation import confusion, overlap_plan
         self._two_class_od('overlap_adapt')
+        if self.od.channels != 3:
+            raise ValueError(f'overlap_adapt: the OD model reads {self.od.channels}-channel images; training on '
+                             'device-made images is built for three-channel models only')
         K = len(recordings)
         if K < 2:
             raise ValueError(f'{K} recordings: an overlap adaptation needs at least two speakers')
@@ -310,7 +314,8 @@ class Room:
 
         def images(pool, plan):
             clips, lens = self.ctx.od_mix(pool, plan)
-            return self.ctx.od_features(clips, lens=lens, db=False, norm=False, zcr=False)['img']
+            return self.ctx.od_features(clips, lens=lens, db=False, norm=False, zcr=False,
+                                        image_type=self.od.image_type)['img']
 
         img_tr, img_va = images(pool_tr, plan_tr), images(pool_va, plan_va)
 

@@ -184,7 +184,9 @@ def layout(shapes):
         if kind == weights.OD:
             hk = shapes.get('layer_with_weights-41/kernel')
             n_classes = int(hk[1]) if hk is not None and len(hk) == 2 else 2   # the Dense(K) head
-            items, head = weights.od_spec(n_classes), _lib.HEAD_SOFTMAX
+            # the stem kernel's [1,1,C,16] names the channels (1: OverlapDetector(imagetype='gray'))
+            channels = int(k0[2]) if int(k0[2]) in weights.OD_CHANNELS else 3
+            items, head = weights.od_spec(n_classes, channels), _lib.HEAD_SOFTMAX
         else:
             head_kernel = shapes.get('layer_with_weights-42/kernel')
             if head_kernel is None or len(head_kernel) != 2:
@@ -318,9 +320,10 @@ def save_overlap(model_dir, W):
     the variables are written, and parity of the key layout with a real TF save is unpinned."""
     from . import weights
     k = weights.od_classes(W)      # any K: the head is the last item, so the BiLSTM's indices do not move
-    weights.check(weights.OD, W, k)
+    ch = weights.od_channels(W)    # 3 or 1: the stem kernel's shape alone differs
+    weights.check(weights.OD, W, k, ch)
     tensors = {}
-    for i, (name, _, role) in enumerate(weights.od_spec(k)):
+    for i, (name, _, role) in enumerate(weights.od_spec(k, ch)):
         tensors[f'variables/{i}' if role.startswith('lstm_') else name] = W[name]
     _write_bundle(model_dir, tensors)
 

@@ -54,12 +54,18 @@ def _bilstm(k, d):
 OD_MAX_CLASSES = 8   # MMLA_OD_MAX_CLASSES
 
 
-def od_spec(n_classes=2):
+OD_CHANNELS = (3, 1)   # the stem's input channels: RGB images, or OverlapDetector(imagetype='gray')
+
+
+def od_spec(n_classes=2, channels=3):
     """[(name, shape, role)] in packed order for OD-NET with a K-way head (its last item; 2: the deployed
-    timit2.0 model, 3: the reference's research models, overlap_detector.py:394)."""
+    timit2.0 model, 3: the reference's research models, overlap_detector.py:394) on images of `channels`
+    channels (3; 1: imagetype='gray', whose stem is Conv2D(16, 1) on one channel, overlap_detector.py:84-90)."""
     if not 2 <= int(n_classes) <= OD_MAX_CLASSES:
         raise ValueError(f'OD n_classes {n_classes} outside [2, {OD_MAX_CLASSES}]')
-    s = _conv(0, (1, 1, 3, 16))
+    if int(channels) not in OD_CHANNELS:
+        raise ValueError(f'OD channels {channels}: expected 3 or 1')
+    s = _conv(0, (1, 1, int(channels), 16))
     k = 1
     cin = 16
     for c, pool in zip(CHANNELS, POOL):
@@ -95,9 +101,9 @@ def si_spec(n_classes=630):
     return s
 
 
-def spec(kind, n_classes=None):
+def spec(kind, n_classes=None, channels=3):
     if kind == OD:
-        return od_spec(2 if n_classes is None else n_classes)
+        return od_spec(2 if n_classes is None else n_classes, channels)
     return si_spec(630 if n_classes is None else n_classes)
 
 
@@ -129,12 +135,29 @@ def od_classes_of(n_floats):
     return k
 
 
+def od_layout_of(n_floats):
+    """(K, channels) of a packed OD blob of n_floats.  A one-channel blob is 32 floats (two rows of the stem
+    kernel) shorter than the three-channel blob of its K, and 513 K - 32 is no multiple of 513: no two
+    layouts share a size.  ValueError for any other size."""
+    base = n_params(OD) - 513 * 2
+    for ch in OD_CHANNELS:
+        k, rest = divmod(int(n_floats) - base + (32 if ch == 1 else 0), 513)
+        if not rest and 2 <= k <= OD_MAX_CLASSES:
+            return k, ch
+    raise ValueError(f'{n_floats} floats is not an OD blob of 2..{OD_MAX_CLASSES} classes and 3 or 1 channels')
+
+
 def od_classes(W):
     """K of an OD weight dict: the width of its Dense head."""
     return int(W['layer_with_weights-41/kernel'].shape[1])
 
 
-def synthetic(kind, seed=0, n_classes=None, head_gain=None):
+def od_channels(W):
+    """Input channels of an OD weight dict: the stem kernel's [1,1,C,16]."""
+    return int(W['layer_with_weights-0/kernel'].shape[2])
+
+
+def synthetic(kind, seed=0, n_classes=None, head_gain=None, channels=3):
     """Seeded synthetic weights in the reference layout.
 
     Kernels are Glorot-uniform (the Keras default the reference trains from), recurrent kernels
@@ -152,7 +175,7 @@ def synthetic(kind, seed=0, n_classes=None, head_gain=None):
     m2 = 2.0e4 if kind == OD else 150.0     # second moment of the network input
     stem_gain = None
     act_m2 = 0.6                              # E[act(bn(x))^2] for unit-variance BN output
-    items = spec(kind, n_classes)
+    items = spec(kind, n_classes, channels)
     i = 0
     cur = m2
     resid = None
@@ -214,11 +237,12 @@ def initial(kind, seed=0, n_classes=None):
     return _initial(spec(kind, n_classes), 0x696E6974 + 7919 * int(seed))
 
 
-def initial_od(seed=0, n_classes=2):
+def initial_od(seed=0, n_classes=2, channels=3):
     """The Keras initial state of ``__ResBLSTM`` (overlap_detector.py:362-390), what ``train_model`` starts
     from: the same initialisers as ``initial`` over ``od_spec(n_classes)``, with numpy's draws from a stream
-    of its own.  The head is the last draw, so every other tensor is the two-class draw bit for bit."""
-    return _initial(od_spec(n_classes), 0x696E6F64 + 7919 * int(seed))
+    of its own.  The head is the last draw, so every other tensor is the two-class draw bit for bit.
+    channels=1: the one-channel stem of imagetype='gray' (the first draw, so the other tensors differ)."""
+    return _initial(od_spec(n_classes, channels), 0x696E6F64 + 7919 * int(seed))
 
 
 def _initial(items, stream):
@@ -239,9 +263,9 @@ def _initial(items, stream):
     return {k: np.asarray(v, dtype=np.float32) for k, v in W.items()}
 
 
-def check(kind, W, n_classes=None):
+def check(kind, W, n_classes=None, channels=3):
     """Raise ValueError unless W has exactly the spec's names and shapes."""
-    items = spec(kind, n_classes)
+    items = spec(kind, n_classes, channels)
     names = {n for n, _, _ in items}
     missing = [n for n in names if n not in W]
     if missing:
@@ -251,19 +275,19 @@ def check(kind, W, n_classes=None):
             raise ValueError(f'{n}: shape {tuple(W[n].shape)} != expected {s}')
 
 
-def pack(kind, W, n_classes=None):
-    """Flatten W into the canonical float32 blob for ``mmla_load_weights``."""
-    check(kind, W, n_classes)
+def pack(kind, W, n_classes=None, channels=3):
+    """Flatten W into the canonical float32 blob for ``mmla_load_weights`` (channels: the OD stem's, 3 or 1)."""
+    check(kind, W, n_classes, channels)
     return np.concatenate([np.ascontiguousarray(W[n], dtype=np.float32).ravel()
-                           for n, _, _ in spec(kind, n_classes)])
+                           for n, _, _ in spec(kind, n_classes, channels)])
 
 
-def unpack(kind, blob, n_classes=None):
+def unpack(kind, blob, n_classes=None, channels=3):
     """The inverse of ``pack``: the flat float32 blob -> {name: array} in the spec's shapes."""
     blob = np.asarray(blob, dtype=np.float32).ravel()
-    items = spec(kind, n_classes)
+    items = spec(kind, n_classes, channels)
     if blob.size != sum(int(np.prod(s)) for _, s, _ in items):
-        raise ValueError(f'blob of {blob.size} floats, the spec holds {n_params(kind, n_classes)}')
+        raise ValueError(f'blob of {blob.size} floats, the spec holds {n_params(kind, n_classes, channels)}')
     W, at = {}, 0
     for name, shape, _ in items:
         n = int(np.prod(shape))
@@ -272,5 +296,5 @@ def unpack(kind, blob, n_classes=None):
     return W
 
 
-def n_params(kind, n_classes=None):
-    return int(sum(int(np.prod(s)) for _, s, _ in spec(kind, n_classes)))
+def n_params(kind, n_classes=None, channels=3):
+    return int(sum(int(np.prod(s)) for _, s, _ in spec(kind, n_classes, channels)))
